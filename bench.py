@@ -17,8 +17,11 @@ per-step host input is only (pi, T, E) (a few KB), exactly what Forwarder.forwar
              Launched by the driver under torch.distributed.run; run directly (no WORLD_SIZE in the
              environment) it starts its own N rank processes before anything touches the GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` and, at N=1,
-`cpu_baseline` and `extra_configs` (the other BASELINE configs at their per-GPU size, a few steps each).
+Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline`.  A plain run measures the headline
+only; --full adds, at N=1, `cpu_baseline`, `extra_configs` (the other BASELINE configs at their per-GPU size, a few steps
+each) and the rank-1 hand-off counters of one more evaluation.
+--dump-outputs DIR writes what the last timed step returned (the log-likelihood, one per parameter set) as
+DIR/loglik.npy (float64); the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -58,12 +61,16 @@ def parse_args(argv=None):
     ap.add_argument("--condition-ms", type=float, default=60.0,
                     help="untimed evaluations for this many milliseconds before the W warmup steps of every timed "
                          "region: the card's clocks leave the idle state over the first ~15 ms of work (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline, at N=1: the CPU baseline, extra_configs and the rank-1 hand-off counters")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gen-workers", type=int, default=0,
                     help="processes that sample the synthetic alignments (0 = automatic: up to 16, forked before the "
                          "first GPU call - or in-process when a profiler's tool library is injected, because rocprofv3 "
                          "--pmc initialises the GPU before Python starts and a fork from such a process can hang)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs leg (profiling runs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs leg")
     ap.add_argument("--no-compress", action="store_true",
                     help="raw symbol stream (one step per alignment column), kernel chosen automatically")
     ap.add_argument("--mode", type=int, default=-1, help="imc_set_compression mode 0..5 (overrides --no-compress)")
@@ -187,6 +194,8 @@ def main():
     CONDITION_MS = args.condition_ms
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -241,7 +250,7 @@ def main():
     # ---- synthetic data: everything this process will need, generated before the GPU is touched ----
     t0 = time.time()
     requests = [("main%d" % i, key, cols, sd) for i, sd in enumerate(seeds)]
-    extras = world == 1 and not args.no_extra and not args.force_collective and args.batch == 1 and not args.fixture and workload_kind == "config2" \
+    extras = args.full and world == 1 and not args.no_extra and not args.force_collective and args.batch == 1 and not args.fixture and workload_kind == "config2" \
         and not args.no_compress and args.mode < 0 and n_states == 20 and not args.columns and not args.chunks
     if extras:
         requests += [("c3", "im150_t0", 100_000_000, 20240002)]
@@ -308,9 +317,9 @@ def main():
     if args.batch > 1:
         pis, Ts, Es, model_build_ms = proposals(d, key, n_states, args.batch, T)
 
-    def step():
+    def step():                         # returns what a caller of the path receives
         if args.batch > 1:
-            return float(ll.forward_params_batch(pis, Ts, Es)[0])
+            return ll.forward_params_batch(pis, Ts, Es)
         return ll.forward_params(pi, T, E)
 
     def fence():
@@ -333,10 +342,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return bool(int(t.item()))
 
-    value, elapsed, k_ms, s_ms = timed_steps(lib, step, args.steps, args.warmup, fence, agree if world > 1 else None)
+    output, elapsed, k_ms, s_ms = timed_steps(lib, step, args.steps, args.warmup, fence, agree if world > 1 else None)
+    value = float(output[0]) if args.batch > 1 else output
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loglik": output})
     plan = _capi.last_plan()
     rank1_stats = None
-    if world == 1 and args.batch == 1:     # one extra synchronous evaluation: the hand-off counters are read back there
+    if args.full and world == 1 and args.batch == 1:   # one more synchronous evaluation: the hand-off counters are read back there
         from imcoalhmm_amd.hmm import forward_chunks
         forward_chunks([f.handle for f in forwarders], pi, T, E)
         rank1_stats = dict(zip(("segments_tested", "collapsed"), _capi.last_rank1()))
@@ -420,7 +432,7 @@ def main():
             },
         }
         out.update(scaling_fields)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pi, T, E, first_chunk, args.cpu_sample_columns)
     if extras:
         del forwarders, ll
@@ -432,6 +444,13 @@ def main():
     if world > 1 or (dist.is_available() and dist.is_initialized()):
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: {name: what the last timed step returned} -> DIR/<name>.npy, float64, at least 1-D."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.atleast_1d(np.asarray(a, dtype=np.float64)))
 
 
 def scaling_report(torch, dist, rdev, elapsed, alone_elapsed, local_cols, batch, steps):
@@ -674,6 +693,8 @@ def rehearse_cpu(args, rank, world):
     fields = {}
     if world > 1:
         elapsed, _, fields = scaling_report(torch, dist, torch.device("cpu"), elapsed, alone_elapsed, float(len(mine)), 1, steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loglik": value})
     if rank == 0:
         rec = {"metric": "launcher rehearsal (no GPU, INVALID as a measurement)", "value": 0.0, "unit": "columns/s",
                "n_gpus": args.gpus, "ranks": ranks, "backend": "gloo" if world > 1 else None,

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(REPO, "bench.py")
 
@@ -44,6 +47,22 @@ def test_single_rank_reports_one_rank():
     assert rec["n_gpus"] == 1 and rec["ranks"] == 1 and rec["backend"] is None
 
 
+def test_dump_outputs_writes_what_the_timed_path_returned(tmp_path):
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse-cpu", "--steps", "2", "--warmup", "0",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300,
+                         env=_clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    got = np.load(str(tmp_path / "out" / "loglik.npy"))
+    assert got.dtype == np.float64 and got.tolist() == [rec["config"]["loglik"]]
+
+
+def test_steps_below_one_is_refused():
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--rehearse-cpu", "--steps", "0"], capture_output=True,
+                         text=True, timeout=120, env=_clean_env())
+    assert out.returncode != 0 and "--steps" in (out.stderr + out.stdout)
+
+
 def test_multi_rank_line_carries_its_own_single_gpu_base():
     """An N > 1 line must be judgeable by itself: the ranks' shards timed alone (no collective), the efficiency against
     that base, and every rank's step time; --strong deals a FIXED number of chunks over the ranks."""
@@ -62,3 +81,21 @@ def test_multi_rank_line_carries_its_own_single_gpu_base():
         assert len(per["per_rank"]) == 2 and per["min"] <= per["max"] and per["max"] == max(per["per_rank"])
         # rank 0's partial alone is only its own shard: chunks 0, 2, 4, ...
         assert rec["config"]["alone_partial"] == -float(sum(1000 + i for i in range(0, total, 2)))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_its_outputs_repeat(tmp_path):
+    """A plain run times the headline and nothing else (the other legs are --full's); two runs with the same arguments
+    see the same inputs, so their dumped outputs are bit-identical and equal the line's loglik."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=_clean_env())
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64"
+        assert "cpu_baseline" not in rec and "extra_configs" not in rec
+        dumps.append(np.load(str(d / "loglik.npy")))
+        assert dumps[-1].dtype == np.float64 and dumps[-1].tolist() == [rec["config"]["loglik"]]
+    assert dumps[0].tobytes() == dumps[1].tobytes()
