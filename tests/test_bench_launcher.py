@@ -11,6 +11,7 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(REPO, "bench.py")
+ORACLE_TOL = 1e-11
 
 
 def _clean_env():
@@ -99,3 +100,34 @@ def test_plain_run_is_the_headline_only_and_its_outputs_repeat(tmp_path):
         dumps.append(np.load(str(d / "loglik.npy")))
         assert dumps[-1].dtype == np.float64 and dumps[-1].tolist() == [rec["config"]["loglik"]]
     assert dumps[0].tobytes() == dumps[1].tobytes()
+    want = _bench_oracle()["headline"]["zip"]["total"][0]               # tests/golden/make_bench_oracle.py
+    assert abs(dumps[0][0] - want) < ORACLE_TOL * abs(want), (dumps[0][0], want)
+
+
+def _bench_oracle():
+    with open(os.path.join(REPO, "tests", "golden", "bench_oracle.json")) as fh:
+        return json.load(fh)["workloads"]
+
+
+@pytest.mark.gpu
+def test_variant_runs_dump_the_oracle_values(tmp_path):
+    """What bench.py returns under its workload flags equals the CPU oracle on the same inputs: config[2], the
+    config[3] slice, the headline with 64 proposals and the per-GPU slice of config[4] (all 64 proposal totals).
+    The runs go in sequence and stop at the first failing one: nothing follows a run that went wrong on the GPU."""
+    import bench_workloads as bw
+    oracle = _bench_oracle()
+    for name in ("config2", "config3_slice", "headline_b64", "pop150_slice"):
+        w = bw.WORKLOADS[name]
+        d = tmp_path / name
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--condition-ms", "0",
+                              "--dump-outputs", str(d)] + list(w.flags),
+                             capture_output=True, text=True, timeout=600, env=_clean_env())
+        assert out.returncode == 0, (name, out.returncode, out.stderr[-2000:])
+        got = np.load(str(d / "loglik.npy"))
+        want = np.array(oracle[name]["zip"]["total"])
+        assert got.shape == want.shape, (name, got.shape, want.shape)
+        err = np.abs(got - want) / np.abs(want)
+        if not err.max() < ORACLE_TOL and [bw.digest(c) for c in bw.generate(w)] != oracle[name]["sha256"]:
+            pytest.fail("inputs changed: rerun make_bench_oracle.py (%s)" % name)
+        assert err.max() < ORACLE_TOL, (name, int(err.argmax()), got[err.argmax()], want[err.argmax()])
+        print("\n[bench oracle] bench.py %s: worst rel err %.2e over %d values" % (" ".join(w.flags), err.max(), err.size))
