@@ -145,8 +145,14 @@ struct Ctx {
     bool table_pairs = true;  // IMC_TABLE_PAIRS=0: k_zpropagate4's table one dictionary depth per launch (A/B measurements)
     int table_triples = -1;   // three dictionary depths per table launch, one wavefront per token (k_z4_level3): -1 = up to 12 states
                               // (measured at 10 states: 106 vs 108 us and 113.5 vs 116 us per evaluation; at 20 states 54 vs 52.5 us for
-                              // the table - 2197 wavefronts of 125 MFMAs in the depth 7-9 launch - so pairs stay), 0 = never, 1 = always
+                              // the table - 2197 wavefronts of 125 MFMAs in the depth 7-9 launch - so pairs stay; again with the column-split
+                              // pairs: 253.3 / 256.4 vs 258.8 / 260.2 us per evaluation, profiles/table_split_sweep.txt), 0 = never, 1 = always
                               // (IMC_TABLE_TRIPLES)
+    bool table_split = true;  // IMC_TABLE_SPLIT=0: every two-depth table launch in the four-tokens-per-wavefront form (A/B measurements).
+                              // Otherwise a launch takes the column-split form (one token per wavefront, k_z4_level2<., ., W>) while it is
+                              // latency: entries x parameter sets <= table_split_max, about one wavefront per SIMD.  Beyond that the build
+                              // is throughput and the four-tokens form issues 1.6x fewer matrix instructions (at 20 states) in 4x fewer wavefronts.
+    int table_split_max = -1; // -1: four per compute unit (IMC_TABLE_SPLIT_MAX)
     bool xcd_affine = true;   // k_zpropagate4: a parameter set's workgroups all on one XCD when B is 2, 4 or a multiple of 8 (IMC_XCD_AFFINE=0: off)
     int fuse_tail = 1;        // the chunk's last workgroup finishes the chunk (zip3_tail) instead of k_chain launches: 1 = where a chunk is
                               // at most four workgroups (one in-wavefront fold; measured: 100 x 1e6 columns -1.5 us, and +6 us at 13
@@ -200,6 +206,8 @@ int ensure_ctx()
     if (const char *pt = std::getenv("IMC_PACK_TABLE")) g.pack_table = std::atoi(pt) != 0;
     if (const char *tp = std::getenv("IMC_TABLE_PAIRS")) g.table_pairs = std::atoi(tp) != 0;
     if (const char *fh = std::getenv("IMC_FUSE_HEAD")) g.fuse_head = std::atoi(fh) != 0;
+    if (const char *ts = std::getenv("IMC_TABLE_SPLIT")) g.table_split = std::atoi(ts) != 0;
+    if (const char *tm = std::getenv("IMC_TABLE_SPLIT_MAX")) g.table_split_max = std::max(0, std::atoi(tm));
     if (const char *tt = std::getenv("IMC_TABLE_TRIPLES")) g.table_triples = std::atoi(tt) != 0 ? 1 : 0;
     if (const char *ft = std::getenv("IMC_FUSE_TAIL")) g.fuse_tail = std::max(0, std::min(2, std::atoi(ft)));
     if (const char *xa = std::getenv("IMC_XCD_AFFINE")) g.xcd_affine = std::atoi(xa) != 0;
@@ -522,6 +530,8 @@ struct KernelChoice {
     void (*zip4_level)(BigArgs, int, int) = nullptr;
     void (*zip4_level2)(BigArgs, const int4 *, int, int, const double *) = nullptr;   // two dictionary depths per launch
     void (*zip4_level2_first)(BigArgs, const int4 *, int, int, const double *) = nullptr;   // ... the first one: parameters + raw operators too
+    void (*zip4_level2_split)(BigArgs, const int4 *, int, int, const double *) = nullptr;         // ... column-split form, one token per wavefront
+    void (*zip4_level2_split_first)(BigArgs, const int4 *, int, int, const double *) = nullptr;
     void (*zip4_level3)(BigArgs, const int4 *, int, int, const double *) = nullptr;        // three dictionary depths per launch
     void (*zip4_level3_first)(BigArgs, const int4 *, int, int, const double *) = nullptr;
     size_t (*zip4_level3_lds)(size_t) = nullptr;
@@ -557,6 +567,8 @@ KernelChoice make_kc()
             k.zip4_level = k_z4_level<NP / 4>;
             k.zip4_level2 = k_z4_level2<NP / 4, false>;
             k.zip4_level2_first = k_z4_level2<NP / 4, true>;
+            k.zip4_level2_split = k_z4_level2<NP / 4, false, Z4_SPLIT_WAVES>;
+            k.zip4_level2_split_first = k_z4_level2<NP / 4, true, Z4_SPLIT_WAVES_FIRST>;
             k.zip4_level3 = k_z4_level3<NP / 4, false>;
             k.zip4_level3_first = k_z4_level3<NP / 4, true>;
             k.zip4_level3_lds = &Z4L3Geom<NP / 4>::lds_bytes;
@@ -1777,6 +1789,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
     bool a_recorded = false;
     if (prof) { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); HIP_TRY(hipEventCreate(&ev.c)); }
 #define IMC_MARK_A() do { if (prof && !a_recorded) { HIP_TRY(hipEventRecord(ev.a, stream)); a_recorded = true; } } while (0)
+    bool split_used = false;            // a table launch took the column-split form
     bool tail_used = false;             // the propagate launch finishes the chunks itself (zip3_tail): no stitch launches
     p->kernels.clear();
     auto note = [&](const std::string &k) { p->kernels += (p->kernels.empty() ? "" : "+") + k; };
@@ -1920,8 +1933,19 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
                     }
                 } else if (g.table_pairs && gr.d_tab_desc2) {
                     bool head = fuse_head;
+                    const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
                     for (const auto &lc : gr.tab2) {          // two dictionary depths per launch
-                        if (head)
+                        if (g.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
+                            if (head)
+                                hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
+                                                   dim3(Z4_SPLIT_WAVES_FIRST * 64), p->pstride * 8, stream, ba,
+                                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)p->h_params_dev[p->slot]);
+                            else
+                                hipLaunchKernelGGL(kc->zip4_level2_split, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES - 1) / Z4_SPLIT_WAVES, (unsigned)B),
+                                                   dim3(Z4_SPLIT_WAVES * 64), 0, stream, ba,
+                                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)nullptr);
+                            split_used = true;
+                        } else if (head)
                             hipLaunchKernelGGL(kc->zip4_level2_first, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64),
                                                p->pstride * 8, stream, ba,
                                                (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)p->h_params_dev[p->slot]);
@@ -2012,6 +2036,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
     IMC_MARK_A();
 #undef IMC_MARK_A
     if (prof) HIP_TRY(hipEventRecord(ev.b, stream));
+    if (split_used) note("table-split");
     if (tail_used) note("fused-tail");
     for (size_t l = 0; l + 1 < p->levels.size() && !tail_used; ++l) {
         const Level &in = p->levels[l], &ot = p->levels[l + 1];

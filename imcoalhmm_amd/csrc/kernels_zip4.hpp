@@ -5,6 +5,8 @@
 //
 //   * k_z4_raw / k_z4_level<NT>: the table in global memory, one launch per dictionary depth, each token the MFMA step
 //     itself on its children's entries (four tokens per wavefront, as in k_zpropagate3's prologue).
+//     k_z4_level2: two depths per launch; its column-split form (z4_split_entry) gives a token a whole wavefront - the four
+//     MFMA blocks hold four column tiles of one product - for the launches that are latency, not throughput.
 //   * k_zpropagate4<NT>: k_zpropagate3's scan.  Every workgroup copies the H hottest operators (+ the identity) from
 //     the global table into LDS.  A step whose token is hot reads its A operands from LDS one tile-row ahead, exactly
 //     as k_zpropagate3; a step whose token is cold takes them from 25 registers per lane that were loaded from the
@@ -122,6 +124,144 @@ __global__ __launch_bounds__(64) void k_z4_level(BigArgs a, int first, int count
     }
 }
 
+// ---- the COLUMN-SPLIT form of a two-depth entry (k_z4_level2<., ., WAVES >= 1>): one token per WAVEFRONT -----------------
+// The columns of an operator product are independent, Out[:, J] = A * B[:, J], so the four blocks of the matrix
+// instruction hold four column tiles of ONE token instead of four tokens: block bq owns tile J = bq + 4 p in pass p
+// (NPASS = 1 up to NT = 4, 2 for NT = 5, 6).  Lane l = 16 q + 4 bq + r holds, per product,
+//     B[p][K]   = element (4K + q, 4J + r) of the B operand, its own column tile only           (NPASS * NT doubles)
+//     A[I][K]   = element (4I + r, 4K + q) of the A operand, ALL rows - the same addresses in all four blocks, so
+//                 the extra blocks fetch no extra cache lines                                   (NT * NT doubles)
+//     Out[p][I] = element (4I + q, 4J + r) of the product                                       (NPASS * NT doubles)
+// and every Out[p][I] is accumulated over K = 0 .. NT - 1 by the same MFMA sequence on the same operands as
+// zip4_step_regs' Pout[I][J]: the bits of an entry do not depend on the form.  A product is NPASS * NT^2 matrix
+// instructions (50 at NT = 5) instead of NT^3 (125) - a table launch is latency, and this is the length of its chain.
+// The left child's product is already the B operand of the token's own product (block J computed exactly the column
+// tile block J needs); the right child's goes column tiles -> `turn` (the wavefront's LDS area) -> A rows, read back
+// by all four blocks, still inside one wavefront.  A padding tile (J >= NT in the last pass) computes on tile 0's
+// operands, stays out of the rescale's maximum and stores nothing.  The rescale's maximum runs over the whole
+// wavefront (all six lane bits) and both passes, i.e. over the same NP^2 elements as zip3_rescale's in the
+// four-tokens form: the same power of two.
+// NL / NR: the left / right child is recomputed from the grandchildren.  One straight-line instance per flag pair, with
+// every table load of the wavefront issued before the first matrix instruction, so that the compiler counts its waits
+// (vmcnt(n)) instead of draining the queue in front of every product.
+template <int NT, bool FIRST, bool NL, bool NR>
+__device__ __forceinline__ void z4_split_entry(const BigArgs &a, double *Gt, int *Gc, double *turn, const double *lp,
+                                               int z, int zl, int zr, int ll, int lr, int rl, int rr)
+{
+    using Geo = Zip3Geom<NT>;
+    constexpr int TOK = Geo::TOK, NPASS = (NT + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
+    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const int IDENT = a.A;
+    // this lane's column tiles: where element (4K + q, 4J + r) of an entry lives is toff + K * tstr (Zip3Geom::idx)
+    int tcol[NPASS], toff[NPASS], tstr[NPASS];
+    bool tv[NPASS];
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) {
+        const int J = bq + 4 * p;
+        tv[p] = J < NT;
+        const int Jc = tv[p] ? J : 0;
+        const bool mainp = Jc < Geo::NTE;
+        tcol[p] = 4 * Jc + r;
+        toff[p] = mainp ? (r * 4 + q) * Geo::NTE + Jc : Geo::MAIN + r * 4 + q;
+        tstr[p] = mainp ? 16 * Geo::NTE : 16;
+    }
+    auto leaf = [&](int tok, int i, int j) __attribute__((always_inline)) {
+        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
+        const double v = Etg[(size_t)(tok == IDENT ? 0 : tok) * a.PP + i] * Tp[(size_t)j * a.PP + i];
+        return tok == IDENT ? (i == j ? 1.0 : 0.0) : v;
+    };
+    auto expo = [&](int tok) __attribute__((always_inline)) { if constexpr (FIRST) return 0; else return Gc[tok]; };
+    auto load_B = [&](double (&Bt)[NPASS][NT], int tok) __attribute__((always_inline)) {
+        const double *G = Gt + (size_t)tok * TOK;
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+            for (int K = 0; K < NT; ++K) {
+                if constexpr (FIRST) Bt[p][K] = leaf(tok, 4 * K + q, tcol[p]);
+                else Bt[p][K] = G[toff[p] + K * tstr[p]];
+            }
+    };
+    auto load_A = [&](double (&Ar)[NT][NT], int tok) __attribute__((always_inline)) {     // Ar[I][K] = C[4I + r][4K + q]
+        const double *G = Gt + (size_t)tok * TOK;
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            if constexpr (FIRST) {
+#pragma unroll
+                for (int K = 0; K < NT; ++K) Ar[I][K] = leaf(tok, 4 * I + r, 4 * K + q);
+            } else zip4_load_row_global<NT>(Ar[I], G, I, lo, lx);
+        }
+    };
+    // Out[p][I] <- sum over K of Ar[I][K] * Bt[p][K] (K ascending per accumulator; neighbours in issue order are independent)
+    auto product = [&](const double (&Bt)[NPASS][NT], double (&Out)[NPASS][NT], const double (&Ar)[NT][NT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int K = 0; K < NT; ++K)
+#pragma unroll
+            for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+                for (int I = 0; I < NT; ++I)
+                    Out[p][I] = __builtin_amdgcn_mfma_f64_4x4x4f64(Ar[I][K], Bt[p][K], K == 0 ? 0.0 : Out[p][I], 0, 0, 0);
+    };
+
+    // ---- every load of the wavefront ----
+    double LB[NPASS][NT], LA[NT][NT], RB[NPASS][NT], RA[NT][NT];
+    int eL, eR;
+    if constexpr (NL) { load_B(LB, ll); load_A(LA, lr); eL = expo(ll) + expo(lr); }     // L = C_lr * C_ll
+    else { load_B(LB, zl); eL = expo(zl); }
+    if constexpr (NR) { load_B(RB, rl); load_A(RA, rr); eR = expo(rl) + expo(rr); }     // R = C_rr * C_rl
+    else { load_A(RA, zr); eR = expo(zr); }
+    // ---- left child: the token's B operand ----
+    double L[NPASS][NT];
+    if constexpr (NL) product(LB, L, LA);
+    else {
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+            for (int K = 0; K < NT; ++K) L[p][K] = LB[p][K];
+    }
+    // ---- right child: the token's A operand rows ----
+    double R[NT][NT];
+    if constexpr (NR) {
+        double Rt[NPASS][NT];
+        product(RB, Rt, RA);
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+            for (int I = 0; I < NT; ++I)
+                if (tv[p]) turn[toff[p] + I * tstr[p]] = Rt[p][I];
+        wave_fence();
+#pragma unroll
+        for (int I = 0; I < NT; ++I) zip3_load_row<NT>(R[I], turn, I, lo, lx);
+    } else {
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int K = 0; K < NT; ++K) R[I][K] = RA[I][K];
+    }
+    // ---- the token itself ----
+    double Out[NPASS][NT];
+    product(L, Out, R);
+    // zip3_rescale's rule over the token's NP^2 elements: they are spread over the 64 lanes and the passes
+    int hmax = 0;
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+        for (int I = 0; I < NT; ++I) hmax = max(hmax, tv[p] ? __double2hiint(Out[p][I]) & 0x7fffffff : 0);
+    const int field = hmax >> 20;
+    int e = field == 0 ? INT_MIN : field == 0x7ff ? INT_MAX : field - 1022;
+#pragma unroll
+    for (int m = 1; m <= 32; m *= 2) e = max(e, __shfl_xor(e, m, 64));
+    e = (e == INT_MAX || e == INT_MIN) ? 0 : e;
+    double *Gz = Gt + (size_t)z * TOK;
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+            if (tv[p]) Gz[toff[p] + I * tstr[p]] = ldexp(Out[p][I], -e);
+    if (lane == 0) Gc[z] = eL + eR + e;
+}
+
 // TWO dictionary depths per launch.  A token of the second depth has at least one child in the first, which a sibling
 // workgroup of the same launch is only just building - so the wavefront RECOMPUTES that child from the grandchildren
 // (both older than the launch), keeps the product in registers (a left child: a result tile is already in the layout
@@ -139,51 +279,84 @@ __global__ __launch_bounds__(64) void k_z4_level(BigArgs a, int first, int count
 // never reads the table; workgroup 0 also writes the raw entries and the identity into the table and the parameters into
 // a.params for the launches that follow.  This replaces k_stage_params + k_z4_raw + the two host-paced gaps between
 // three very short kernels (rocprofv3 timeline, profiles/r03_trace_config1.txt: 3.4 + 4.0 + 2.4 + 3.8 us).
-template <int NT, bool FIRST>
-__global__ __launch_bounds__(64) void k_z4_level2(BigArgs a, const int4 *desc2, int first, int count, const double *params_src)
+// SPLIT = 0: four tokens per wavefront as described above, one wavefront per workgroup.  SPLIT = W >= 1: the column-split
+// form, one token per wavefront (z4_split_entry), W wavefronts per workgroup; it reads the same entries (a padding entry's
+// wavefront has nothing to do).  The host takes it for the launches that are latency, not throughput (table_split).
+constexpr int Z4_SPLIT_WAVES = 1;          // wavefronts (= tokens) per workgroup of the split form: spread over as many CUs as there are tokens ...
+constexpr int Z4_SPLIT_WAVES_FIRST = 4;    // ... but the first launch's workgroups each fetch the parameter set from host memory: no more of them than before
+template <int NT, bool FIRST, int SPLIT = 0>
+__global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs a, const int4 *desc2, int first, int count, const double *params_src)
 {
     using Geo = Zip3Geom<NT>;
-    constexpr int TOK = Geo::TOK, NP = Geo::NP;
-    __shared__ __attribute__((aligned(16))) double turn[4 * TOK];          // one entry per MFMA block: D layout in, A rows out
+    constexpr int TOK = Geo::TOK, NP = Geo::NP, WAVES = SPLIT ? SPLIT : 1, THREADS = WAVES * 64;
+    // SPLIT = 0: one entry per MFMA block, D layout in, A rows out; else one entry per wavefront
+    __shared__ __attribute__((aligned(16))) double turn[(SPLIT ? WAVES : 4) * TOK];
     extern __shared__ __attribute__((aligned(16))) double rawtab[];        // FIRST: the parameter set (a.pstride doubles)
-    const int b = blockIdx.y, lane = threadIdx.x;
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
     const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
     double *Gt = a.Ctab + (size_t)b * (a.A + 1) * TOK;
     int *Gc = a.cex + (size_t)b * (a.A + 1);
     const int IDENT = a.A;
-    if constexpr (FIRST) {
-        const double *src = params_src + (size_t)b * a.pstride;
-        double *lp = rawtab;                                               // a.pstride doubles (even)
-        // (all of a lane's loads in flight together: `src` is host memory, ~2 us per round trip over PCIe)
-        for (int k0 = 0; k0 < (int)a.pstride; k0 += 8 * 128) {
-            double2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + u * 128 + lane * 2;
-                v[u] = k < (int)a.pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + u * 128 + lane * 2;
-                if (k < (int)a.pstride) *reinterpret_cast<double2 *>(lp + k) = v[u];
-            }
-        }
-        wave_fence();
-        if (blockIdx.x == 0) {                                            // (wavefront-uniform)
+    // split form: this wavefront's entry, requested ahead of the parameter fetch (the two round trips overlap)
+    const int wti = blockIdx.x * WAVES + (tid >> 6);                      // (wavefront-uniform)
+    int4 e0 = make_int4(-1, 0, 0, 0), e1 = make_int4(0, 0, 0, 0);
+    if constexpr (SPLIT != 0) {
+        if (wti < count) { e0 = desc2[2 * (first + wti)]; e1 = desc2[2 * (first + wti) + 1]; }
+    }
+    // FIRST: the parameters and the table's raw entries for the launches that follow (the split form writes them behind its own entry)
+    auto publish = [&]() __attribute__((always_inline)) {
+        const double *lp = rawtab;
+        if (blockIdx.x == 0) {                                            // (workgroup-uniform)
             double *dp = const_cast<double *>(a.params) + (size_t)b * a.pstride;
-            for (int k = lane * 2; k < (int)a.pstride; k += 128) *reinterpret_cast<double2 *>(dp + k) = *reinterpret_cast<const double2 *>(lp + k);
+            for (int k = tid * 2; k < (int)a.pstride; k += 2 * THREADS) *reinterpret_cast<double2 *>(dp + k) = *reinterpret_cast<const double2 *>(lp + k);
         }
         // the table's raw entries and the identity, dealt over the launch's workgroups (later launches read them)
         const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
         for (int s = blockIdx.x; s <= a.S; s += gridDim.x) {
             double *Gz = Gt + (size_t)(s < a.S ? s : IDENT) * TOK;
-            for (int idx = lane; idx < NP * NP; idx += 64) {
+            for (int idx = tid; idx < NP * NP; idx += THREADS) {
                 const int i = idx / NP, j = idx - i * NP;
                 Gz[Geo::idx(i, j)] = s < a.S ? Etg[(size_t)s * a.PP + i] * Tp[(size_t)j * a.PP + i] : (i == j ? 1.0 : 0.0);
             }
-            if (lane == 0) Gc[s < a.S ? s : IDENT] = 0;
+            if (tid == 0) Gc[s < a.S ? s : IDENT] = 0;
         }
+    };
+    if constexpr (FIRST) {
+        const double *src = params_src + (size_t)b * a.pstride;
+        double *lp = rawtab;                                               // a.pstride doubles (even)
+        // (all of a lane's loads in flight together: `src` is host memory, ~2 us per round trip over PCIe)
+        for (int k0 = 0; k0 < (int)a.pstride; k0 += 8 * 2 * THREADS) {
+            double2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k = k0 + (u * THREADS + tid) * 2;
+                v[u] = k < (int)a.pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k = k0 + (u * THREADS + tid) * 2;
+                if (k < (int)a.pstride) *reinterpret_cast<double2 *>(lp + k) = v[u];
+            }
+        }
+        if constexpr (WAVES > 1) __syncthreads();
+        else wave_fence();
+        if constexpr (SPLIT == 0) publish();
+    }
+    if constexpr (SPLIT != 0) {
+        const int z = __builtin_amdgcn_readfirstlane(e0.x);
+        if (z >= 0) {                                                     // (-1: beyond the launch, or a padding entry of the four-tokens form)
+            const int zl = __builtin_amdgcn_readfirstlane(e0.y), zr = __builtin_amdgcn_readfirstlane(e0.z), fl = __builtin_amdgcn_readfirstlane(e0.w);
+            const int ll = __builtin_amdgcn_readfirstlane(e1.x), lr = __builtin_amdgcn_readfirstlane(e1.y);
+            const int rl = __builtin_amdgcn_readfirstlane(e1.z), rr = __builtin_amdgcn_readfirstlane(e1.w);
+            double *mine = turn + (size_t)(tid >> 6) * TOK;
+            if (fl == 3) z4_split_entry<NT, FIRST, true, true>(a, Gt, Gc, mine, rawtab, z, zl, zr, ll, lr, rl, rr);
+            else if (fl == 2) z4_split_entry<NT, FIRST, false, true>(a, Gt, Gc, mine, rawtab, z, zl, zr, ll, lr, rl, rr);
+            else if (fl == 1) z4_split_entry<NT, FIRST, true, false>(a, Gt, Gc, mine, rawtab, z, zl, zr, ll, lr, rl, rr);
+            else z4_split_entry<NT, FIRST, false, false>(a, Gt, Gc, mine, rawtab, z, zl, zr, ll, lr, rl, rr);
+        }
+        if constexpr (FIRST) publish();
+        return;
     }
     const int ti = blockIdx.x * 4 + bq;
     int4 d0 = ti < count ? desc2[2 * (first + ti)] : make_int4(-1, 0, 0, 0);
