@@ -71,6 +71,7 @@ SIGNATURES = [
     ("imc_set_rank1_handoff", ctypes.c_int, [ctypes.c_int]),
     ("imc_set_blocked_kernel", ctypes.c_int, [ctypes.c_int]),
     ("imc_set_table_streaming", ctypes.c_int, [ctypes.c_int]),
+    ("imc_set_wide_blocked", ctypes.c_int, [ctypes.c_int]),
     ("imc_obs_recompress", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("imc_last_plan", ctypes.c_int, [_u64p]),
     ("imc_last_kernels", ctypes.c_char_p, []),
@@ -167,6 +168,12 @@ def last_rank1():
     a, b = ctypes.c_uint64(), ctypes.c_uint64()
     check(lib().imc_last_rank1(ctypes.byref(a), ctypes.byref(b)))
     return int(a.value), int(b.value)
+
+
+def set_wide_blocked(mode):
+    """25-32 states on the register-blocked fp64-MFMA scan (k_zpropagate4<7 | 8>): -1 = where the planner's estimate
+    prefers it (default), 0 = never, 1 = wherever every dictionary of the call has a token level the scan can run."""
+    check(lib().imc_set_wide_blocked(int(mode)))
 
 
 def last_plan():

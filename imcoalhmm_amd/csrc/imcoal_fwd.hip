@@ -140,6 +140,10 @@ struct Ctx {
                               // (k_zpropagate4) and the LDS table otherwise (k_zpropagate3); 3 = LDS table only;
                               // 5 = hybrid wherever it is possible (tests); 2 = k_zpropagate2 (DPP, VALU).
                               // IMC_BLOCKED=2|3|4|5 at start-up
+    int wide_blocked = -1;    // 25-32 states on the blocked MFMA scan (k_zpropagate4<7 | 8>, four wavefronts per workgroup, streamed
+                              // table) instead of the vector / GEMM-chain kernels: -1 = where the cost model prefers it, 0 = never,
+                              // 1 = wherever every dictionary of the call has a token level the scan can run (IMC_WIDE_BLOCKED).
+                              // Automatic mode only (imc_set_compression(1)): the pinned modes keep their kernels.
     int z4_stream = -1;       // k_zpropagate4's table: -1 = streamed (nothing cached in LDS) while the launch's tables are
                               // cache resident, 0 = always the hybrid LDS cache, 1 = always streamed (IMC_Z4_STREAM)
     bool table_pairs = true;  // IMC_TABLE_PAIRS=0: k_zpropagate4's table one dictionary depth per launch (A/B measurements)
@@ -211,6 +215,7 @@ int ensure_ctx()
     if (const char *tt = std::getenv("IMC_TABLE_TRIPLES")) g.table_triples = std::atoi(tt) != 0 ? 1 : 0;
     if (const char *ft = std::getenv("IMC_FUSE_TAIL")) g.fuse_tail = std::max(0, std::min(2, std::atoi(ft)));
     if (const char *xa = std::getenv("IMC_XCD_AFFINE")) g.xcd_affine = std::atoi(xa) != 0;
+    if (const char *wb = std::getenv("IMC_WIDE_BLOCKED")) { const int v = std::atoi(wb); if (v >= -1 && v <= 1) g.wide_blocked = v; }
     if (const char *zs = std::getenv("IMC_Z4_STREAM")) { const int v = std::atoi(zs); if (v >= -1 && v <= 1) g.z4_stream = v; }
     g.pid = me;
     g.ready = true;
@@ -538,6 +543,9 @@ struct KernelChoice {
     size_t (*zip4_lds)(int, int) = nullptr;
     int (*zip4_max_hot)(int, size_t) = nullptr;
     int tok_doubles = 0;               // doubles per table entry of the MFMA kernels
+    int z4_waves = Z2WAVES;            // wavefronts per workgroup of the blocked scan (Zip4Shape); segments per workgroup = 4 x
+    bool wide_blocked = false;         // 25-32 states: of the blocked family only the streamed scan and the one-depth table build exist
+    int z4_slots() const { return z4_waves * 4; }
     bool chain_self_emax = false;      // the stitch kernel finds the units' largest exponents itself (no k_emax launch)
     bool zip4_attr_set = false, zip4w_attr_set = false, zip4s_attr_set = false, zip4sw_attr_set = false, zip4_attr_l3 = false;
     // the blocked kernel in use (g.blocked_variant) and its LDS need for an alphabet of A tokens
@@ -575,6 +583,16 @@ KernelChoice make_kc()
             k.zip4_lds = &Zip4Geom<NP / 4>::lds_bytes;
             k.zip4_max_hot = &Zip4Geom<NP / 4>::max_hot;
         }
+    }
+    if constexpr (NP == 28 || NP == 32) {   // streamed scan only, four wavefronts per workgroup (PlanBuilder::wide)
+        k.tok_doubles = Zip3Geom<NP / 4>::TOK;
+        k.zip4s = k_zpropagate4<NP / 4, false, false>;
+        k.zip4sw = k_zpropagate4<NP / 4, true, false>;
+        k.zip4_raw = k_z4_raw<NP / 4>;
+        k.zip4_level = k_z4_level<NP / 4>;
+        k.zip4_lds = &Zip4Geom<NP / 4>::lds_bytes;
+        k.z4_waves = Zip4Shape<NP / 4>::WAVES;
+        k.wide_blocked = true;
     }
     return k;
 }
@@ -677,6 +695,7 @@ struct Group {             // one propagate launch
     std::vector<int> chunks;
     uint32_t vec_begin = 0, n_vecs = 0;
     size_t seglen = 0;
+    double model_us = 0.0, model_tab_us = 0.0;   // the planner's estimate for this group's launches and the table's part of it (dictionary groups; compared by build_plan)
     uint64_t vsteps = 0;   // executed vector-steps per parameter set (columns or tokens)
     uint64_t stream_len = 0;
 };
@@ -698,6 +717,7 @@ struct Level {             // one level of the stitch hierarchy (level 0 = propa
 struct Plan {
     std::vector<uint64_t> key;
     KernelChoice *kc = nullptr;
+    bool wide = false;               // 25-32 states on the blocked scan (PlanBuilder::wide)
     int N = 0, S = 0, B = 0, n_chunks = 0;
     uint32_t n_segs = 0, n_vecs = 0;
     std::vector<Group> groups;
@@ -860,6 +880,10 @@ struct PlanBuilder {
     int n_chunks = 0, N = 0, S = 0, B = 0;
     bool op_mode = false;               // imc_forward_state(as_operator): no segment is a chunk's "first"
     KernelChoice *kc = nullptr;
+    // 25-32 states: kc is the vector kernels' entry and every dictionary's chunks run its streamed blocked scan
+    // (k_zpropagate4<7 | 8>); chunks without tokens stay on the vector kernels.  wide_ok: every dictionary had a level for it.
+    bool wide = false, wide_ok = true;
+    bool mfma() const { return kc->use3() || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
     std::unique_ptr<Plan> p;
     bool big = false;                   // GEMM-chain / mat-vec chain kernels (global-memory operator table)
     std::vector<int> chunk_group;       // chunk -> index into p->groups
@@ -906,7 +930,9 @@ struct PlanBuilder {
         // the operator table per evaluation ((A - S) dependent small products), which dominates on short inputs.
         // Estimate: table build + main loop with all 16-lane rows of the machine busy.
         std::map<const DictDev *, int> dict_level;
-        const bool mfma_blocked = !big && kc->use3() && g.kernel_pref != 1;
+        const bool mfma_blocked = !big && mfma() && g.kernel_pref != 1;
+        const int SL = kc->z4_slots();   // segments per workgroup of the blocked kernels
+        std::map<const DictDev *, double> dict_cost, dict_tab;     // per dictionary, microseconds: the chosen level's estimate, its table part
         if (g.compression) {
             std::map<const DictDev *, std::vector<int>> by_dict;
             for (int f = 0; f < n_chunks; ++f)
@@ -923,11 +949,12 @@ struct PlanBuilder {
                         // one workgroup builds it in L2, steps on tokens outside the LDS-cached hot set cost ~12 % more).
                         const int A = o0->alphabet[l];
                         if (!(A > o0->nsym && A <= HYBRID_MAX_ALPHABET && o0->d_tok[l]) || o0->wide_raw) continue;
-                        const bool fits = !o0->wide[l] && kc->blocked_lds(A) <= LDS_BUDGET;   // (k_zpropagate3 reads byte streams)
+                        const bool fits = !wide && !o0->wide[l] && kc->blocked_lds(A) <= LDS_BUDGET;   // (k_zpropagate3 reads byte streams)
                         const int max_hot = kc->zip4 ? kc->zip4_max_hot(A, LDS_BUDGET) : 0;
                         const double table_bytes = (double)B * (A + 1) * kc->tok_doubles * 8.0;
-                        const bool hybrid_ok = !fits && kc->zip4 && g.blocked_variant >= 4 && max_hot >= 8 && !o0->tok_count[l].empty() &&
-                                               table_bytes <= 2.0e9;
+                        // (25-32 states: the streamed form or nothing - a table it does not take stays off this path)
+                        const bool hybrid_ok = !fits && !o0->tok_count[l].empty() && table_bytes <= 2.0e9 &&
+                                               (wide ? kc->zip4s && z4_streamed(table_bytes, B) : kc->zip4 && g.blocked_variant >= 4 && max_hot >= 8);
                         if (!fits && !hybrid_ok) continue;
                         // (the scan's LDS: the fold's exchange area + the exponents and slot map of all A + 1 entries - at 24
                         // states the exchange area alone is 152 KB and levels beyond 768 tokens do not fit)
@@ -936,12 +963,13 @@ struct PlanBuilder {
                         {
                             std::map<int, int> per_depth;
                             for (int z = o0->nsym; z < A; ++z) per_depth[kv.first->depth[z]]++;
-                            for (auto &pd : per_depth) passes += (pd.second + (int)Z2SLOTS - 1) / (int)Z2SLOTS;
+                            for (auto &pd : per_depth) passes += (pd.second + SL - 1) / SL;
                         }
                         // (up to 8 states a step is not MFMA time: measured round 3, 4 and 8 states, 64 sets - 0.08 / 0.14 us from
                         // the LDS table, 0.19 / 0.22 from the global one; from 12 states on both follow the instruction count)
                         const double nt = kc->NP / 4.0;
-                        const double t_step = nt < 1.5 ? 0.08 : nt < 2.5 ? 0.14 : std::max(0.25, 1.88 * nt * nt * nt / 125.0);
+                        // (a workgroup's step: its wavefronts share the SIMDs' matrix pipes two by two - or, four wavefronts, have one each)
+                        const double t_step = nt < 1.5 ? 0.08 : nt < 2.5 ? 0.14 : std::max(0.25, 1.88 * nt * nt * nt / 125.0) * (kc->z4_waves / 8.0);
                         const double t_step_g = nt < 1.5 ? 0.19 : nt < 2.5 ? 0.22 : t_step;
                         // Time of the scan itself: workgroups of 32 segments are dealt PER CHUNK (a chunk of u workgroups is cut
                         // into 32 u segments), and a launch of more workgroups than CUs runs in rounds, each paying the
@@ -951,14 +979,14 @@ struct PlanBuilder {
                         for (int f : kv.second) maxtok = std::max(maxtok, (double)chunks[f]->ntok[l]);
                         // (up to 12 states two workgroups of the global-table kernel share a CU: twice the slots, 1.85x the step)
                         const bool two_per_cu = !fits && kc->NP <= 12 && z4_streamed(table_bytes, B);
-                        const double n_ch = (double)kv.second.size(), slots = (double)g.cus * Z2SLOTS * (two_per_cu ? 2.0 : 1.0);
+                        const double n_ch = (double)kv.second.size(), slots = (double)g.cus * SL * (two_per_cu ? 2.0 : 1.0);
                         auto scan_time = [&](double fixed_us, double step_us) {
                             if (two_per_cu) step_us *= 1.85;
                             double best_t = 1e300;
                             for (int r = 1; r <= 6; ++r) {
-                                const double units = std::max(1.0, std::floor(slots * r / (n_ch * B) / Z2SLOTS));
-                                const double seg = std::max(16.0, std::ceil(maxtok / (Z2SLOTS * units)));
-                                const double rounds = std::ceil(n_ch * B * units * Z2SLOTS / slots);
+                                const double units = std::max(1.0, std::floor(slots * r / (n_ch * B) / SL));
+                                const double seg = std::max(16.0, std::ceil(maxtok / (SL * units)));
+                                const double rounds = std::ceil(n_ch * B * units * SL / slots);
                                 best_t = std::min(best_t, rounds * (fixed_us + seg * step_us));
                             }
                             return best_t;
@@ -987,12 +1015,13 @@ struct PlanBuilder {
                             const bool streamed = z4_streamed(table_bytes, B);
                             // (table: one ~4.5 us launch per depth, or one ~5.7 us launch per pair of depths)
                             // (measured round 3: the first launch - it fetches the parameters - ~13 us, the others ~7.5)
-                            double t_table = g.table_pairs ? 13.0 + (std::ceil(depths / 2.0) - 1.0) * 7.5 : 6.0 + depths * 4.9;
+                            double t_table = g.table_pairs && kc->zip4_level2 ? 13.0 + (std::ceil(depths / 2.0) - 1.0) * 7.5 : 6.0 + depths * 4.9;
                             // ... which is latency; B tables of A operators are also two reads and a write of an operator per
                             // token and parameter set, at ~2.8 TB/s (measured round 3, 64 sets: 4096- against 512-token tables)
                             t_table += std::max(0.0, table_bytes * 3.0 / 2.8e6 - 0.5 * t_table);
                             cost = t_table + scan_time(8.0, t_step_g * (streamed ? 1.06 : 1.0 + cold_pen * cold));
                         }
+                        if (cost < best) dict_cost[kv.first] = cost;
                         if (g.blocked_variant == 5 && !fits) cost *= 1e-3;      // tests: the hybrid table wherever it is possible
                         if (std::getenv("IMC_DEBUG_LEVELS"))
                             std::fprintf(stderr, "[imc] level %d alphabet %d %s: model %.1f us\n", l, A,
@@ -1019,17 +1048,18 @@ struct PlanBuilder {
                         c_tab = (o0->alphabet[l] - S) * (400.0 + n3 / 64.0);
                         c_main = std::max(16.0, toks * B / ((double)g.cus * 32.0)) * 0.65 * n3;
                     }
-                    if (c_tab + c_main < best) { best = c_tab + c_main; best_l = l; }
+                    if (c_tab + c_main < best) { best = c_tab + c_main; best_l = l; dict_cost[kv.first] = best / 2200.0; dict_tab[kv.first] = c_tab / 2200.0; }
                 }
                 if (const char *fl = std::getenv("IMC_FORCE_LEVEL")) {   // experiments only: pin the dictionary level index
                     const int l = std::atoi(fl);
                     const imc_obs *o0 = chunks[kv.second[0]];
-                    const bool hybrid = mfma_blocked && kc->zip4 && g.blocked_variant >= 4 && !o0->wide_raw;
+                    const bool hybrid = mfma_blocked && (wide || (kc->zip4 && g.blocked_variant >= 4)) && !o0->wide_raw;
                     const int amax_forced = hybrid ? HYBRID_MAX_ALPHABET : a_max;
-                    if (l >= 0 && l < imc::kNumLevels && o0->alphabet[l] <= amax_forced && !(hybrid && kc->blocked_lds(o0->alphabet[l]) > LDS_BUDGET && kc->zip4_lds(o0->alphabet[l], 0) > LDS_BUDGET) && o0->alphabet[l] > o0->nsym && o0->d_tok[l] &&
+                    if (l >= 0 && l < imc::kNumLevels && o0->alphabet[l] <= amax_forced && !(hybrid && (wide || kc->blocked_lds(o0->alphabet[l]) > LDS_BUDGET) && kc->zip4_lds(o0->alphabet[l], 0) > LDS_BUDGET) && o0->alphabet[l] > o0->nsym && o0->d_tok[l] &&
                         (hybrid ? !o0->tok_count[l].empty() : !o0->wide[l])) best_l = l;
                 }
                 dict_level[kv.first] = best_l;
+                if (wide && best_l < 0) wide_ok = false;
             }
         }
         chunk_group.assign(n_chunks, -1);
@@ -1053,7 +1083,8 @@ struct PlanBuilder {
                 gr.A = S;
                 if (gr.zip) { gr.dict = o->dict; gr.A = o->alphabet[level]; }
                 // an alphabet beyond LDS can only have been chosen for the hybrid-table kernel
-                gr.zip4 = gr.zip && mfma_blocked && (kc->blocked_lds(gr.A) > LDS_BUDGET || o->wide[level]);
+                gr.zip4 = gr.zip && mfma_blocked && (wide || kc->blocked_lds(gr.A) > LDS_BUDGET || o->wide[level]);
+                if (gr.zip) { gr.model_us = dict_cost[o->dict.get()]; gr.model_tab_us = dict_tab[o->dict.get()]; }
                 gr.wide_tokens = gr.zip && o->wide[level];
                 p->groups.push_back(gr);
                 gi = (int)p->groups.size() - 1;
@@ -1109,6 +1140,8 @@ struct PlanBuilder {
                     gr.bigvec = true;
                     gr.seglen = std::max<size_t>(16, round_up(lmax, 16));
                 }
+                // (build_plan's comparison: the level estimate's table part + this, the refined estimate of the chain that was taken)
+                if (gr.zip) gr.model_us = gr.model_tab_us + (gr.bigvec ? cost_vec : cost_gemm) / 2200.0;
             } else {
                 // vector kernel (one vector per lane group) ...
                 double cost_vec = 0.0;
@@ -1125,7 +1158,8 @@ struct PlanBuilder {
                 gr.seglen = seg_vec;
                 // ... or the register-blocked kernel (one operator per 16-lane row): fill every row of the machine
                 // once; first segments waste 1 - 1/N of their row, which the cost comparison accounts for
-                if (kc->zip2 && g.kernel_pref != 1 && (kc->blocked_lds(gr.A) <= LDS_BUDGET || gr.zip4) && (gr.zip || (S == gr.A && S <= imc::kByteAlphabet))) {
+                if ((kc->zip2 || (wide && gr.zip4)) && g.kernel_pref != 1 && (gr.zip4 || kc->blocked_lds(gr.A) <= LDS_BUDGET) && (gr.zip || (S == gr.A && S <= imc::kByteAlphabet))) {
+                    const int SL = kc->z4_slots(), WV = kc->z4_waves;   // segments / wavefronts per workgroup
                     size_t total = 0;
                     for (size_t L : lens) total += L;
                     // Up to 12 states the global-table kernel needs 124 registers and no LDS to speak of: TWO workgroups share a
@@ -1134,25 +1168,25 @@ struct PlanBuilder {
                     // of 104-token segments 113 us).
                     const bool two_per_cu = gr.zip4 && kc->use3() && kc->NP <= 12 &&
                                             z4_streamed((double)B * (gr.A + 1) * kc->tok_doubles * 8.0, B);
-                    const double rows = (double)g.cus * Z2WAVES * 4 * (two_per_cu ? 2.0 : 1.0);
+                    const double rows = (double)g.cus * SL * (two_per_cu ? 2.0 : 1.0);
                     const double rb = kc->NP / 4.0;
                     // per wavefront-step (4 segments): DPP/VALU form measured ~2900 at N=20; the MFMA form issues
                     // (NP/4)^3 v_mfma_f64_4x4x4 at ~25.5 cycles each with two wavefronts per SIMD and nothing else
-                    const double step_cycles = (kc->use3() ? 25.5 * rb * rb * rb * 0.55 : 5.8 * rb * rb * kc->NP) * (two_per_cu ? 1.85 : 1.0);
+                    const double step_cycles = (mfma() ? 25.5 * rb * rb * rb * 0.55 : 5.8 * rb * rb * kc->NP) * (two_per_cu ? 1.85 : 1.0);
                     size_t seg_blk = 16;
                     double slots = 0.0, cost_blk = 1e300;
                     // a workgroup takes 32 consecutive segments of ONE chunk: rows are allocated per chunk in 32s
                     // (... except chunks that are ONE segment: those are packed, a row each - make_units)
-                    const bool can_pack = kc->use3() && !op_mode;
+                    const bool can_pack = mfma() && !op_mode;
                     auto rows_used = [&](size_t sg) {
                         double r = 0.0, singles = 0.0;
                         for (size_t L : lens) {
                             if (!L) continue;
                             const double nseg = std::ceil((double)L / (double)sg);
                             if (nseg <= 1.0 && can_pack) singles += 1.0;
-                            else r += std::ceil(nseg / Z2SLOTS) * Z2SLOTS;
+                            else r += std::ceil(nseg / SL) * SL;
                         }
-                        return r + std::ceil(singles / Z2SLOTS) * Z2SLOTS;
+                        return r + std::ceil(singles / SL) * SL;
                     };
                     // Candidates: fill the machine's rows `rounds` times - or, when chunks x parameter sets alone need more
                     // rounds than that (every chunk takes at least one workgroup of 32 rows per parameter set: 100 chunks x 64
@@ -1164,7 +1198,7 @@ struct PlanBuilder {
                     for (size_t L : lens) lmax = std::max(lmax, L);
                     std::vector<size_t> cands;
                     for (int rounds = 1; rounds <= 16; ++rounds) {
-                        const double target = std::max((double)Z2SLOTS, std::floor(rows * rounds / B));
+                        const double target = std::max((double)SL, std::floor(rows * rounds / B));
                         // (the blocked kernels take segments of any multiple of 4 tokens - dword-aligned 16-byte
                         // loads - so the machine's rows can be filled to within a per cent, not to within 16 tokens)
                         size_t sg = std::max<size_t>(16, round_up((size_t)std::ceil((double)total / target), Z2GRAN));
@@ -1174,7 +1208,7 @@ struct PlanBuilder {
                         cands.push_back(sg);
                     }
                     for (size_t u = 1; u <= 8; ++u)
-                        cands.push_back(std::max<size_t>(16, round_up((lmax + Z2SLOTS * u - 1) / (Z2SLOTS * u), Z2GRAN)));
+                        cands.push_back(std::max<size_t>(16, round_up((lmax + SL * u - 1) / (SL * u), Z2GRAN)));
                     // ... and, for mixes of one long chunk with many short ones, the same for the MEDIAN chunk plus a few fixed
                     // short lengths: both families above follow the longest chunk, and when the short chunks alone need more
                     // than 16 rounds (each takes a workgroup per parameter set whatever the segment length) every candidate
@@ -1185,7 +1219,7 @@ struct PlanBuilder {
                         std::sort(sorted.begin(), sorted.end());
                         const size_t med = sorted[sorted.size() / 2];
                         for (size_t u = 1; u <= 4; ++u)
-                            cands.push_back(std::max<size_t>(16, round_up((med + Z2SLOTS * u - 1) / (Z2SLOTS * u), Z2GRAN)));
+                            cands.push_back(std::max<size_t>(16, round_up((med + SL * u - 1) / (SL * u), Z2GRAN)));
                         for (size_t fixed_len : {16, 32, 48, 64, 96, 128, 192}) cands.push_back(fixed_len);
                         // whole chunks as single segments (packed 32 to a workgroup): the length of the median, the 90 % and the
                         // longest chunk
@@ -1197,15 +1231,15 @@ struct PlanBuilder {
                         // per round of workgroups: the main loop, plus the table rebuild and the 5-level in-kernel fold
                         // (table: the VALU form builds token by token; the MFMA form one dictionary depth per pass,
                         // ~10 depths; with the hybrid table a workgroup only copies its hot set from L2)
-                        const double table = !kc->use3() ? (double)(gr.A - S) * (400.0 + (double)kc->NP * kc->NP * kc->NP / 64.0)
+                        const double table = !mfma() ? (double)(gr.A - S) * (400.0 + (double)kc->NP * kc->NP * kc->NP / 64.0)
                                              : gr.zip4 ? 9000.0 : 2600.0 * std::min(12.0, (double)(gr.A - S));
-                        const double fixed = table + 5.0 * (Z2WAVES / 4.0) * step_cycles;
+                        const double fixed = table + 5.0 * (WV / 4.0) * step_cycles;
                         // A segment length that is not a multiple of 16 ends in a MASKED block (the pipeline is re-primed per
                         // run of it: ~3.5 us; measured at 10 states, 100 x 1e6 columns: 48-token segments 101.9 us, 44-token
                         // ones 109.6) - so the next multiple of 16 is priced beside the exact fit.
                         for (size_t cand : {sg, round_up(sg, 16)}) {
                             const double u = rows_used(cand);
-                            double c = std::ceil(u * B / rows) * ((double)cand * (Z2WAVES / 4.0) * step_cycles + fixed + (cand % 16 ? 7700.0 : 0.0));
+                            double c = std::ceil(u * B / rows) * ((double)cand * (WV / 4.0) * step_cycles + fixed + (cand % 16 ? 7700.0 : 0.0));
                             // (every chunk a single packed segment: measured 10 % behind the best split where the model has a tie)
                             if (can_pack && cand >= lmax) c *= 1.15;
                             if (c < cost_blk) { cost_blk = c; seg_blk = cand; slots = u; }
@@ -1217,6 +1251,7 @@ struct PlanBuilder {
                     const bool vec_fits = !gr.zip || kc->zip_lds(gr.A) <= LDS_BUDGET;   // the table may only fit the blocked kernel
                     if (g.kernel_pref == 2 || cost_blk < cost_vec || !vec_fits || gr.zip4) { gr.zip2 = true; gr.seglen = seg_blk; }
                 }
+                if (gr.zip && !gr.zip2) gr.model_us = gr.model_tab_us + cost_vec / 2200.0;   // (build_plan's comparison)
             }
             if (g.seg_override) gr.seglen = round_up(std::max<size_t>(g.seg_override, 16), 16);   // tests: force stitching
             if (gr.bigvec)
@@ -1294,7 +1329,7 @@ struct PlanBuilder {
         chunk_units.assign(n_chunks, {});   // per chunk: (seg0, nsegs)
         for (int f = 0; f < n_chunks; ++f) {
             const Group &gr = p->groups[chunk_group[f]];
-            const uint32_t step = gr.zip2 ? (uint32_t)Z2SLOTS : 1u;
+            const uint32_t step = gr.zip2 ? (uint32_t)kc->z4_slots() : 1u;
             for (uint32_t sid = chunk_seg[f]; sid < chunk_seg[f + 1]; sid += step)
                 chunk_units[f].push_back({sid, std::min(step, chunk_seg[f + 1] - sid)});
         }
@@ -1319,8 +1354,8 @@ struct PlanBuilder {
                         // A chunk that is ONE segment needs no fold: up to 32 consecutive such chunks share a workgroup, each
                         // in a slot of its own (Z2Block::first == 2).  One workgroup per chunk left 31 of 32 rows idle when
                         // the chunks are short (10000 chunks of 1e4 columns, 20 states: 39 rounds of workgroups, 1.97 ms).
-                        const bool whole = kc->use3() && fst && ns == 1 && chunk_units[f].size() == 1;
-                        if (whole && !gr.blocks.empty() && gr.blocks.back().first == 2 && gr.blocks.back().n < Z2SLOTS &&
+                        const bool whole = mfma() && fst && ns == 1 && chunk_units[f].size() == 1;
+                        if (whole && !gr.blocks.empty() && gr.blocks.back().first == 2 && gr.blocks.back().n < (uint32_t)kc->z4_slots() &&
                             gr.blocks.back().seg0 + gr.blocks.back().n == sid && gr.blocks.back().out_vec0 + gr.blocks.back().n == unit_vec0[uid])
                             ++gr.blocks.back().n;
                         else
@@ -1332,13 +1367,13 @@ struct PlanBuilder {
             }
             gr.n_vecs = (uint32_t)vecs.size() - gr.vec_begin;
         }
-        // fused tail: one blocked-MFMA group holds every chunk, no chunk is empty or longer than Z2SLOTS workgroups
-        if (p->groups.size() == 1 && p->groups[0].zip2 && kc->use3() && !op_mode && n_chunks > 0) {
+        // fused tail: one blocked-MFMA group holds every chunk, no chunk is empty or longer than a workgroup has slots
+        if (p->groups.size() == 1 && p->groups[0].zip2 && mfma() && !op_mode && n_chunks > 0) {
             Group &gr = p->groups[0];
             bool ok = true;
             size_t most = 0;
             for (int f = 0; f < n_chunks; ++f) {
-                ok = ok && !chunk_units[f].empty() && chunk_units[f].size() <= (size_t)Z2SLOTS;
+                ok = ok && !chunk_units[f].empty() && chunk_units[f].size() <= (size_t)kc->z4_slots();
                 most = std::max(most, chunk_units[f].size());
             }
             if (ok) {
@@ -1478,7 +1513,7 @@ struct PlanBuilder {
                 for (int z = 0; z < gr.A; ++z) ids[z] = (uint16_t)z;
                 std::stable_sort(ids.begin(), ids.end(), [&](uint16_t x, uint16_t y) { return cnt[x] > cnt[y]; });
                 const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
-                gr.stream_table = z4_streamed(tables, B);
+                gr.stream_table = wide || z4_streamed(tables, B);
                 gr.n_hot = gr.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
                 gr.hot.assign(ids.begin(), ids.begin() + gr.n_hot);
                 e = up((void **)&gr.d_hot, gr.hot.data(), gr.hot.size() * sizeof(uint16_t));
@@ -1638,7 +1673,7 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
     key.reserve(n_chunks + 5);
     for (int f = 0; f < n_chunks; ++f) key.push_back(chunks[f]->id);
     key.push_back((uint64_t)N); key.push_back((uint64_t)S); key.push_back((uint64_t)B);
-    key.push_back((uint64_t)g.seg_override); key.push_back((uint64_t)(g.compression * 4 + g.kernel_pref + (op_mode ? 64 : 0) + g.blocked_variant * 128 + (g.z4_stream + 1) * 1024));
+    key.push_back((uint64_t)g.seg_override); key.push_back((uint64_t)(g.compression * 4 + g.kernel_pref + (op_mode ? 64 : 0) + g.blocked_variant * 128 + (g.z4_stream + 1) * 1024 + (g.wide_blocked + 1) * 4096));
     { const char *fl = std::getenv("IMC_FORCE_LEVEL"); key.push_back(fl ? (uint64_t)(std::atoi(fl) + 1) : 0u); }   // (experiments / tests)
     for (auto it = g_plans.begin(); it != g_plans.end(); ++it) {
         if ((*it)->key == key) {
@@ -1684,13 +1719,46 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
         };
         if (g.rank1_handoff && !g.seg_override && !eligible(kc) && eligible(kc + 1)) kc = kc + 1;
     }
-    auto p = std::make_unique<Plan>();
-    p->key = key; p->kc = kc; p->N = N; p->S = S; p->B = B; p->n_chunks = n_chunks;
+    // The first two phases (groups, dictionary levels, segment lengths: host arithmetic only) for a kernel family.
+    auto start = [&](PlanBuilder &b, KernelChoice *k, bool wide) {
+        b.chunks = chunks; b.n_chunks = n_chunks; b.N = N; b.S = S; b.B = B; b.op_mode = op_mode; b.kc = k; b.wide = wide;
+        b.p = std::make_unique<Plan>();
+        b.p->key = key; b.p->kc = k; b.p->wide = wide; b.p->N = N; b.p->S = S; b.p->B = B; b.p->n_chunks = n_chunks;
+        b.assign_groups();
+        b.choose_segment_lengths();
+    };
     PlanBuilder pb;
-    pb.chunks = chunks; pb.n_chunks = n_chunks; pb.N = N; pb.S = S; pb.B = B; pb.op_mode = op_mode; pb.kc = kc;
-    pb.p = std::move(p);
-    pb.assign_groups();
-    pb.choose_segment_lengths();
+    start(pb, kc, false);
+    // 25-32 states, automatic mode: the blocked scan (k_zpropagate4<7 | 8>) is one more candidate for the chunks that have a
+    // dictionary - a second plan on the vector kernels' entry, whose dictionary groups take the scan.  It must take EVERY
+    // dictionary of the call, and, where today's plan is the GEMM chain's, every chunk that has columns: raw streams and
+    // uncompressed chunks stay on the kernels they have.  A plan that runs all of its dictionary groups on the mat-vec chain
+    // (many short chains) keeps that choice.  Otherwise the two plans' estimates for the dictionary groups decide - the
+    // scan's is the blocked kernels' own model (assign_groups), with four wavefronts and 16 segments per workgroup.
+    KernelChoice *kw = (N > 24 && N <= 32) ? choose_kernel(N, false) : nullptr;
+    if (kw && kw->wide_blocked && g.wide_blocked != 0 && g.compression == 1 && g.kernel_pref == 0 && n_chunks > 0) {
+        PlanBuilder wb;
+        start(wb, kw, true);
+        bool any = false, all = wb.wide_ok;
+        double us_wide = 0.0, us_base = 0.0;
+        for (const Group &gr : wb.p->groups) {
+            bool cols = false;
+            for (int f : gr.chunks) cols = cols || chunks[f]->L > 0;
+            if (gr.zip4) { any = true; us_wide += gr.model_us; }
+            else if (cols && kc->R == 0) all = false;
+        }
+        bool base_matvec = false, base_other = false;
+        for (const Group &gr : pb.p->groups)
+            if (gr.zip) { us_base += gr.model_us; (gr.bigvec ? base_matvec : base_other) = true; }
+        base_matvec = base_matvec && !base_other;
+        if (std::getenv("IMC_DEBUG"))
+            std::fprintf(stderr, "[imc] plan: blocked scan at %d states %s, model %.1f us; present kernels %.1f us%s\n", N,
+                         any && all ? "possible" : "not possible", us_wide, us_base, base_matvec ? " (mat-vec chain)" : "");
+        if (any && all && (g.wide_blocked == 1 || (!base_matvec && us_wide < us_base))) {
+            pb = std::move(wb);
+            kc = kw;
+        }
+    }
     pb.cut_segments();
     if (int rc = pb.make_units()) return rc;
     pb.make_hierarchy();
@@ -1900,7 +1968,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
             ba.P = p->levels[0].d_P; ba.EX = p->levels[0].d_EX;
             ba.tab_order = gr.d_tab_order; ba.tab_lvl = gr.d_tab_lvl; ba.tab_nlvl = gr.tab_nlvl;
             ba.hot = gr.d_hot; ba.n_hot = gr.n_hot; ba.tab_desc = gr.d_tab_desc;
-            if (gr.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.tail_stride <= 4)) && allow_tail && kc->use3()) {
+            if (gr.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.tail_stride <= 4)) && allow_tail && (kc->use3() || p->wide)) {
                 ba.tail = gr.d_tails; ba.tailX = gr.d_tailX; ba.tailE = gr.d_tailE; ba.tail_arrive = gr.d_tail_arrive;
                 ba.tail_out = out; ba.tail_stride = gr.tail_stride; ba.n_chunks = p->n_chunks;
                 tail_used = true;
@@ -1913,7 +1981,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
                     hipLaunchKernelGGL(kc->zip4_raw, dim3((unsigned)S + 1, (unsigned)B), dim3(256), 0, stream, ba);
                     HIP_TRY(hipGetLastError());
                 }
-                if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && NP <= 12)) && gr.d_tab_desc3) {
+                if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && NP <= 12)) && gr.d_tab_desc3 && kc->zip4_level3) {
                     bool head = fuse_head;
                     if (!kc->zip4_attr_l3) {
                         HIP_TRY(hipFuncSetAttribute((const void *)kc->zip4_level3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
@@ -1931,7 +1999,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
                         head = false;
                         HIP_TRY(hipGetLastError());
                     }
-                } else if (g.table_pairs && gr.d_tab_desc2) {
+                } else if (g.table_pairs && gr.d_tab_desc2 && kc->zip4_level2) {
                     bool head = fuse_head;
                     const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
                     for (const auto &lc : gr.tab2) {          // two dictionary depths per launch
@@ -1986,7 +2054,7 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
                         if ((B % 8) & sets) phase(sets, sets);
                     scan_grid = dim3((unsigned)wg);
                 }
-                hipLaunchKernelGGL(scan, scan_grid, dim3(Z2WAVES * 64), kc->zip4_lds(gr.A, gr.n_hot), stream, ba);
+                hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.n_hot), stream, ba);
                 note(std::string("k_zpropagate4<") + std::to_string(NP / 4) + (gr.wide_tokens ? ",16" : "") + (gr.stream_table ? ",streamed>" : ">") + strm);
                 lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A);
                 HIP_TRY(hipGetLastError());
@@ -2659,6 +2727,14 @@ int imc_set_table_streaming(int mode)
     std::lock_guard<std::mutex> lk(g_mu);
     if (mode < -1 || mode > 1) return fail(IMC_ERR_ARG, "table streaming mode must be -1 (automatic), 0 (hybrid LDS cache) or 1 (streamed)");
     g.z4_stream = mode;                     // (part of the plan key)
+    return IMC_OK;
+}
+
+int imc_set_wide_blocked(int mode)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (mode < -1 || mode > 1) return fail(IMC_ERR_ARG, "wide blocked mode must be -1 (automatic), 0 (never) or 1 (wherever possible)");
+    g.wide_blocked = mode;                  // (part of the plan key)
     return IMC_OK;
 }
 

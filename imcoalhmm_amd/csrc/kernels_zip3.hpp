@@ -127,7 +127,9 @@ __device__ __forceinline__ void zip3_rescale(double (&P)[NT][NT], int &ex)
 // holds and keeps its own P.  Round 2's fold was five workgroup-wide levels (two barriers and a step by all eight
 // wavefronts each): 16 us at N = 20 (in-kernel timestamps, profiles/r02_z4_phase_times.txt).
 // TABLE_LIVE: X overlays an LDS table that other wavefronts may still be reading -> one more barrier in front.
-template <int NT, bool TABLE_LIVE, bool RESCALE = true>
+// SLOTS: segments per workgroup of the calling kernel (Z2SLOTS; 16 for the four-wavefront workgroups of 25-32 states,
+// whose stage B then ends at level 4).
+template <int NT, bool TABLE_LIVE, bool RESCALE = true, int SLOTS = Z2SLOTS>
 __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *X, int *xe, int n, int slot, int wv, int lo, int lx)
 {
     using Geo = Zip3Geom<NT>;
@@ -161,12 +163,12 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
     if (wv * 4 + 1 < n) {                                   // (wavefront-uniform: this wavefront holds at least two segments)
         if ((bq & 1) && slot < n) put(slot);
         wave_fence();
-        take(slot + 1 < Z2SLOTS ? slot + 1 : slot, !(bq & 1) && slot + 1 < n);
+        take(slot + 1 < SLOTS ? slot + 1 : slot, !(bq & 1) && slot + 1 < n);
         if (wv * 4 + 2 < n) {
             wave_fence();                                   // (the reads of level 1 are done before area slot 2 is rewritten)
             if (bq == 2 && slot < n) put(slot);
             wave_fence();
-            take(slot + 2 < Z2SLOTS ? slot + 2 : slot, bq == 0 && slot + 2 < n);
+            take(slot + 2 < SLOTS ? slot + 2 : slot, bq == 0 && slot + 2 < n);
         }
     }
     if (n <= 4) return;
@@ -192,7 +194,7 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
         wave_fence();
         take(bq + 1 < 4 ? bq + 1 : bq, !(bq & 1) && 2 * (bq + 1) < nw);
     }
-    if (nw > 4) {                                           // level 5: 2 -> 0
+    if (SLOTS > 16 && nw > 4) {                             // level 5: 2 -> 0
         wave_fence();
         if (bq == 2) put(2);
         wave_fence();
@@ -205,7 +207,7 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
 // vector in column 0).  With at most Z2SLOTS workgroups per chunk the stitch is one more zip3_fold: every workgroup
 // publishes its operator in an LDS table entry's layout (sc1 stores: written through, the publishing wavefront drains
 // them with s_waitcnt vmcnt(0) before it signals), then adds one to the chunk's arrival counter (an agent-scope atomic);
-// the workgroup whose add returns n_units - 1 is the last: its 32 slots reload the chunk's operators (sc1 loads: past
+// the workgroup whose add returns n_units - 1 is the last: its slots reload the chunk's operators (sc1 loads: past
 // this CU's L1; nobody on this XCD has read those lines before), fold them as the scan's own fold does, and slot 0
 // turns column 0 of the product into the chunk's log-likelihood, ln2 * exponent + log(sum), written straight to the
 // result slot.  (MI355X_MICROARCH.md, "Valid forms": one lane signals for all of its workgroup's stores, the consumer is
@@ -214,7 +216,7 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
 // Every published operator and every exponent sits on cache lines of its own (TOK * 8 is a multiple of 128 bytes, an
 // exponent has a 128-byte slot): a last arriver that shares an XCD with an earlier one must not find a line in that
 // L2 that was fetched before all of its words were written.
-template <int NT>
+template <int NT, int SLOTS = Z2SLOTS>
 __device__ __forceinline__ void zip3_tail(const BigArgs &a, double (&P)[NT][NT], int &ex, double *X, int *xe, int b, int bx, int slot, int lo, int lx)
 {
     using Geo = Zip3Geom<NT>;
@@ -251,7 +253,7 @@ __device__ __forceinline__ void zip3_tail(const BigArgs &a, double (&P)[NT][NT],
                 P[K][J] = valid ? v : 0.0;
             }
         ex = __hip_atomic_load(&a.tailE[(cb * a.tail_stride + (valid ? slot : 0)) * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        zip3_fold<NT, true>(P, ex, X, xe, (int)td.n_units, slot, tid >> 6, lo, lx);
+        zip3_fold<NT, true, true, SLOTS>(P, ex, X, xe, (int)td.n_units, slot, tid >> 6, lo, lx);
         if (tid == 0) __hip_atomic_store(&a.tail_arrive[cb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (slot == 0) {

@@ -16,18 +16,32 @@
 #pragma once
 #include "kernels_zip3.hpp"
 
+// Workgroup shape of the scan.  Up to 24 states (NT <= 6) eight wavefronts, two per SIMD, share the 512 registers of a
+// lane; P, Q and one operand set are 3 NT^2 doubles - 294 registers at NT = 7, 384 at NT = 8 - so from 25 states on a
+// workgroup is FOUR wavefronts, one per SIMD with the whole unified register file (VGPRs + AGPRs) to itself, and 16
+// segments.  The fold's exchange area then holds 17 entries (104 / 136 KB) where 33 would not fit LDS.
+template <int NT>
+struct Zip4Shape {
+    static constexpr int WAVES = NT <= 6 ? Z2WAVES : 4;
+    static constexpr int SLOTS = WAVES * 4;
+    // the hybrid form's slot map: the streamed form never reads it, and from NT = 7 on (streamed only) LDS has no room for it
+    static constexpr bool SLOT_MAP = NT <= 6;
+};
+
 template <int NT>
 struct Zip4Geom {
     using G3 = Zip3Geom<NT>;
     static constexpr int TOK = G3::TOK;
+    static constexpr int SLOTS = Zip4Shape<NT>::SLOTS;
+    static constexpr int MAPS = Zip4Shape<NT>::SLOT_MAP ? 2 : 1;
     // LDS: `slots` operator entries (hot operators + identity; later the fold's exchange area), the slot map and the
     // exponents of all A + 1 table entries
-    static constexpr int slots(int H) { return (H + 1 > Z2SLOTS + 1 ? H + 1 : Z2SLOTS + 1); }
-    static constexpr size_t lds_bytes(int A, int H) { return (size_t)slots(H) * TOK * 8 + (size_t)(2 * (A + 2) + 64) * 4 + 16; }
+    static constexpr int slots(int H) { return (H + 1 > SLOTS + 1 ? H + 1 : SLOTS + 1); }
+    static constexpr size_t lds_bytes(int A, int H) { return (size_t)slots(H) * TOK * 8 + (size_t)(MAPS * (A + 2) + 64) * 4 + 16; }
     // how many hot operators fit beside the identity
     static constexpr int max_hot(int A, size_t budget)
     {
-        const size_t fixed = (size_t)(2 * (A + 2) + 64) * 4 + 16;
+        const size_t fixed = (size_t)(MAPS * (A + 2) + 64) * 4 + 16;
         const size_t n = budget > fixed ? (budget - fixed) / ((size_t)TOK * 8) : 0;
         return n > 1 ? (int)n - 1 : 0;
     }
@@ -588,11 +602,17 @@ struct Z4Tok {              // one step's operator for this lane's segment (kept
 // entry (if that is cold) as soon as each row has been consumed.
 // `refill`: the token whose global entry goes into `pre` behind the rows just consumed - the next step's (one register
 // set) or the one after (two sets: see Zip4Ring).
-template <int NT, bool HYB>
+// ROWS < NT (32 states: NT = 8, ROWS = 4): `pre` is a ring of ROWS tile-rows instead of a whole operator - P, Q and a
+// whole operand set are 384 registers there, and the rest of the kernel does not fit beside them.  Slot I % ROWS holds
+// tile-row I; behind tile-row I it is refilled with row I + ROWS of cur, or, past cur's last row, with row I + ROWS - NT
+// of `refill`: a load is then ROWS tile-rows (ROWS * NT^2 matrix instructions, 256 of them ~1.7 us) ahead of its use
+// instead of a whole step.  ROWS divides NT, so the next step finds its rows 0 .. ROWS - 1 in slots 0 .. ROWS - 1.
+template <int NT, bool HYB, int ROWS = NT>
 __device__ __forceinline__ void zip4_step(const double (&Pin)[NT][NT], double (&Pout)[NT][NT], const double *C, const double *Gt, const double *Gi,
-                                          const Z4Tok &cur, const Z4Tok &nxt, const Z4Tok &refill, double (&al)[NT], double (&pre)[NT][NT], int lo, int lx)
+                                          const Z4Tok &cur, const Z4Tok &nxt, const Z4Tok &refill, double (&al)[NT], double (&pre)[ROWS][NT], int lo, int lx)
 {
     constexpr int TOK = Zip3Geom<NT>::TOK;
+    static_assert(NT % ROWS == 0 && (ROWS == NT || !HYB), "a ring of tile-rows: streamed form only, ROWS divides NT");
     // The refill is issued for EVERY step - a hot next token fetches the identity entry `Gi` instead (the same few
     // cache lines for every such lane: L1 hits) - so that the number of loads in flight is the same on every path and
     // the compiler can wait for exactly the tile-row it needs (with the loads under a branch it waited for all of
@@ -611,7 +631,7 @@ __device__ __forceinline__ void zip4_step(const double (&Pin)[NT][NT], double (&
             else zip3_load_row<NT>(an, Cn, 0, lo, lx);
         }
 #pragma unroll
-        for (int K = 0; K < NT; ++K) av[K] = cur_cold ? pre[I][K] : al[K];
+        for (int K = 0; K < NT; ++K) av[K] = cur_cold ? pre[I % ROWS][K] : al[K];
         __builtin_amdgcn_sched_barrier(0);         // keep the LDS prefetch ahead of this tile-row's MFMAs
 #pragma unroll
         for (int K = 0; K < NT; ++K)
@@ -619,7 +639,8 @@ __device__ __forceinline__ void zip4_step(const double (&Pin)[NT][NT], double (&
             for (int J = 0; J < NT; ++J)
                 Pout[I][J] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[K], Pin[K][J], K == 0 ? 0.0 : Pout[I][J], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        zip4_load_row_global<NT>(pre[I], Gn, I, lo, lx);                 // (per lane; a full step ahead of its use)
+        if (I + ROWS < NT) zip4_load_row_global<NT>(pre[I % ROWS], Gt + (size_t)cur.tok * TOK, I + ROWS, lo, lx);
+        else zip4_load_row_global<NT>(pre[I % ROWS], Gn, I + ROWS - NT, lo, lx);   // (per lane; a full step ahead of its use when ROWS = NT)
         if constexpr (HYB) {
 #pragma unroll
             for (int K = 0; K < NT; ++K) al[K] = an[K];
@@ -639,18 +660,21 @@ __device__ long long g_z4_dbg[1024 * 8 * 3];        // [0]: phases of wavefront 
 // (L1 / L2 / Infinity Cache) a step ahead.  Without the per-row LDS reads and the LDS-or-register selects a step is
 // ~10 % faster as long as the tables of a launch stay cache resident (the host decides: Z4_STREAM_MAX_BYTES).
 template <int NT, bool WIDE, bool HYB>
-__global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigArgs a)
+__global__ __launch_bounds__(Zip4Shape<NT>::WAVES * 64, Zip4Shape<NT>::WAVES / 4) void k_zpropagate4(BigArgs a)
 {
     constexpr int TB = WIDE ? 2 : 1;                                   // bytes per token
     using Geo = Zip3Geom<NT>;
     using G4 = Zip4Geom<NT>;
-    constexpr int NP = Geo::NP, TOK = Geo::TOK, THREADS = Z2WAVES * 64;
+    constexpr int SLOTS = Zip4Shape<NT>::SLOTS;                        // segments per workgroup
+    constexpr bool SLOT_MAP = Zip4Shape<NT>::SLOT_MAP;
+    static_assert(SLOT_MAP || !HYB, "the hybrid form needs the slot map");
+    constexpr int NP = Geo::NP, TOK = Geo::TOK, THREADS = Zip4Shape<NT>::WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int H = HYB ? a.n_hot : 0;                                   // hot operators; LDS slot H = the identity
     double *C = lds;                                                   // [slots(H)][TOK]
     int *cex = reinterpret_cast<int *>(C + (size_t)G4::slots(H) * TOK);   // [A + 1] exponents of the table entries
-    int *slot_of = cex + a.A + 2;                                      // [A + 1] LDS slot of a token, -1 = cold
-    int *xex = slot_of + a.A + 2;                                      // [Z2SLOTS + 1] the fold's exchange exponents
+    int *slot_of = cex + a.A + 2;                                      // [A + 1] LDS slot of a token, -1 = cold (SLOT_MAP)
+    int *xex = SLOT_MAP ? slot_of + a.A + 2 : slot_of;                 // [SLOTS + 1] the fold's exchange exponents
 
     const int tid = threadIdx.x;
     int b = (int)blockIdx.y, bx = (int)blockIdx.x;                     // parameter set, block (BigArgs::n_phases)
@@ -678,7 +702,7 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
 
     // ---- LDS: exponents, slot map, the hot operators and the identity ----
     Z4_STAMP(0);
-    for (int z = tid; z <= a.A; z += THREADS) { cex[z] = Gc[z]; slot_of[z] = -1; }
+    for (int z = tid; z <= a.A; z += THREADS) { cex[z] = Gc[z]; if constexpr (SLOT_MAP) slot_of[z] = -1; }
     if constexpr (HYB) {
         __syncthreads();
         for (int k = tid; k <= H; k += THREADS) slot_of[k < H ? (int)a.hot[k] : IDENT] = k;
@@ -696,7 +720,7 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
     const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
     const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
     const Z2Block blk = a.blocks[bx];
-    const int slot = (tid >> 6) * 4 + bq;                   // 0..Z2SLOTS-1 within the workgroup
+    const int slot = (tid >> 6) * 4 + bq;                   // 0..SLOTS-1 within the workgroup
     const bool valid = slot < (int)blk.n;
     // A lane without a segment runs the wavefront's unconditional token loads on another segment's stream: the FIRST
     // slot of its own wavefront (whose length bounds the wavefront's full blocks: nfull is a minimum over the valid
@@ -739,12 +763,14 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
     // round trip and the streamed form keeps TWO sets, each refilled with the operator two steps ahead (microbenchmark
     // profiles/tools/micro/mb_scan_ring3.hip, 10 states: 60.0 -> 35.4 us for the planner's 100 x 1e6-column shape, the
     // MFMA instruction's own rate; at 20 states the same change is slower: mb_scan_ring2.hip).
+    // (32 states: a ring of four tile-rows instead of the whole operand set - see zip4_step)
     constexpr int RING = (!HYB && NT <= 4) ? 2 : 1;
-    double al[NT] = {}, pre[RING][NT][NT];
+    constexpr int ROWS = NT == 8 ? 4 : NT;
+    double al[NT] = {}, pre[RING][ROWS][NT];
 #pragma unroll
     for (int d = 0; d < RING; ++d)
 #pragma unroll
-        for (int I = 0; I < NT; ++I)
+        for (int I = 0; I < ROWS; ++I)
 #pragma unroll
             for (int K = 0; K < NT; ++K) pre[d][I][K] = 0.0;
     auto mk = [&](int tok) __attribute__((always_inline)) {
@@ -761,21 +787,21 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
         if constexpr (HYB) zip3_load_row<NT>(al, C + (size_t)max(c.s, 0) * TOK, 0, lo, lx);
         const double *Gc0 = c.s < 0 ? Gt + (size_t)c.tok * TOK : Gi;        // (unconditional, as zip4_step's refill)
 #pragma unroll
-        for (int I = 0; I < NT; ++I) zip4_load_row_global<NT>(pre[0][I], Gc0, I, lo, lx);
+        for (int I = 0; I < ROWS; ++I) zip4_load_row_global<NT>(pre[0][I], Gc0, I, lo, lx);
         if constexpr (RING == 2) {
             const double *Gc1 = Gt + (size_t)c1.tok * TOK;
 #pragma unroll
-            for (int I = 0; I < NT; ++I) zip4_load_row_global<NT>(pre[1][I], Gc1, I, lo, lx);
+            for (int I = 0; I < ROWS; ++I) zip4_load_row_global<NT>(pre[1][I], Gc1, I, lo, lx);
         }
     };
     // two steps on t0, t1; tn, tn1: the tokens of the two positions behind them (tn1 only matters to the two-set form)
     auto two_steps = [&](const Z4Tok &t0, const Z4Tok &t1, const Z4Tok &tn, const Z4Tok &tn1) __attribute__((always_inline)) {
         if constexpr (RING == 2) {
-            zip4_step<NT, HYB>(P, Q, C, Gt, Gi, t0, t1, tn, al, pre[0], lo, lx);
-            zip4_step<NT, HYB>(Q, P, C, Gt, Gi, t1, tn, tn1, al, pre[1], lo, lx);
+            zip4_step<NT, HYB, ROWS>(P, Q, C, Gt, Gi, t0, t1, tn, al, pre[0], lo, lx);
+            zip4_step<NT, HYB, ROWS>(Q, P, C, Gt, Gi, t1, tn, tn1, al, pre[1], lo, lx);
         } else {
-            zip4_step<NT, HYB>(P, Q, C, Gt, Gi, t0, t1, t1, al, pre[0], lo, lx);
-            zip4_step<NT, HYB>(Q, P, C, Gt, Gi, t1, tn, tn, al, pre[0], lo, lx);
+            zip4_step<NT, HYB, ROWS>(P, Q, C, Gt, Gi, t0, t1, t1, al, pre[0], lo, lx);
+            zip4_step<NT, HYB, ROWS>(Q, P, C, Gt, Gi, t1, tn, tn, al, pre[0], lo, lx);
         }
         ex += t0.ce + t1.ce;
     };
@@ -894,7 +920,7 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
 
     // ---- fold the workgroup's segments into one (zip3_fold; the LDS entries become the exchange area; the streamed
     // form keeps nothing in LDS during the scan, so its wavefronts start folding as they finish) ----
-    zip3_fold<NT, HYB>(P, ex, C, xex, (int)blk.n, slot, tid >> 6, lo, lx);
+    zip3_fold<NT, HYB, true, SLOTS>(P, ex, C, xex, (int)blk.n, slot, tid >> 6, lo, lx);
 
     Z4_STAMP(5);
 #ifdef IMC_Z4_TIMING
@@ -925,5 +951,5 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate4(BigAr
             }
         }
     }
-    if (a.tail) zip3_tail<NT>(a, P, ex, C, xex, b, bx, slot, lo, lx);
+    if (a.tail) zip3_tail<NT, SLOTS>(a, P, ex, C, xex, b, bx, slot, lo, lx);
 }

@@ -210,7 +210,8 @@ int imc_profile_read(double *ms_propagate, double *ms_stitch, uint64_t *n_propag
 int imc_last_rank1(uint64_t *checked, uint64_t *collapsed);
 /* Switch the hand-off on (default) or off for plans built from now on (A/B comparisons, tests). */
 int imc_set_rank1_handoff(int on);
-/* Register-blocked kernel for N <= 24: 4 (default) = the fp64-MFMA scan (v_mfma_f64_4x4x4: the DP units are the same,
+/* Register-blocked kernel for N <= 24 (its variants do not apply to 25-32 states: see imc_set_wide_blocked): 4 (default)
+ * = the fp64-MFMA scan (v_mfma_f64_4x4x4: the DP units are the same,
  * the matrix form needs a quarter of the issue slots and no cross-lane moves) with its operator table in LDS
  * (k_zpropagate3) or, where the planner's estimate says it pays, with a hybrid table - a dictionary level of up to
  * 4096 tokens in global memory / L2, the hottest operators cached in LDS (k_zpropagate4); 3 = LDS table only;
@@ -224,6 +225,17 @@ int imc_set_blocked_kernel(int variant);
  * 0 = always hybrid; 1 = always streamed (A/B measurements, tests).
  * IMC_Z4_STREAM=-1|0|1 in the environment sets the mode at start-up. */
 int imc_set_table_streaming(int mode);
+/* 25 to 32 states on the register-blocked fp64-MFMA scan (k_zpropagate4<7>: 25-28 states, <8>: 29-32): workgroups of
+ * four wavefronts - one per SIMD, each with the lane's whole 512-register file - and 16 segments, the operator table
+ * always streamed, built one dictionary depth per launch.  -1 (default) = automatic: in automatic mode
+ * (imc_set_compression(1)) the scan is one more candidate for the token streams of a call, priced by the blocked
+ * kernels' own cost model against the GEMM chain / the LDS-table vector kernels; a call that runs on the mat-vec chain
+ * (many short chains) stays there.  0 = never (the kernels of the releases before this switch).  1 = wherever every
+ * dictionary of the call has a token level the scan can run (a table the streamed form accepts, see
+ * imc_set_table_streaming).  Raw streams, chunks too short to be compressed and the pinned modes 2-5 of
+ * imc_set_compression keep their kernels whatever the mode.
+ * IMC_WIDE_BLOCKED=-1|0|1 in the environment sets the mode at start-up. */
+int imc_set_wide_blocked(int mode);
 /* Description of the last launch plan, out8[0..7] = segments, vectors, per-column segment length,
  * executed vector-columns (per-column kernel), token segment length, executed vector-tokens (token
  * kernel), tokens in the compressed streams, token alphabet. */
