@@ -80,6 +80,11 @@ SIGNATURES = [
      [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _dp, _dp, _dp, _dp,
       _dp, _dp, ctypes.c_int]),
     ("imc_model_expm", ctypes.c_int, [ctypes.c_int, _dp, _dp]),
+    # ... and the same two on the device (csrc/kernels_model.hpp)
+    ("imc_model_transitions_device", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _dp, _dp, _dp, _dp,
+      _dp, _dp]),
+    ("imc_model_expm_batch_device", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp]),
 ]
 
 _lib = None

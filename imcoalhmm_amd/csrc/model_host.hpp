@@ -76,6 +76,20 @@ static inline bool solve(double *M, double *R, int n)
     return true;
 }
 
+// Pade degree m (3, 5, 7, 9 or 13) and number of squarings s for a matrix of 1-norm nrm: Higham's thresholds theta_m
+// (see expm below).  The ONE place where the choice is made: expm calls it, and so does the device path
+// (imc_model_transitions_device / imc_model_expm_batch_device pass m and s to k_model_expm), so both take the same branch.
+static inline void expm_plan(double nrm, int &m, int &s)
+{
+    s = 0;
+    if (nrm <= 2.097847961257068) {             // low degrees, no scaling
+        m = nrm <= 1.495585217958292e-2 ? 3 : nrm <= 2.539398330063230e-1 ? 5 : nrm <= 9.504178996162932e-1 ? 7 : 9;
+        return;
+    }
+    m = 13;
+    if (nrm > 5.371920351148152) s = std::max(0, (int)std::ceil(std::log2(nrm / 5.371920351148152)));
+}
+
 // exp(A) by scaling and squaring with Pade approximants (Higham, SIAM J. Matrix Anal. Appl. 26(4), 2005, Algorithm 2.3:
 // degree 3, 5, 7 or 9 while the 1-norm is below theta_m, else [13/13] after scaling below theta_13 = 5.37;
 // scipy.linalg.expm - what CTMC.py:39-51 and models.py call - chooses among the same approximants, so the two agree
@@ -97,8 +111,9 @@ static inline bool expm(const double *A, double *out, int n, std::vector<double>
         for (size_t k = 0; k < nn; ++k) { Tm[k] = V[k] - U[k]; out[k] = V[k] + U[k]; }
         return solve(Tm, out, n);
     };
-    if (nrm <= 2.097847961257068) {             // low degrees, no scaling
-        const int m = nrm <= 1.495585217958292e-2 ? 3 : nrm <= 2.539398330063230e-1 ? 5 : nrm <= 9.504178996162932e-1 ? 7 : 9;
+    int m = 13, s = 0;
+    expm_plan(nrm, m, s);
+    if (m < 13) {                               // low degrees, no scaling
         const double *c = m == 3 ? b3 : m == 5 ? b5 : m == 7 ? b7 : b9;
         matmul(A, A, A2, n);
         if (m >= 5) matmul(A2, A2, A4, n);
@@ -117,8 +132,6 @@ static inline bool expm(const double *A, double *out, int n, std::vector<double>
         matmul(A, Tm, U, n);
         return finish();
     }
-    int s = 0;
-    if (nrm > 5.371920351148152) s = std::max(0, (int)std::ceil(std::log2(nrm / 5.371920351148152)));
     const double scale = std::ldexp(1.0, -s);
     for (size_t k = 0; k < nn; ++k) As[k] = A[k] * scale;
     matmul(As, As, A2, n);

@@ -37,7 +37,7 @@ __all__ = [
     "coalescence_points", "emission_matrix", "StateSpace", "isolation_space", "single_space",
     "migration_space", "IsolationModel", "IsolationMigrationModel",
     "VariableCoalescenceRateIsolationModel", "VariableCoalAndMigrationRateModel",
-    "IsolationMigrationEpochsModel",
+    "IsolationMigrationEpochsModel", "set_device_transitions",
 ]
 
 
@@ -321,8 +321,22 @@ class _Through(object):
 # native path (csrc/model_host.hpp behind include/imcoal_model.h): the same recursion in C++ for
 # small state spaces, where the ~40 numpy calls per interval - not the arithmetic - are the cost
 # ---------------------------------------------------------------------------------------------
-NATIVE_MAX_SPACE = 32           # larger spaces (the 94-state migration space) stay on numpy / BLAS
-_native = {"lib": None, "tried": False, "structures": {}}
+NATIVE_MAX_SPACE = 32           # larger spaces (the 94-state migration space) stay on numpy / BLAS ...
+DEVICE_MAX_SPACE = 128          # ... or, with set_device_transitions(True), go to the GPU (csrc/kernels_model.hpp) up to this order
+_native = {"lib": None, "tried": False, "structures": {}, "device": os.environ.get("IMC_MODEL_DEVICE", "0") == "1",
+           "device_calls": 0, "device_count": None}
+
+
+def set_device_transitions(on):
+    """Build (pi, T) of populations whose state spaces exceed NATIVE_MAX_SPACE (every model with a migration epoch) on the
+    GPU (imc_model_transitions_device) instead of numpy.  Off by default; IMC_MODEL_DEVICE=1 at import switches it on.
+    Without the library or a device the numpy path runs as before.  With the switch on the first ``build_batch``
+    initialises HIP in this process: it counts as a first ``imc_*`` call for fork() (fork the workers before it).
+    ``_native["device_calls"]`` counts the populations handed to the device entry point, whether the call then succeeds
+    or raises (a call answered with "no device" falls back to numpy and is not counted).  Returns the previous setting."""
+    was = _native["device"]
+    _native["device"] = bool(on)
+    return was
 
 
 def _native_lib():
@@ -356,9 +370,10 @@ def expm(A):
     return out
 
 
-def _native_structure(system):
+def _native_structure(system, max_space=NATIVE_MAX_SPACE):
     """The parameter-independent part of a PiecewiseCTMC as the int32 arrays of imc_model_transitions,
-    cached per (state spaces, piece pattern, projections)."""
+    cached per (state spaces, piece pattern, projections, largest space the caller's route takes): False when a
+    space is larger than ``max_space``."""
     q_index, piece_q, projs, piece_proj = {}, [], [], []
     for Q, _, proj in system.pieces:
         piece_q.append(q_index.setdefault(id(Q), len(q_index)))
@@ -372,11 +387,11 @@ def _native_structure(system):
             else:
                 projs.append(proj)
                 piece_proj.append(len(projs) - 1)
-    key = (tuple(id(sp) for sp in system.spaces), tuple(piece_q), tuple(piece_proj), tuple(id(p) for p in projs))
+    key = (tuple(id(sp) for sp in system.spaces), tuple(piece_q), tuple(piece_proj), tuple(id(p) for p in projs), max_space)
     st = _native["structures"].get(key)
     if st is None:
         spaces = system.spaces
-        if max(sp.size for sp in spaces) > NATIVE_MAX_SPACE:
+        if max(sp.size for sp in spaces) > max_space:
             st = False
         else:
             lists = [np.asarray(c, dtype=np.int32) for sp in spaces for c in (sp.begin_states, sp.left_states, sp.end_states)]
@@ -396,15 +411,63 @@ def _native_structure(system):
     return st, q_index
 
 
-def _native_transitions(systems):
+def _native_transitions(systems, device=False):
+    """(pi, T) by the library - the host C++ path, or with ``device`` the GPU path for the spaces above
+    NATIVE_MAX_SPACE - or None: the caller goes on to the next path."""
     lib = _native_lib()
     if lib is None:
         return None
     if len(systems[0].spaces) < 2:          # a single interval: nothing to exponentiate, numpy does it
         return None
-    st, q_index = _native_structure(systems[0])
+    if device:
+        largest = max(sp.size for sp in systems[0].spaces)
+        if not _native["device"] or largest <= NATIVE_MAX_SPACE or largest > DEVICE_MAX_SPACE:
+            return None
+        if _native["device_count"] is None:
+            _native["device_count"] = int(lib.imc_device_count())
+        if _native["device_count"] <= 0:
+            return None
+    st, q_index = _native_structure(systems[0], DEVICE_MAX_SPACE if device else NATIVE_MAX_SPACE)
     if not st:
         return None
+    packed = _native_pack(systems, st, q_index)
+    if packed is None:
+        return None
+    q_size, Qs, dts, starts = packed
+    n, nb = st["n"], len(systems)
+    pi = np.empty((nb, n))
+    T = np.empty((nb, n, n))
+    call = _native.get("device_call" if device else "call")
+    if call is None:            # raw addresses instead of typed pointer objects: 15 data_as() calls cost more than the recursion
+        vp = ctypes.c_void_p
+        args = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
+        if device:
+            call = _native["device_call"] = ctypes.CFUNCTYPE(*args)(("imc_model_transitions_device", lib))
+        else:
+            call = _native["call"] = ctypes.CFUNCTYPE(*(args + [ctypes.c_int]))(("imc_model_transitions", lib))
+    addr = st.get("addr")
+    if addr is None:
+        addr = st["addr"] = tuple(st[k].ctypes.data for k in ("space_size", "cls_off", "cls_idx", "piece_q", "piece_proj", "proj_off", "proj"))
+    tail = () if device else (min(16, os.cpu_count() or 1) if nb >= 8 else 1,)      # n_threads: the host form only
+    rc = call(nb, n, addr[0], addr[1], addr[2], addr[3], addr[4], st["n_q"], q_size.ctypes.data, len(st["proj_off"]), addr[5], addr[6],
+              Qs.ctypes.data, dts.ctypes.data, starts.ctypes.data, pi.ctypes.data, T.ctypes.data, *tail)
+    if device:
+        if rc == -6:            # IMC_ERR_NODEVICE: no usable device after all - the numpy path
+            _native["device_count"] = 0
+            return None
+        _native["device_calls"] += 1
+    if rc != 0:
+        msg = lib.imc_last_error().decode("utf-8", "replace")
+        if "must be supported on the B class" in msg:
+            raise ValueError(msg)
+        raise AssertionError(msg)
+    return pi, T
+
+
+def _native_pack(systems, st, q_index):
+    """The parameter-dependent arrays of imc_model_transitions for systems of structure ``st``:
+    ``(q_size, Q [B][sum of squares], dt [B][n - 1], start [B][|S_0|])``, or None when a system
+    has another piece pattern than the first."""
     n, nb = st["n"], len(systems)
     order = sorted(q_index, key=q_index.get)
     first = {id(Q): Q for Q, _, _ in systems[0].pieces}
@@ -430,26 +493,7 @@ def _native_transitions(systems):
                 return None
             dts[b, i] = dt
         starts[b] = sy.start
-    pi = np.empty((nb, n))
-    T = np.empty((nb, n, n))
-    threads = min(16, os.cpu_count() or 1) if nb >= 8 else 1
-    call = _native.get("call")
-    if call is None:            # raw addresses instead of typed pointer objects: 15 data_as() calls cost more than the recursion
-        vp = ctypes.c_void_p
-        proto = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp,
-                                 vp, vp, vp, vp, vp, ctypes.c_int)
-        call = _native["call"] = proto(("imc_model_transitions", lib))
-    addr = st.get("addr")
-    if addr is None:
-        addr = st["addr"] = tuple(st[k].ctypes.data for k in ("space_size", "cls_off", "cls_idx", "piece_q", "piece_proj", "proj_off", "proj"))
-    rc = call(nb, n, addr[0], addr[1], addr[2], addr[3], addr[4], st["n_q"], q_size.ctypes.data, len(st["proj_off"]), addr[5], addr[6],
-              Qs.ctypes.data, dts.ctypes.data, starts.ctypes.data, pi.ctypes.data, T.ctypes.data, threads)
-    if rc != 0:
-        msg = lib.imc_last_error().decode("utf-8", "replace")
-        if "must be supported on the B class" in msg:
-            raise ValueError(msg)
-        raise AssertionError(msg)
-    return pi, T
+    return q_size, Qs, dts, starts
 
 
 def hmm_transitions_batch(systems):
@@ -466,6 +510,8 @@ def hmm_transitions_batch(systems):
     as stacked matrix products.
     """
     done = _native_transitions(systems)
+    if done is None and _native["device"]:
+        done = _native_transitions(systems, device=True)
     if done is not None:
         return done
     spaces = systems[0].spaces

@@ -1,0 +1,138 @@
+"""The device route of the model layer (imc_model_transitions_device / imc_model_expm_batch_device, csrc/kernels_model.hpp)
+as far as a machine without a GPU can see it: the symbols, the argument checks (they run before any HIP call), the
+silent numpy fallback of models.py, the host path's bits after its degree choice moved into imc_model::expm_plan, and
+the kernels' register budget.  The arithmetic is checked on the device in tests/test_gpu_model_device.py."""
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from imcoalhmm_amd import _capi, build
+from imcoalhmm_amd import models as M
+from model_device_cases import _dp, call_transitions, one_space_case
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+NEW = ("imc_model_transitions_device", "imc_model_expm_batch_device")
+
+
+def _lib():
+    if M._native_lib() is None:
+        pytest.skip("libimcoal_fwd.so is not built")
+    return _capi.lib()
+
+
+def test_new_symbols_are_exported_declared_and_bound():
+    lib = _lib()
+    header = open(os.path.join(REPO, "include", "imcoal_model.h")).read()
+    names = [sig[0] for sig in _capi.SIGNATURES]
+    for name in NEW:
+        assert hasattr(lib, name)
+        assert re.search(r"\bint %s\(" % name, header), name
+        assert names.count(name) == 1
+    # the device form takes the host form's arguments without n_threads
+    by_name = {sig[0]: sig for sig in _capi.SIGNATURES}
+    assert by_name["imc_model_transitions_device"][2] == by_name["imc_model_transitions"][2][:-1]
+
+
+@pytest.mark.parametrize("what", ["null Q", "null pi", "order 129", "257 intervals", "class index out of range", "negative count"])
+def test_bad_arguments_are_refused_before_any_device_call(what):
+    lib = _lib()
+    null = None
+    if what == "order 129":
+        case = one_space_case(129, 3)
+    elif what == "257 intervals":
+        case = one_space_case(6, 257)
+    else:
+        case = one_space_case(6, 3)
+    if what == "class index out of range":
+        case["cls_idx"][4] = 6
+    if what.startswith("null"):
+        null = what.split()[1]
+    if what == "negative count":
+        A = np.zeros((1, 4, 4))
+        rc = lib.imc_model_expm_batch_device(4, -1, A.ctypes.data_as(_dp), A.ctypes.data_as(_dp))
+    else:
+        rc, _, _ = call_transitions(lib, case, device=True, null=null)
+    assert rc == _capi.IMC_ERR_ARG, (what, rc, lib.imc_last_error())
+    assert lib.imc_last_error()
+    A = np.zeros((1, 129, 129))
+    assert lib.imc_model_expm_batch_device(129, 1, A.ctypes.data_as(_dp), A.ctypes.data_as(_dp)) == _capi.IMC_ERR_ARG
+    assert lib.imc_model_expm_batch_device(4, 1, None, A.ctypes.data_as(_dp)) == _capi.IMC_ERR_ARG
+
+
+def test_valid_calls_without_a_device_say_so():
+    lib = _lib()
+    if lib.imc_device_count() > 0:
+        pytest.skip("a device is present: tests/test_gpu_model_device.py runs the calls")
+    rc, _, _ = call_transitions(lib, one_space_case(6, 3), device=True)
+    assert rc == _capi.IMC_ERR_NODEVICE, (rc, lib.imc_last_error())
+    A = np.zeros((2, 4, 4))
+    out = np.empty_like(A)
+    assert lib.imc_model_expm_batch_device(4, 2, A.ctypes.data_as(_dp), out.ctypes.data_as(_dp)) == _capi.IMC_ERR_NODEVICE
+    # the host form of the same call works
+    rc, pi, T = call_transitions(lib, one_space_case(6, 3), device=False)
+    assert rc == 0 and abs(pi.sum() - 1) < 1e-12
+
+
+def test_switch_without_a_device_falls_back_to_numpy():
+    lib = _lib()
+    if lib.imc_device_count() > 0:
+        pytest.skip("a device is present: tests/test_gpu_model_device.py covers the routed path")
+    model = M.IsolationMigrationModel(3, 3)
+    theta = np.array([0.001, 0.001, 1000.0, 0.4, 200.0])
+    thetas = np.stack([theta * (1.0 + 0.03 * k) for k in range(3)])
+    off = model.build_batch(thetas)
+    calls = M._native["device_calls"]
+    was = M.set_device_transitions(True)
+    try:
+        assert was is False                                   # the default is off
+        on = model.build_batch(thetas)
+    finally:
+        M.set_device_transitions(was)
+    assert M._native["device_calls"] == calls == 0
+    for a, b in zip(off, on):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_host_expm_is_unchanged_bit_for_bit():
+    """imc_model_expm on the matrices of test_native_expm_matches_scipy against the bytes the library returned before the
+    degree / squaring choice moved into imc_model::expm_plan (tests/golden/make_expm_host_golden.py)."""
+    lib = _lib()
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_expm_host_golden", os.path.join(HERE, "golden", "make_expm_host_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    gold = np.load(os.path.join(HERE, "golden", "expm_host_golden.npz"))
+    seen = 0
+    for n, scale, Q in gen.matrices():
+        want = gold["n%d_s%g" % (n, scale)]
+        got = gen.host_expm(lib, Q)
+        assert got.tobytes() == want.tobytes(), (n, scale, np.abs(got - want).max())
+        seen += 1
+    assert seen == len(gold.files) == 55
+
+
+def test_model_kernels_do_not_spill():
+    src = '#include <hip/hip_runtime.h>\n#include "kernels_model.hpp"\n'
+    with tempfile.TemporaryDirectory() as tmp:
+        tu = os.path.join(tmp, "model_kernels.hip")
+        with open(tu, "w") as fh:
+            fh.write(src)
+        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
+               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+    name, seen = None, {}
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name and re.match(r"_Z\d+k_model_", name):
+            seen[name] = int(m.group(1))
+    assert len(seen) >= 3, seen                               # k_model_expm, k_model_joint, k_model_unpad
+    assert all(v == 0 for v in seen.values()), seen
