@@ -49,10 +49,13 @@
 #include "kernels_zip3.hpp"
 #include "kernels_zip4.hpp"
 #include "pair_dict.hpp"
+#include "plan_host.hpp"
 #include "model_host.hpp"
 #include "kernels_model.hpp"
 #include "../../include/imcoal_model.h"
 #include "obs_io.hpp"
+
+static_assert(sizeof(imc::Desc4) == sizeof(int4) && alignof(imc::Desc4) == alignof(int4), "descriptor entries are uploaded as int4");
 
 namespace {
 
@@ -172,10 +175,10 @@ struct Ctx {
     uint64_t last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t r1_checked = 0, r1_collapsed = 0;   // last call: operator segments tested / certified rank one
     std::string last_kernels;   // propagate kernels of the last enqueue, e.g. "k_zpropagate2<5>[tokens]"
+    std::vector<const void *> lds_opted;   // kernels of this device that may use LDS_BUDGET bytes of dynamic LDS (allow_lds_budget)
 } g;
 
 void drop_plans();
-void reset_kernel_attributes();
 void model_release();
 
 int ensure_ctx()
@@ -379,12 +382,8 @@ std::shared_ptr<DictDev> make_dictionary(const uint8_t *host, const imc::tok_t *
             imc::train_dict_wide(nd->dict, std::vector<imc::tok_t>(lvl256.begin() + 1, lvl256.begin() + 1 + nt), wide_min_count(nt), max_depth);
         }
     }
-    nd->depth.assign(nd->dict.alphabet, 0);
-    for (int z = nsym; z < nd->dict.alphabet; ++z)
-        nd->depth[z] = 1 + std::max(nd->depth[nd->dict.left[z]], nd->depth[nd->dict.right[z]]);
-    for (int z = nsym; z < nd->dict.alphabet; ++z) nd->order.push_back((uint16_t)z);
-    std::stable_sort(nd->order.begin(), nd->order.end(),
-                     [&](uint16_t x, uint16_t y) { return nd->depth[x] < nd->depth[y]; });
+    nd->depth = imc::dict_depths(nd->dict);
+    nd->order = imc::dict_order(nd->dict, nd->depth);
     return nd;
 }
 
@@ -508,28 +507,24 @@ using ChainFn = void (*)(const ChainDesc *, int, const uint32_t *, uint32_t, uin
                          const int *, uint32_t, double *, int *, double *, int);
 
 struct KernelChoice {
-    int R, G, NP, VPW, minw;       // R == 0: large-N GEMM-chain path (kernels_big.hpp), NP = 32 * TR
-    void (*plain)(PropArgs);
-    void (*zip)(PropArgs);
-    size_t (*zip_lds)(int);
-    ChainFn chain;
-    bool zip_attr_set;
-    void (*big_table_raw)(BigArgs);
-    void (*big_table_level)(BigArgs, const uint16_t *, int);
-    void (*big_prop)(BigArgs, const BigBlock *);
-    int big_prop_waves;            // wavefronts per workgroup of big_prop (NT, or 8 for the dealt-tiles variant)
-    void (*big_vec)(BigArgs, const BigBlock *, int, int);
-    void (*big_vec_tail)(BigArgs, const BigBlock *, int, int);   // rank-one hand-off: mat-vec chain over segment tails
-    int big_vec_waves;
-    int big_nslab;
-    size_t big_lds;
-    void (*zip2)(BigArgs);         // register-blocked token kernel (NP = 4 RB <= 24), else null
-    size_t (*zip2_lds)(int);
-    bool zip2_attr_set;
-    bool plain_attr_set = false;
+    int R = 0, G = 0, NP = 0, VPW = 0, minw = 1;   // R == 0: large-N GEMM-chain path (kernels_big.hpp), NP = 16 * G
+    void (*plain)(PropArgs) = nullptr;
+    void (*zip)(PropArgs) = nullptr;
+    size_t (*zip_lds)(int) = nullptr;
+    ChainFn chain = nullptr;
+    void (*big_table_raw)(BigArgs) = nullptr;
+    void (*big_table_level)(BigArgs, const uint16_t *, int) = nullptr;
+    void (*big_prop)(BigArgs, const BigBlock *) = nullptr;
+    int big_prop_waves = 0;        // wavefronts per workgroup of big_prop (NT, or 8 for the dealt-tiles variant)
+    void (*big_vec)(BigArgs, const BigBlock *, int, int) = nullptr;
+    void (*big_vec_tail)(BigArgs, const BigBlock *, int, int) = nullptr;   // rank-one hand-off: mat-vec chain over segment tails
+    int big_vec_waves = 0;
+    int big_nslab = 0;
+    size_t big_lds = 0;
+    void (*zip2)(BigArgs) = nullptr;   // register-blocked token kernel (NP = 4 RB <= 24), else null
+    size_t (*zip2_lds)(int) = nullptr;
     void (*zip3)(BigArgs) = nullptr;   // ... its fp64-MFMA form (same launch geometry and block list)
     size_t (*zip3_lds)(int) = nullptr;
-    bool zip3_attr_set = false;
     void (*zip4)(BigArgs) = nullptr;   // ... with the hybrid LDS / L2 operator table, and the kernels that build that table
     void (*zip4w)(BigArgs) = nullptr;  // ... on 16-bit token streams (dictionary levels beyond 256 tokens)
     void (*zip4s)(BigArgs) = nullptr, (*zip4sw)(BigArgs) = nullptr;   // ... with the STREAMED table (nothing cached in LDS)
@@ -549,7 +544,6 @@ struct KernelChoice {
     bool wide_blocked = false;         // 25-32 states: of the blocked family only the streamed scan and the one-depth table build exist
     int z4_slots() const { return z4_waves * 4; }
     bool chain_self_emax = false;      // the stitch kernel finds the units' largest exponents itself (no k_emax launch)
-    bool zip4_attr_set = false, zip4w_attr_set = false, zip4s_attr_set = false, zip4sw_attr_set = false, zip4_attr_l3 = false;
     // the blocked kernel in use (g.blocked_variant) and its LDS need for an alphabet of A tokens
     bool use3() const;
     size_t blocked_lds(int A) const { return use3() ? zip3_lds(A) : zip2_lds(A); }
@@ -559,8 +553,12 @@ template <int R, int G, int MW>
 KernelChoice make_kc()
 {
     constexpr int NP = R * G;
-    KernelChoice k{R, G, NP, 64 / G, MW, k_propagate<R, G, MW>, k_zpropagate<R, G>, &ZipGeom<R, G>::lds_bytes,
-                   k_chain<NP, (NP <= 12 ? 6 : NP <= 24 ? 4 : NP <= 32 ? 3 : NP <= 64 ? 2 : 1)>, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, false};
+    KernelChoice k;
+    k.R = R; k.G = G; k.NP = NP; k.VPW = 64 / G; k.minw = MW;
+    k.plain = k_propagate<R, G, MW>;
+    k.zip = k_zpropagate<R, G>;
+    k.zip_lds = &ZipGeom<R, G>::lds_bytes;
+    k.chain = k_chain<NP, (NP <= 12 ? 6 : NP <= 24 ? 4 : NP <= 32 ? 3 : NP <= 64 ? 2 : 1)>;
     k.chain_self_emax = true;          // (k_chain<NP, D > 0>: one wavefront, prefetch ring)
     if constexpr (NP % 4 == 0 && NP <= 24) {
         k.zip2 = k_zpropagate2<NP / 4>;
@@ -602,14 +600,22 @@ KernelChoice make_kc()
 template <int NT, int NSLAB>
 KernelChoice make_big()
 {
-    constexpr int NP = 16 * NT;   // NT wavefronts per workgroup
     // NT = 6, 10, 14: one tile-row per wavefront would load the SIMDs unevenly -> tiles dealt over 8 wavefronts
     constexpr bool dealt = NT > 4 && NT % 4 != 0;
-    void (*prop)(BigArgs, const BigBlock *) = k_big_propagate<NT, NSLAB>;
-    if constexpr (dealt) prop = k_big_propagate_s<NT, NSLAB>;
-    return KernelChoice{0, NT, NP, 0, 1, nullptr, nullptr, nullptr, k_chain<NP, 0>, false, k_big_table_raw<NT>,
-                        k_big_table_level<NT>, prop, dealt ? BS_WAVES : NT, k_big_vector<NT, false>, k_big_vector<NT, true>, BigVec<NT>::WAVES, NSLAB,
-                        BigSlab<NT, NSLAB>::bytes, nullptr, nullptr, false};
+    KernelChoice k;
+    k.G = NT; k.NP = 16 * NT;          // NT wavefronts per workgroup
+    k.chain = k_chain<16 * NT, 0>;
+    k.big_table_raw = k_big_table_raw<NT>;
+    k.big_table_level = k_big_table_level<NT>;
+    k.big_prop = k_big_propagate<NT, NSLAB>;
+    if constexpr (dealt) k.big_prop = k_big_propagate_s<NT, NSLAB>;
+    k.big_prop_waves = dealt ? BS_WAVES : NT;
+    k.big_vec = k_big_vector<NT, false>;
+    k.big_vec_tail = k_big_vector<NT, true>;
+    k.big_vec_waves = BigVec<NT>::WAVES;
+    k.big_nslab = NSLAB;
+    k.big_lds = BigSlab<NT, NSLAB>::bytes;
+    return k;
 }
 
 bool KernelChoice::use3() const { return zip3 && g.blocked_variant >= 3; }
@@ -635,12 +641,6 @@ KernelChoice *choose_kernel(int N, bool prefer_gemm)
     for (auto &k : kChoices)
         if (k.NP >= N) return &k;
     return nullptr;
-}
-
-void reset_kernel_attributes()
-{
-    for (auto &k : kChoices) k.zip4_attr_l3 = k.zip_attr_set = k.zip2_attr_set = k.zip3_attr_set = k.zip4_attr_set = k.zip4w_attr_set = k.zip4s_attr_set = k.zip4sw_attr_set = k.plain_attr_set = false;
-    for (auto &k : kMidChoices) k.zip4_attr_l3 = k.zip_attr_set = k.zip2_attr_set = k.zip3_attr_set = k.zip4_attr_set = k.zip4w_attr_set = k.zip4s_attr_set = k.zip4sw_attr_set = k.plain_attr_set = false;
 }
 
 // ---- launch plan ----------------------------------------------------------------------------------
@@ -676,6 +676,8 @@ struct Group {             // one propagate launch
     std::vector<std::pair<int, int>> tab3;
     std::vector<int> tab_lvl;                 // host copy of the depth offsets
     int tab_nlvl = 0;
+    std::vector<std::pair<int, int>> table_runs;   // GEMM chain: (first, count) in the dictionary's depth order per k_big_table_level launch
+    imc::PhaseTable phases;                   // hybrid table: the XCD-affine grid of the scan (used when B > 1)
     double *d_Ctab = nullptr;
     double *d_Cpack = nullptr;                // big groups that run the mat-vec chain: packed copy of the table ([B][A][N][TS])
     int *d_cex = nullptr;
@@ -1511,13 +1513,12 @@ struct PlanBuilder {
                 std::vector<uint64_t> cnt((size_t)gr.A, 0);
                 for (int f : gr.chunks)
                     for (size_t z = 0; z < chunks[f]->tok_count[gr.level].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[gr.level][z];
-                std::vector<uint16_t> ids((size_t)gr.A);
-                for (int z = 0; z < gr.A; ++z) ids[z] = (uint16_t)z;
-                std::stable_sort(ids.begin(), ids.end(), [&](uint16_t x, uint16_t y) { return cnt[x] > cnt[y]; });
+                const std::vector<uint16_t> ids = imc::hot_order(cnt);
                 const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
                 gr.stream_table = wide || z4_streamed(tables, B);
                 gr.n_hot = gr.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
                 gr.hot.assign(ids.begin(), ids.begin() + gr.n_hot);
+                gr.phases = imc::xcd_phases(B, (int)gr.blocks.size());
                 e = up((void **)&gr.d_hot, gr.hot.data(), gr.hot.size() * sizeof(uint16_t));
                 if (e == hipSuccess) e = dev_alloc((void **)&gr.d_Ctab, (size_t)B * (gr.A + 1) * kc->tok_doubles * 8);
                 if (e == hipSuccess) e = dev_alloc((void **)&gr.d_cex, (size_t)B * (gr.A + 1) * 4 + 16);
@@ -1525,122 +1526,35 @@ struct PlanBuilder {
             if (gr.zip2 && gr.zip && e == hipSuccess) {
                 // merged tokens of this level's alphabet (ids S .. A-1) grouped by dictionary depth, for the table build
                 const DictDev &dd = *gr.dict;
-                std::vector<uint16_t> order;
-                std::vector<int> lvl(1, 0);
-                int cur = -1;
-                for (uint16_t z : dd.order) {                       // (sorted by depth, then id)
-                    if ((int)z >= gr.A) continue;
-                    if (dd.depth[z] != cur) {
-                        if (cur >= 0) lvl.push_back((int)order.size());
-                        cur = dd.depth[z];
-                    }
-                    order.push_back(z);
-                }
-                lvl.push_back((int)order.size());
-                gr.tab_nlvl = order.empty() ? 0 : (int)lvl.size() - 1;
-                gr.tab_lvl = lvl;
-                e = up((void **)&gr.d_tab_order, order.data(), order.size() * sizeof(uint16_t));
-                if (e == hipSuccess) e = up((void **)&gr.d_tab_lvl, lvl.data(), lvl.size() * sizeof(int));
+                const imc::DepthOrder o = imc::depth_order_below(dd.order, dd.depth, gr.A);
+                gr.tab_nlvl = o.nlvl;
+                gr.tab_lvl = o.lvl;
+                e = up((void **)&gr.d_tab_order, o.order.data(), o.order.size() * sizeof(uint16_t));
+                if (e == hipSuccess) e = up((void **)&gr.d_tab_lvl, o.lvl.data(), o.lvl.size() * sizeof(int));
                 if (e == hipSuccess && gr.zip4) {
-                    std::vector<int4> desc;
-                    for (uint16_t z : order) desc.push_back(make_int4((int)z, (int)dd.dict.left[z], (int)dd.dict.right[z], 0));
+                    const std::vector<imc::Desc4> desc = imc::level_descriptors(dd.dict, o);
+                    const imc::TableSchedule s2 = imc::pairs_schedule(dd.dict, dd.depth, o, S);
+                    const imc::TableSchedule s3 = imc::triples_schedule(dd.dict, dd.depth, o, S, gr.A);
+                    gr.tab2 = s2.launches;
+                    gr.tab3 = s3.launches;
                     e = up((void **)&gr.d_tab_desc, desc.data(), desc.size() * sizeof(int4));
-                    // two depths per launch (k_z4_level2): launch k builds depths 2k+1 and 2k+2; a second-depth token
-                    // whose child sits in the first depth recomputes it from the grandchildren.  Entries of a launch:
-                    // the first depth's, then the second depth's grouped by which children they recompute, every group
-                    // padded to whole wavefronts (four entries) with idle entries (token -1).
-                    std::vector<int4> d2;
-                    gr.tab2.clear();
-                    auto pad4 = [&]() { while ((d2.size() / 2) % 4) { d2.push_back(make_int4(-1, 0, 0, 0)); d2.push_back(make_int4(0, 0, 0, 0)); } };
-                    for (int d = 0; d < gr.tab_nlvl; d += 2) {
-                        const int first = (int)(d2.size() / 2);
-                        for (int k = lvl[d]; k < lvl[d + 1]; ++k) {
-                            const int z = order[k];
-                            d2.push_back(make_int4(z, (int)dd.dict.left[z], (int)dd.dict.right[z], 0));
-                            d2.push_back(make_int4(0, 0, 0, 0));
-                        }
-                        pad4();
-                        if (d + 1 < gr.tab_nlvl) {
-                            const int d_first = dd.depth[order[lvl[d]]];
-                            for (int flags = 1; flags <= 3; ++flags) {
-                                for (int k = lvl[d + 1]; k < lvl[d + 2]; ++k) {
-                                    const int z = order[k], zl = dd.dict.left[z], zr = dd.dict.right[z];
-                                    const bool nl = zl >= S && dd.depth[zl] == d_first, nr = zr >= S && dd.depth[zr] == d_first;
-                                    if ((nl ? 1 : 0) + (nr ? 2 : 0) != flags) continue;
-                                    d2.push_back(make_int4(z, zl, zr, flags));
-                                    d2.push_back(make_int4(nl ? (int)dd.dict.left[zl] : 0, nl ? (int)dd.dict.right[zl] : 0,
-                                                           nr ? (int)dd.dict.left[zr] : 0, nr ? (int)dd.dict.right[zr] : 0));
-                                }
-                                pad4();
-                            }
-                        }
-                        gr.tab2.push_back({first, (int)(d2.size() / 2) - first});
-                    }
-                    if (e == hipSuccess && !d2.empty()) e = up((void **)&gr.d_tab_desc2, d2.data(), d2.size() * sizeof(int4));
-                    // three depths per launch (k_z4_level3): launch k builds depths 3k+1 .. 3k+3, one wavefront per token;
-                    // a token's eight leaves are the nodes of its dictionary tree that lie at depth <= 3k (already in the
-                    // table), a ready node in the first leaf of its range and the identity in the rest of it
-                    std::vector<int4> d3;
-                    gr.tab3.clear();
-                    for (int d = 0; d < gr.tab_nlvl; d += 3) {
-                        const int first = (int)(d3.size() / 3);
-                        const int d_ready = dd.depth[order[lvl[d]]] - 1;            // entries up to this depth exist
-                        for (int k = lvl[d]; k < lvl[std::min(d + 3, gr.tab_nlvl)]; ++k) {
-                            int leaves[8];
-                            for (int &x : leaves) x = gr.A;                       // the identity entry
-                            struct Fill {
-                                const DictDev &dd; int S, d_ready; int *leaves;
-                                void operator()(int t, int lo, int hi) const
-                                {
-                                    if (t < S || dd.depth[t] <= d_ready || hi - lo == 1) { leaves[lo] = t; return; }
-                                    const int mid = (lo + hi) / 2;
-                                    (*this)((int)dd.dict.left[t], lo, mid);
-                                    (*this)((int)dd.dict.right[t], mid, hi);
-                                }
-                            } fill{dd, S, d_ready, leaves};
-                            fill((int)order[k], 0, 8);
-                            d3.push_back(make_int4((int)order[k], leaves[0], leaves[1], leaves[2]));
-                            d3.push_back(make_int4(leaves[3], leaves[4], leaves[5], leaves[6]));
-                            d3.push_back(make_int4(leaves[7], 0, 0, 0));
-                        }
-                        gr.tab3.push_back({first, (int)(d3.size() / 3) - first});
-                    }
-                    if (e == hipSuccess && !d3.empty()) e = up((void **)&gr.d_tab_desc3, d3.data(), d3.size() * sizeof(int4));
+                    if (e == hipSuccess && !s2.desc.empty()) e = up((void **)&gr.d_tab_desc2, s2.desc.data(), s2.desc.size() * sizeof(int4));
+                    if (e == hipSuccess && !s3.desc.empty()) e = up((void **)&gr.d_tab_desc3, s3.desc.data(), s3.desc.size() * sizeof(int4));
                 }
             }
             if (!gr.big || e != hipSuccess) continue;
             const size_t np2 = (size_t)kc->NP * kc->NP;
-            // workgroup list: slabs of one segment 8 ids apart (same XCD -> they share the operator rows in L2)
-            {
-                std::vector<BigBlock> lin;
-                for (size_t i2 = 0; i2 < gr.seg_ids.size(); ++i2) {
-                    const bool fst = seg_first[gr.seg_ids[i2]] != 0;
-                    for (int sl = 0; sl < (fst ? 1 : kc->big_nslab); ++sl)
-                        lin.push_back(BigBlock{gr.seg_ids[i2], (uint32_t)sl, gr.seg_out[i2], 0u});
-                }
-                // lin is segment-major; re-deal non-first segments in tiles of 8 segments x nslab
-                gr.big_blocks.clear();
-                std::vector<BigBlock> firsts, rest;
-                for (const BigBlock &bb : lin) (seg_first[bb.seg] ? firsts : rest).push_back(bb);
-                const size_t ns = (size_t)kc->big_nslab;
-                for (size_t base = 0; base < rest.size(); base += 8 * ns) {
-                    const size_t nseg = std::min<size_t>(8, (rest.size() - base) / ns);
-                    for (size_t sl = 0; sl < ns; ++sl)
-                        for (size_t k2 = 0; k2 < nseg; ++k2) gr.big_blocks.push_back(rest[base + k2 * ns + sl]);
-                }
-                for (const BigBlock &bb : firsts) gr.big_blocks.push_back(bb);
-            }
+            if (gr.zip) gr.table_runs = imc::depth_runs_below(gr.dict->order, gr.dict->depth, gr.A);
+            gr.big_blocks = imc::deal_slabs<BigBlock>(gr.seg_ids, gr.seg_out, seg_first, kc->big_nslab);
             e = up((void **)&gr.d_big_blocks, gr.big_blocks.data(), gr.big_blocks.size() * sizeof(BigBlock));
             if (e == hipSuccess) e = dev_alloc((void **)&gr.d_Ctab, (size_t)B * gr.A * np2 * 8);
             if (e == hipSuccess && (gr.bigvec || gr.rank1) && N < kc->NP && g.pack_table)   // the mat-vec chain reads a packed copy
                 e = dev_alloc((void **)&gr.d_Cpack, (size_t)B * gr.A * N * (size_t)(N + (N & 1)) * 8);
             if (e == hipSuccess) e = dev_alloc((void **)&gr.d_cex, (size_t)B * gr.A * 4 + 16);
             if (gr.rank1) {
-                for (size_t i2 = 0; i2 < gr.seg_ids.size(); ++i2)
-                {
-                    gr.tail_blocks.push_back(BigBlock{gr.seg_ids[i2], 0u, gr.seg_out[i2], 0u});   // (first segments included)
-                    if (!seg_first[gr.seg_ids[i2]]) gr.r1_segs.push_back({gr.seg_ids[i2], segs[gr.seg_ids[i2]].len});
-                }
+                gr.tail_blocks = imc::tail_list<BigBlock>(gr.seg_ids, gr.seg_out);
+                for (uint32_t id : gr.seg_ids)
+                    if (!seg_first[id]) gr.r1_segs.push_back({id, segs[id].len});
                 const size_t nrec = (size_t)B * segs.size();
                 if (e == hipSuccess) e = up((void **)&gr.d_tail_blocks, gr.tail_blocks.data(), gr.tail_blocks.size() * sizeof(BigBlock));
                 if (e == hipSuccess) e = zalloc((void **)&gr.d_r1flag, nrec * 4);
@@ -1806,38 +1720,85 @@ int stage_params(Plan *p, const double *pis, const double *Ts, const double *Es,
     return IMC_OK;
 }
 
-// Enqueue one batch evaluation on `stream`: parameter upload, propagate, stitch.  Per-chunk results are written
-// to `out` ([B][n_chunks]; device memory or mapped pinned host memory).  Contains no synchronisation, so the
-// same call sequence can be captured into a hipGraph.
-int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
-{
+// ---- enqueue: shared state, then one function per kernel family --------------------------------------------
+
+// What the launches of one enqueue() share.
+struct Launch {
+    Plan *p;
+    hipStream_t stream;
+    double *out;
+    bool allow_tail;
     KernelChoice *kc = p->kc;
-    const int N = p->N, S = p->S, NP = kc->NP, B = p->B;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    if (cap == hipStreamCaptureStatusNone && p->have_last && p->last_stream != stream)
-        HIP_TRY(hipStreamWaitEvent(stream, p->ev_params[p->last_slot], 0));     // the plan's previous call ran on another stream
-    // Parameter upload.  Small sets (every BASELINE shape but the 64-proposal batch at N = 150) are fetched by a kernel
-    // from the mapped staging slot: a copy command costs its own ~3 us plus a ~10 us hand-over between the copy and the
-    // first kernel (rocprofv3 kernel trace), a kernel in the same queue costs one launch.
+    int B = p->B;
+    bool fuse_head = false;       // the first table launch fetches the parameters itself: no k_stage_params, no k_z4_raw
+    bool direct_params = false;   // the few workgroups of a small k_zpropagate3 launch fetch them themselves
+    // Profiling: ev.a .. ev.b brackets the propagate kernel(s).  For k_zpropagate4, whose operator table is built by
+    // launches of its own, ev.a goes between the table launches and the scan: "kernel_ms" is then the duration of the
+    // scan launch itself - the number rocprofv3's per-kernel average has to agree with.
+    bool prof = false, a_recorded = false;
+    Ev3 ev{nullptr, nullptr, nullptr};
+    bool split_used = false;      // a table launch took the column-split form
+    bool tail_used = false;       // the propagate launch finishes the chunks itself (zip3_tail): no stitch launches
+
+    int mark_a()
+    {
+        if (prof && !a_recorded) { HIP_TRY(hipEventRecord(ev.a, stream)); a_recorded = true; }
+        return IMC_OK;
+    }
+    void note(const std::string &k) const { p->kernels += (p->kernels.empty() ? "" : "+") + k; }
+    // imc_last_plan's numbers: segment length, vector-steps (and stream length, alphabet) of the column / token groups
+    void account(const Group &gr) const
+    {
+        uint64_t *lp = p->lp;
+        if (gr.zip) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
+        else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
+    }
+    int fetch_params();
+    BigArgs blocked_args(const Group &gr);
+    int big_table(const Group &gr, const BigArgs &ba) const;
+    int matvec_chain(const Group &gr);
+    int gemm_chain(const Group &gr);
+    int z4_table(const Group &gr, const BigArgs &ba);
+    int zip4(const Group &gr);
+    int zip32(const Group &gr);
+    int zpropagate(const Group &gr);
+    int propagate(const Group &gr);
+    int stitch() const;
+};
+
+const char *stream_tag(const Group &gr) { return gr.zip ? "[tokens]" : "[columns]"; }
+
+// Opt a kernel in to LDS_BUDGET bytes of dynamic LDS: one hipFuncSetAttribute per function and device (g.lds_opted).
+template <class Fn>
+int allow_lds_budget(Fn *fn)
+{
+    const void *f = (const void *)fn;
+    if (std::find(g.lds_opted.begin(), g.lds_opted.end(), f) != g.lds_opted.end()) return IMC_OK;
+    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
+    g.lds_opted.push_back(f);
+    return IMC_OK;
+}
+
+// Parameter upload.  Small sets (every BASELINE shape but the 64-proposal batch at N = 150) are fetched by a kernel
+// from the mapped staging slot: a copy command costs its own ~3 us plus a ~10 us hand-over between the copy and the
+// first kernel (rocprofv3 kernel trace), a kernel in the same queue costs one launch.
+int Launch::fetch_params()
+{
     const size_t pbytes = (size_t)B * p->pstride * 8;
     // One streamed / hybrid-table group and nothing else (BASELINE config[1], the config[3] slice): the first table launch
     // fetches the parameters itself (k_z4_level2<., true>) - no k_stage_params, no k_z4_raw.
-    bool fuse_head = false, direct_params = false;
-    {
-        int active = 0;
-        const Group *only = nullptr;
-        for (const Group &gr : p->groups)
-            if (gr.n_vecs) { ++active; only = &gr; }
-        const size_t head_lds = p->pstride * 8;
-        fuse_head = g.fuse_head && active == 1 && only->zip4 && g.table_pairs && only->d_tab_desc2 && !only->tab2.empty() &&
-                    kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
-        // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
-        // columns): each of its few workgroups fetches the parameter set itself
-        direct_params = g.fuse_head && active == 1 && only->zip2 && !only->zip4 && kc->use3() && pbytes <= STAGE_KERNEL_MAX_BYTES &&
-                        only->blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
-                        ((kc->blocked_lds(only->A) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
-    }
+    int active = 0;
+    const Group *only = nullptr;
+    for (const Group &gr : p->groups)
+        if (gr.n_vecs) { ++active; only = &gr; }
+    const size_t head_lds = p->pstride * 8;
+    fuse_head = g.fuse_head && active == 1 && only->zip4 && g.table_pairs && only->d_tab_desc2 && !only->tab2.empty() &&
+                kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
+    // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
+    // columns): each of its few workgroups fetches the parameter set itself
+    direct_params = g.fuse_head && active == 1 && only->zip2 && !only->zip4 && kc->use3() && pbytes <= STAGE_KERNEL_MAX_BYTES &&
+                    only->blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
+                    ((kc->blocked_lds(only->A) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
     if (fuse_head || direct_params) {
         // (nothing to enqueue here)
     } else if (pbytes <= STAGE_KERNEL_MAX_BYTES) {
@@ -1848,267 +1809,263 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
     } else {
         HIP_TRY(hipMemcpyAsync(p->d_params, p->h_params[p->slot], pbytes, hipMemcpyHostToDevice, stream));
     }
+    return IMC_OK;
+}
 
-    uint64_t *lp = p->lp;
-    lp[0] = p->n_segs; lp[1] = p->n_vecs; lp[2] = lp[3] = lp[4] = lp[5] = lp[6] = lp[7] = 0;
-    Ev3 ev{nullptr, nullptr, nullptr};
-    const bool prof = g.profile && p->n_vecs;
-    // Profiling: ev.a .. ev.b brackets the propagate kernel(s).  For k_zpropagate4, whose operator table is built by
-    // launches of its own, ev.a goes between the table launches and the scan: "kernel_ms" is then the duration of the
-    // scan launch itself - the number rocprofv3's per-kernel average has to agree with.
-    bool a_recorded = false;
-    if (prof) { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); HIP_TRY(hipEventCreate(&ev.c)); }
-#define IMC_MARK_A() do { if (prof && !a_recorded) { HIP_TRY(hipEventRecord(ev.a, stream)); a_recorded = true; } } while (0)
-    bool split_used = false;            // a table launch took the column-split form
-    bool tail_used = false;             // the propagate launch finishes the chunks itself (zip3_tail): no stitch launches
-    p->kernels.clear();
-    auto note = [&](const std::string &k) { p->kernels += (p->kernels.empty() ? "" : "+") + k; };
-    for (const Group &gr : p->groups) {
-        if (!gr.n_vecs) continue;
-        if (!gr.zip4) IMC_MARK_A();
-        const std::string strm = gr.zip ? "[tokens]" : "[columns]";
-        PropArgs a;
-        a.segs = p->d_segs; a.vecs = p->d_vecs + gr.vec_begin; a.n_vecs = gr.n_vecs; a.vec_base = gr.vec_begin;
-        a.n_vecs_total = p->n_vecs; a.N = N; a.S = S;
-        a.params = p->d_params; a.pstride = p->pstride; a.P = p->levels[0].d_P; a.EX = p->levels[0].d_EX;
-        a.A = gr.A; a.tok_left = gr.zip ? gr.dict->d_left : nullptr; a.tok_right = gr.zip ? gr.dict->d_right : nullptr;
-        if (gr.big) {
-            BigArgs ba;
-            ba.n_phases = 0;
-            ba.tail = nullptr; ba.tailX = nullptr; ba.tailE = nullptr; ba.tail_arrive = nullptr; ba.tail_out = nullptr; ba.tail_stride = 0; ba.n_chunks = p->n_chunks;
-            ba.segs = p->d_segs; ba.seg_ids = gr.d_seg_ids; ba.seg_vec0 = gr.d_seg_out; ba.blocks = nullptr;
-            ba.n_group_segs = (uint32_t)gr.seg_ids.size(); ba.n_vecs_total = p->n_vecs;
-            ba.N = N; ba.S = S; ba.A = gr.A; ba.params = p->d_params; ba.params_src = nullptr; ba.pstride = p->pstride; ba.PP = NP;
-            ba.tok_left = gr.zip ? gr.dict->d_left : nullptr; ba.tok_right = gr.zip ? gr.dict->d_right : nullptr;
-            ba.Ctab = gr.d_Ctab; ba.cex = gr.d_cex;
-            ba.Cpack = gr.d_Cpack; ba.TS = N + (N & 1);
-            ba.P = p->levels[0].d_P; ba.EX = p->levels[0].d_EX;
-            ba.phase = gr.rank1 ? 1 : 0; ba.t_from = 0; ba.t_to = gr.rank1 ? gr.checkpoints[0] : INT_MAX;
-            ba.r1flag = gr.d_r1flag; ba.r1at = gr.d_r1at; ba.r1u = gr.d_r1u;
-            ba.r1alpha = gr.d_r1alpha; ba.n_segs = p->n_segs;
-            ba.tab_order = nullptr; ba.tab_lvl = nullptr; ba.tab_nlvl = 0; ba.hot = nullptr; ba.n_hot = 0; ba.tab_desc = nullptr;
-            if (gr.rank1) HIP_TRY(hipMemsetAsync(gr.d_r1flag, 0, (size_t)B * p->n_segs * 4, stream));   // nothing certified yet
-            hipLaunchKernelGGL(kc->big_table_raw, dim3((unsigned)S, (unsigned)B), dim3(kc->G * 64), 0, stream, ba);
-            HIP_TRY(hipGetLastError());
-            if (gr.zip) {   // merged tokens, one launch per dictionary depth (tokens of a depth are independent)
-                const DictDev &dd = *gr.dict;
-                size_t i0 = 0;
-                while (i0 < dd.order.size()) {   // tokens >= A are not part of this level's alphabet: filtered below
-                    size_t i1 = i0;
-                    while (i1 < dd.order.size() && dd.depth[dd.order[i1]] == dd.depth[dd.order[i0]]) ++i1;
-                    // launch the contiguous sub-runs of [i0,i1) whose token id < A
-                    size_t r0 = i0;
-                    while (r0 < i1) {
-                        while (r0 < i1 && (int)dd.order[r0] >= gr.A) ++r0;
-                        size_t r1 = r0;
-                        while (r1 < i1 && (int)dd.order[r1] < gr.A) ++r1;
-                        if (r1 > r0) {
-                            hipLaunchKernelGGL(kc->big_table_level, dim3((unsigned)(r1 - r0), (unsigned)B), dim3(kc->G * 64), 0,
-                                               stream, ba, (const uint16_t *)dd.d_order, (int)r0);
-                            HIP_TRY(hipGetLastError());
-                        }
-                        r0 = r1;
-                    }
-                    i0 = i1;
-                }
-            }
-            if (gr.bigvec) {
-                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.big_blocks.size() * (unsigned)((B + 7) / 8)
-                                             : (unsigned)gr.big_blocks.size() * (unsigned)B;
-                hipLaunchKernelGGL(kc->big_vec, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                                   (const BigBlock *)gr.d_big_blocks, (int)gr.big_blocks.size(), B);
-                note("k_big_vector<" + std::to_string(kc->G) + ">" + strm);
-                if (gr.zip) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
-                else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
-            if (!kc->zip_attr_set) {   // (flag reused: dynamic LDS size of the large-N propagate kernel)
-                HIP_TRY(hipFuncSetAttribute((const void *)kc->big_prop, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)LDS_BUDGET));
-                kc->zip_attr_set = true;
-            }
-            hipLaunchKernelGGL(kc->big_prop, dim3((unsigned)gr.big_blocks.size(), (unsigned)B), dim3(kc->big_prop_waves * 64), kc->big_lds,
-                               stream, ba, (const BigBlock *)gr.d_big_blocks);
-            note(std::string(kc->big_prop_waves != kc->G ? "k_big_propagate_s<" : "k_big_propagate<") + std::to_string(kc->G) + ">" + strm);
-            if (gr.rank1 && !gr.tail_blocks.empty()) {
-                // The first round of heads is done.  Per checkpoint: certify which of the operators still on the GEMM
-                // chain collapsed to rank one, then run the others up to the next checkpoint; after the last one the
-                // certified segments finish on the mat-vec chain and the rest on the GEMM chain.  Every launch covers
-                // all segments and a workgroup with nothing to do exits at once, so there is no host round trip.
-                for (size_t r = 0; r < gr.checkpoints.size(); ++r) {
-                    HIP_TRY(hipGetLastError());
-                    ba.t_to = gr.checkpoints[r];
-                    hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
-                                       (const BigBlock *)gr.d_tail_blocks, NP);
-                    HIP_TRY(hipGetLastError());
-                    ba.t_from = gr.checkpoints[r];
-                    ba.t_to = r + 1 < gr.checkpoints.size() ? gr.checkpoints[r + 1] : INT_MAX;
-                    if (r + 1 == gr.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
-                        const unsigned grid = B >= 8 ? 8u * (unsigned)gr.tail_blocks.size() * (unsigned)((B + 7) / 8)
-                                                     : (unsigned)gr.tail_blocks.size() * (unsigned)B;
-                        hipLaunchKernelGGL(kc->big_vec_tail, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                                           (const BigBlock *)gr.d_tail_blocks, (int)gr.tail_blocks.size(), B);
-                        HIP_TRY(hipGetLastError());
-                    }
-                    hipLaunchKernelGGL(kc->big_prop, dim3((unsigned)gr.big_blocks.size(), (unsigned)B), dim3(kc->big_prop_waves * 64), kc->big_lds,
-                                       stream, ba, (const BigBlock *)gr.d_big_blocks);
-                }
-                note("rank1-handoff");
-            }
-            if (gr.zip) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
-            else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
-        } else if (gr.zip2) {
-            BigArgs ba;
-            ba.n_phases = 0;
-            ba.tail = nullptr; ba.tailX = nullptr; ba.tailE = nullptr; ba.tail_arrive = nullptr; ba.tail_out = nullptr; ba.tail_stride = 0; ba.n_chunks = p->n_chunks;
-            ba.segs = p->d_segs; ba.seg_ids = nullptr; ba.seg_vec0 = nullptr; ba.blocks = gr.d_blocks;
-            ba.n_group_segs = (uint32_t)gr.blocks.size(); ba.n_vecs_total = p->n_vecs;
-            ba.N = N; ba.S = S; ba.A = gr.A; ba.params = p->d_params; ba.params_src = nullptr; ba.pstride = p->pstride; ba.PP = NP;
-            ba.tok_left = gr.zip ? gr.dict->d_left : nullptr; ba.tok_right = gr.zip ? gr.dict->d_right : nullptr;
-            ba.Ctab = nullptr; ba.cex = nullptr; ba.Cpack = nullptr; ba.TS = 0;
-            ba.P = p->levels[0].d_P; ba.EX = p->levels[0].d_EX;
-            ba.tab_order = gr.d_tab_order; ba.tab_lvl = gr.d_tab_lvl; ba.tab_nlvl = gr.tab_nlvl;
-            ba.hot = gr.d_hot; ba.n_hot = gr.n_hot; ba.tab_desc = gr.d_tab_desc;
-            if (gr.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.tail_stride <= 4)) && allow_tail && (kc->use3() || p->wide)) {
-                ba.tail = gr.d_tails; ba.tailX = gr.d_tailX; ba.tailE = gr.d_tailE; ba.tail_arrive = gr.d_tail_arrive;
-                ba.tail_out = out; ba.tail_stride = gr.tail_stride; ba.n_chunks = p->n_chunks;
-                tail_used = true;
-            }
-            if (gr.zip4) {
-                // hybrid table: one workgroup per parameter set builds the operators in global memory (they stay in
-                // L2), then the scan caches the hot ones in LDS and streams the rest a step ahead
-                ba.Ctab = gr.d_Ctab; ba.cex = gr.d_cex;
-                if (!fuse_head) {
-                    hipLaunchKernelGGL(kc->zip4_raw, dim3((unsigned)S + 1, (unsigned)B), dim3(256), 0, stream, ba);
-                    HIP_TRY(hipGetLastError());
-                }
-                if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && NP <= 12)) && gr.d_tab_desc3 && kc->zip4_level3) {
-                    bool head = fuse_head;
-                    if (!kc->zip4_attr_l3) {
-                        HIP_TRY(hipFuncSetAttribute((const void *)kc->zip4_level3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
-                        HIP_TRY(hipFuncSetAttribute((const void *)kc->zip4_level3_first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
-                        kc->zip4_attr_l3 = true;
-                    }
-                    for (const auto &lc : gr.tab3) {          // three dictionary depths per launch, one wavefront per token
-                        const dim3 grid((unsigned)(lc.second + Z4L3_WAVES - 1) / Z4L3_WAVES, (unsigned)B);
-                        if (head)
-                            hipLaunchKernelGGL(kc->zip4_level3_first, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(p->pstride), stream, ba,
-                                               (const int4 *)gr.d_tab_desc3, lc.first, lc.second, (const double *)p->h_params_dev[p->slot]);
-                        else
-                            hipLaunchKernelGGL(kc->zip4_level3, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(0), stream, ba,
-                                               (const int4 *)gr.d_tab_desc3, lc.first, lc.second, (const double *)nullptr);
-                        head = false;
-                        HIP_TRY(hipGetLastError());
-                    }
-                } else if (g.table_pairs && gr.d_tab_desc2 && kc->zip4_level2) {
-                    bool head = fuse_head;
-                    const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
-                    for (const auto &lc : gr.tab2) {          // two dictionary depths per launch
-                        if (g.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
-                            if (head)
-                                hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
-                                                   dim3(Z4_SPLIT_WAVES_FIRST * 64), p->pstride * 8, stream, ba,
-                                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)p->h_params_dev[p->slot]);
-                            else
-                                hipLaunchKernelGGL(kc->zip4_level2_split, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES - 1) / Z4_SPLIT_WAVES, (unsigned)B),
-                                                   dim3(Z4_SPLIT_WAVES * 64), 0, stream, ba,
-                                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)nullptr);
-                            split_used = true;
-                        } else if (head)
-                            hipLaunchKernelGGL(kc->zip4_level2_first, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64),
-                                               p->pstride * 8, stream, ba,
-                                               (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)p->h_params_dev[p->slot]);
-                        else
-                            hipLaunchKernelGGL(kc->zip4_level2, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba,
-                                               (const int4 *)gr.d_tab_desc2, lc.first, lc.second, (const double *)nullptr);
-                        head = false;
-                        HIP_TRY(hipGetLastError());
-                    }
-                } else
-                for (int d = 0; d < gr.tab_nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
-                    const int first = gr.tab_lvl[d], count = gr.tab_lvl[d + 1] - first;
-                    hipLaunchKernelGGL(kc->zip4_level, dim3((unsigned)(count + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba, first, count);
-                    HIP_TRY(hipGetLastError());
-                }
-                void (*scan)(BigArgs) = gr.stream_table ? (gr.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.wide_tokens ? kc->zip4w : kc->zip4);
-                bool &attr4 = gr.stream_table ? (gr.wide_tokens ? kc->zip4sw_attr_set : kc->zip4s_attr_set)
-                                              : (gr.wide_tokens ? kc->zip4w_attr_set : kc->zip4_attr_set);
-                if (!attr4) {
-                    HIP_TRY(hipFuncSetAttribute((const void *)scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET));
-                    attr4 = true;
-                }
-                IMC_MARK_A();
-                // XCD-affine grid (BigArgs::n_phases): with the two-dimensional grid every XCD's L2 sees the tables of all
-                // B parameter sets
-                dim3 scan_grid(ba.n_group_segs, (unsigned)B);
-                if (g.xcd_affine && B > 1) {
-                    int first = 0, wg = 0;
-                    auto phase = [&](int sets, int n_sets_total) {
-                        ba.ph_begin[ba.n_phases] = wg; ba.ph_first[ba.n_phases] = first; ba.ph_sets[ba.n_phases] = sets;
-                        ++ba.n_phases;
-                        const int nb = (int)ba.n_group_segs;
-                        wg += sets >= 8 ? 8 * nb * (n_sets_total / 8) : 8 * ((nb + 8 / sets - 1) / (8 / sets));
-                        first += n_sets_total;
-                    };
-                    if (B >= 8) phase(8, B / 8 * 8);
-                    for (int sets : {4, 2, 1})
-                        if ((B % 8) & sets) phase(sets, sets);
-                    scan_grid = dim3((unsigned)wg);
-                }
-                hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.n_hot), stream, ba);
-                note(std::string("k_zpropagate4<") + std::to_string(NP / 4) + (gr.wide_tokens ? ",16" : "") + (gr.stream_table ? ",streamed>" : ">") + strm);
-                lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A);
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
-            const bool v3 = kc->use3();
-            bool &attr_set = v3 ? kc->zip3_attr_set : kc->zip2_attr_set;
-            if (!attr_set) {
-                HIP_TRY(hipFuncSetAttribute((const void *)(v3 ? kc->zip3 : kc->zip2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)LDS_BUDGET));
-                attr_set = true;
-            }
-            size_t lds3 = kc->blocked_lds(gr.A);
-            if (direct_params) { ba.params_src = p->h_params_dev[p->slot]; lds3 = ((lds3 + 15) & ~(size_t)15) + p->pstride * 8; }
-            hipLaunchKernelGGL(v3 ? kc->zip3 : kc->zip2, dim3(ba.n_group_segs, (unsigned)B), dim3(Z2WAVES * 64), lds3, stream, ba);
-            note(std::string(v3 ? "k_zpropagate3<" : "k_zpropagate2<") + std::to_string(NP / 4) + ">" + strm);
-            if (gr.zip) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
-            else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
-        } else if (gr.zip) {
-            const size_t lds = kc->zip_lds(gr.A);
-            if (!kc->zip_attr_set) {
-                HIP_TRY(hipFuncSetAttribute((const void *)kc->zip, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)LDS_BUDGET));
-                kc->zip_attr_set = true;
-            }
-            const uint32_t vpb = (uint32_t)(ZWAVES * kc->VPW);
-            dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)B);
-            hipLaunchKernelGGL(kc->zip, grid, dim3(ZWAVES * 64), lds, stream, a);
-            note("k_zpropagate<" + std::to_string(kc->R) + "," + std::to_string(kc->G) + ">" + strm);
-            lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A);
-        } else {
-            const uint32_t vpb = (uint32_t)(WPB * kc->VPW);
-            dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)B);
-            const size_t lds = ((size_t)WPB * kc->VPW * NP + (size_t)S * NP) * 8;
-            if (lds > LDS_BUDGET) return fail(IMC_ERR_ARG, "emission table (S x N) too large for LDS");
-            if (lds > 48 * 1024 && !kc->plain_attr_set) {   // large alphabets: opt in to > 64 KB of dynamic LDS
-                HIP_TRY(hipFuncSetAttribute((const void *)kc->plain, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)LDS_BUDGET));
-                kc->plain_attr_set = true;
-            }
-            hipLaunchKernelGGL(kc->plain, grid, dim3(WPB * 64), lds, stream, a);
-            note("k_propagate<" + std::to_string(kc->R) + "," + std::to_string(kc->G) + ">" + strm);
-            lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B;
-        }
+PropArgs prop_args(const Plan *p, const Group &gr)
+{
+    PropArgs a;
+    a.segs = p->d_segs; a.vecs = p->d_vecs + gr.vec_begin; a.n_vecs = gr.n_vecs; a.vec_base = gr.vec_begin;
+    a.n_vecs_total = p->n_vecs; a.N = p->N; a.S = p->S;
+    a.params = p->d_params; a.pstride = p->pstride; a.P = p->levels[0].d_P; a.EX = p->levels[0].d_EX;
+    a.A = gr.A; a.tok_left = gr.zip ? gr.dict->d_left : nullptr; a.tok_right = gr.zip ? gr.dict->d_right : nullptr;
+    return a;
+}
+
+// The BigArgs every kernel of the GEMM-chain and blocked families starts from: whole segments (phase 0), no table, no
+// block list, no fused tail, the two-dimensional grid.  The families set what differs.
+BigArgs common_args(const Plan *p, const Group &gr)
+{
+    BigArgs ba{};
+    ba.segs = p->d_segs;
+    ba.n_vecs_total = p->n_vecs; ba.n_segs = p->n_segs; ba.n_chunks = p->n_chunks;
+    ba.N = p->N; ba.S = p->S; ba.A = gr.A; ba.params = p->d_params; ba.pstride = p->pstride; ba.PP = p->kc->NP;
+    ba.tok_left = gr.zip ? gr.dict->d_left : nullptr; ba.tok_right = gr.zip ? gr.dict->d_right : nullptr;
+    ba.Ctab = gr.d_Ctab; ba.cex = gr.d_cex;
+    ba.P = p->levels[0].d_P; ba.EX = p->levels[0].d_EX;
+    ba.t_to = INT_MAX;
+    return ba;
+}
+
+// ---- operator table in global memory: GEMM chain and mat-vec chain (kernels_big.hpp) ----
+
+BigArgs big_args(const Plan *p, const Group &gr)
+{
+    BigArgs ba = common_args(p, gr);
+    ba.seg_ids = gr.d_seg_ids; ba.seg_vec0 = gr.d_seg_out;
+    ba.n_group_segs = (uint32_t)gr.seg_ids.size();
+    ba.Cpack = gr.d_Cpack; ba.TS = p->N + (p->N & 1);
+    ba.phase = gr.rank1 ? 1 : 0; ba.t_to = gr.rank1 ? gr.checkpoints[0] : INT_MAX;
+    ba.r1flag = gr.d_r1flag; ba.r1at = gr.d_r1at; ba.r1u = gr.d_r1u; ba.r1alpha = gr.d_r1alpha;
+    return ba;
+}
+
+// Raw symbols, then the merged tokens: one launch per run of one dictionary depth (tokens of a depth are independent)
+int Launch::big_table(const Group &gr, const BigArgs &ba) const
+{
+    if (gr.rank1) HIP_TRY(hipMemsetAsync(gr.d_r1flag, 0, (size_t)p->B * p->n_segs * 4, stream));   // nothing certified yet
+    hipLaunchKernelGGL(kc->big_table_raw, dim3((unsigned)p->S, (unsigned)p->B), dim3(kc->G * 64), 0, stream, ba);
+    HIP_TRY(hipGetLastError());
+    for (const auto &run : gr.table_runs) {
+        hipLaunchKernelGGL(kc->big_table_level, dim3((unsigned)run.second, (unsigned)p->B), dim3(kc->G * 64), 0,
+                           stream, ba, (const uint16_t *)gr.dict->d_order, run.first);
         HIP_TRY(hipGetLastError());
     }
-    IMC_MARK_A();
-#undef IMC_MARK_A
-    if (prof) HIP_TRY(hipEventRecord(ev.b, stream));
-    if (split_used) note("table-split");
-    if (tail_used) note("fused-tail");
-    for (size_t l = 0; l + 1 < p->levels.size() && !tail_used; ++l) {
+    return IMC_OK;
+}
+
+// Every chunk is one segment: k_big_vector, no operators.
+int Launch::matvec_chain(const Group &gr)
+{
+    const BigArgs ba = big_args(p, gr);
+    if (int rc = big_table(gr, ba)) return rc;
+    const unsigned grid = B >= 8 ? 8u * (unsigned)gr.big_blocks.size() * (unsigned)((B + 7) / 8)
+                                 : (unsigned)gr.big_blocks.size() * (unsigned)B;
+    hipLaunchKernelGGL(kc->big_vec, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
+                       (const BigBlock *)gr.d_big_blocks, (int)gr.big_blocks.size(), B);
+    note("k_big_vector<" + std::to_string(kc->G) + ">" + stream_tag(gr));
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+// One workgroup per (segment, column slab): k_big_propagate, and the rounds of the rank-one hand-off.
+int Launch::gemm_chain(const Group &gr)
+{
+    BigArgs ba = big_args(p, gr);
+    if (int rc = big_table(gr, ba)) return rc;
+    if (int rc = allow_lds_budget(kc->big_prop)) return rc;
+    const dim3 prop_grid((unsigned)gr.big_blocks.size(), (unsigned)B), prop_block(kc->big_prop_waves * 64);
+    hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.d_big_blocks);
+    note(std::string(kc->big_prop_waves != kc->G ? "k_big_propagate_s<" : "k_big_propagate<") + std::to_string(kc->G) + ">" + stream_tag(gr));
+    if (gr.rank1 && !gr.tail_blocks.empty()) {
+        // The first round of heads is done.  Per checkpoint: certify which of the operators still on the GEMM
+        // chain collapsed to rank one, then run the others up to the next checkpoint; after the last one the
+        // certified segments finish on the mat-vec chain and the rest on the GEMM chain.  Every launch covers
+        // all segments and a workgroup with nothing to do exits at once, so there is no host round trip.
+        for (size_t r = 0; r < gr.checkpoints.size(); ++r) {
+            HIP_TRY(hipGetLastError());
+            ba.t_to = gr.checkpoints[r];
+            hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
+                               (const BigBlock *)gr.d_tail_blocks, kc->NP);
+            HIP_TRY(hipGetLastError());
+            ba.t_from = gr.checkpoints[r];
+            ba.t_to = r + 1 < gr.checkpoints.size() ? gr.checkpoints[r + 1] : INT_MAX;
+            if (r + 1 == gr.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
+                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.tail_blocks.size() * (unsigned)((B + 7) / 8)
+                                             : (unsigned)gr.tail_blocks.size() * (unsigned)B;
+                hipLaunchKernelGGL(kc->big_vec_tail, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
+                                   (const BigBlock *)gr.d_tail_blocks, (int)gr.tail_blocks.size(), B);
+                HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.d_big_blocks);
+        }
+        note("rank1-handoff");
+    }
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+// ---- register-blocked token kernels (kernels_zip2.hpp .. kernels_zip4.hpp) ----
+
+BigArgs Launch::blocked_args(const Group &gr)
+{
+    BigArgs ba = common_args(p, gr);
+    ba.blocks = gr.d_blocks;
+    ba.n_group_segs = (uint32_t)gr.blocks.size();
+    ba.tab_order = gr.d_tab_order; ba.tab_lvl = gr.d_tab_lvl; ba.tab_nlvl = gr.tab_nlvl;
+    ba.hot = gr.d_hot; ba.n_hot = gr.n_hot; ba.tab_desc = gr.d_tab_desc;
+    if (gr.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.tail_stride <= 4)) && allow_tail && (p->kc->use3() || p->wide)) {
+        ba.tail = gr.d_tails; ba.tailX = gr.d_tailX; ba.tailE = gr.d_tailE; ba.tail_arrive = gr.d_tail_arrive;
+        ba.tail_out = out; ba.tail_stride = gr.tail_stride;
+        tail_used = true;
+    }
+    return ba;
+}
+
+// The hybrid table's operators in global memory (they stay in L2): raw symbols, then the merged tokens three, two or
+// one dictionary depth per launch.
+int Launch::z4_table(const Group &gr, const BigArgs &ba)
+{
+    const double *const staged = p->h_params_dev[p->slot], *const none = nullptr;
+    bool head = fuse_head;              // the first launch: parameters + raw operators too
+    if (!fuse_head) {
+        hipLaunchKernelGGL(kc->zip4_raw, dim3((unsigned)p->S + 1, (unsigned)B), dim3(256), 0, stream, ba);
+        HIP_TRY(hipGetLastError());
+    }
+    if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && kc->NP <= 12)) && gr.d_tab_desc3 && kc->zip4_level3) {
+        if (int rc = allow_lds_budget(kc->zip4_level3)) return rc;
+        if (int rc = allow_lds_budget(kc->zip4_level3_first)) return rc;
+        for (const auto &lc : gr.tab3) {          // three dictionary depths per launch, one wavefront per token
+            const dim3 grid((unsigned)(lc.second + Z4L3_WAVES - 1) / Z4L3_WAVES, (unsigned)B);
+            if (head)
+                hipLaunchKernelGGL(kc->zip4_level3_first, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(p->pstride), stream, ba,
+                                   (const int4 *)gr.d_tab_desc3, lc.first, lc.second, staged);
+            else
+                hipLaunchKernelGGL(kc->zip4_level3, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(0), stream, ba,
+                                   (const int4 *)gr.d_tab_desc3, lc.first, lc.second, none);
+            head = false;
+            HIP_TRY(hipGetLastError());
+        }
+    } else if (g.table_pairs && gr.d_tab_desc2 && kc->zip4_level2) {
+        const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
+        for (const auto &lc : gr.tab2) {          // two dictionary depths per launch
+            if (g.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
+                if (head)
+                    hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
+                                       dim3(Z4_SPLIT_WAVES_FIRST * 64), p->pstride * 8, stream, ba,
+                                       (const int4 *)gr.d_tab_desc2, lc.first, lc.second, staged);
+                else
+                    hipLaunchKernelGGL(kc->zip4_level2_split, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES - 1) / Z4_SPLIT_WAVES, (unsigned)B),
+                                       dim3(Z4_SPLIT_WAVES * 64), 0, stream, ba,
+                                       (const int4 *)gr.d_tab_desc2, lc.first, lc.second, none);
+                split_used = true;
+            } else if (head)
+                hipLaunchKernelGGL(kc->zip4_level2_first, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64),
+                                   p->pstride * 8, stream, ba,
+                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, staged);
+            else
+                hipLaunchKernelGGL(kc->zip4_level2, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba,
+                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, none);
+            head = false;
+            HIP_TRY(hipGetLastError());
+        }
+    } else
+        for (int d = 0; d < gr.tab_nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
+            const int first = gr.tab_lvl[d], count = gr.tab_lvl[d + 1] - first;
+            hipLaunchKernelGGL(kc->zip4_level, dim3((unsigned)(count + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba, first, count);
+            HIP_TRY(hipGetLastError());
+        }
+    return IMC_OK;
+}
+
+// k_zpropagate4: the table launches, then the scan caches the hot operators in LDS and streams the rest a step ahead.
+int Launch::zip4(const Group &gr)
+{
+    BigArgs ba = blocked_args(gr);
+    if (int rc = z4_table(gr, ba)) return rc;
+    void (*scan)(BigArgs) = gr.stream_table ? (gr.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.wide_tokens ? kc->zip4w : kc->zip4);
+    if (int rc = allow_lds_budget(scan)) return rc;
+    if (int rc = mark_a()) return rc;
+    // XCD-affine grid (BigArgs::n_phases): with the two-dimensional grid every XCD's L2 sees the tables of all
+    // B parameter sets
+    dim3 scan_grid(ba.n_group_segs, (unsigned)B);
+    if (g.xcd_affine && B > 1) {
+        const imc::PhaseTable &t = gr.phases;
+        ba.n_phases = t.n_phases;
+        for (int k = 0; k < t.n_phases; ++k) { ba.ph_begin[k] = t.ph_begin[k]; ba.ph_first[k] = t.ph_first[k]; ba.ph_sets[k] = t.ph_sets[k]; }
+        scan_grid = dim3((unsigned)t.grid);
+    }
+    hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.n_hot), stream, ba);
+    note(std::string("k_zpropagate4<") + std::to_string(kc->NP / 4) + (gr.wide_tokens ? ",16" : "") + (gr.stream_table ? ",streamed>" : ">") + stream_tag(gr));
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+// k_zpropagate3 (fp64 MFMA) / k_zpropagate2 (DPP, VALU): the table is built in LDS by the scan's own workgroups.
+int Launch::zip32(const Group &gr)
+{
+    BigArgs ba = blocked_args(gr);
+    const bool v3 = kc->use3();
+    void (*scan)(BigArgs) = v3 ? kc->zip3 : kc->zip2;
+    if (int rc = allow_lds_budget(scan)) return rc;
+    size_t lds3 = kc->blocked_lds(gr.A);
+    if (direct_params) { ba.params_src = p->h_params_dev[p->slot]; lds3 = ((lds3 + 15) & ~(size_t)15) + p->pstride * 8; }
+    hipLaunchKernelGGL(scan, dim3(ba.n_group_segs, (unsigned)p->B), dim3(Z2WAVES * 64), lds3, stream, ba);
+    note(std::string(v3 ? "k_zpropagate3<" : "k_zpropagate2<") + std::to_string(kc->NP / 4) + ">" + stream_tag(gr));
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+// ---- vector kernels (kernels_zip.hpp, kernels_plain.hpp) ----
+
+int Launch::zpropagate(const Group &gr)
+{
+    const size_t lds = kc->zip_lds(gr.A);
+    if (int rc = allow_lds_budget(kc->zip)) return rc;
+    const uint32_t vpb = (uint32_t)(ZWAVES * kc->VPW);
+    dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
+    hipLaunchKernelGGL(kc->zip, grid, dim3(ZWAVES * 64), lds, stream, prop_args(p, gr));
+    note("k_zpropagate<" + std::to_string(kc->R) + "," + std::to_string(kc->G) + ">" + stream_tag(gr));
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+int Launch::propagate(const Group &gr)
+{
+    const uint32_t vpb = (uint32_t)(WPB * kc->VPW);
+    dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
+    const size_t lds = ((size_t)WPB * kc->VPW * kc->NP + (size_t)p->S * kc->NP) * 8;
+    if (lds > LDS_BUDGET) return fail(IMC_ERR_ARG, "emission table (S x N) too large for LDS");
+    if (lds > 48 * 1024)                  // large alphabets: opt in to > 64 KB of dynamic LDS
+        if (int rc = allow_lds_budget(kc->plain)) return rc;
+    hipLaunchKernelGGL(kc->plain, grid, dim3(WPB * 64), lds, stream, prop_args(p, gr));
+    note("k_propagate<" + std::to_string(kc->R) + "," + std::to_string(kc->G) + ">" + stream_tag(gr));
+    account(gr);
+    HIP_TRY(hipGetLastError());
+    return IMC_OK;
+}
+
+// ---- stitch (kernels_stitch.hpp): k_emax / k_chain per level, k_finish ----
+
+int Launch::stitch() const
+{
+    const int N = p->N, NP = kc->NP;
+    for (size_t l = 0; l + 1 < p->levels.size(); ++l) {
         const Level &in = p->levels[l], &ot = p->levels[l + 1];
         if (!in.n_segs || !ot.n_chains) continue;
         if (!kc->chain_self_emax) {   // (the single-wavefront chain kernels find the units' largest exponents themselves)
@@ -2123,15 +2080,51 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
                            ot.n_vecs, ot.d_P, ot.d_EX, (last_level && p->finish_fused) ? out : (double *)nullptr, p->n_chunks);
         HIP_TRY(hipGetLastError());
     }
-    if (p->n_chunks && !p->finish_fused && !tail_used) {
+    if (p->n_chunks && !p->finish_fused) {
         const Level &last = p->levels.back();
         hipLaunchKernelGGL(k_finish, dim3((p->n_chunks + 63) / 64, (unsigned)B), dim3(64), 0, stream,
                            p->d_final_vec, p->n_chunks, N, NP, last.n_vecs, last.d_P, last.d_EX, out);
         HIP_TRY(hipGetLastError());
     }
-    if (prof) {
-        HIP_TRY(hipEventRecord(ev.c, stream));
-        g.events.push_back(ev);
+    return IMC_OK;
+}
+
+// Enqueue one batch evaluation on `stream`: parameter upload, propagate, stitch.  Per-chunk results are written
+// to `out` ([B][n_chunks]; device memory or mapped pinned host memory).  Contains no synchronisation, so the
+// same call sequence can be captured into a hipGraph.
+int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream, &cap);
+    if (cap == hipStreamCaptureStatusNone && p->have_last && p->last_stream != stream)
+        HIP_TRY(hipStreamWaitEvent(stream, p->ev_params[p->last_slot], 0));     // the plan's previous call ran on another stream
+    Launch L{p, stream, out, allow_tail};
+    if (int rc = L.fetch_params()) return rc;
+
+    uint64_t *lp = p->lp;
+    lp[0] = p->n_segs; lp[1] = p->n_vecs; lp[2] = lp[3] = lp[4] = lp[5] = lp[6] = lp[7] = 0;
+    L.prof = g.profile && p->n_vecs;
+    if (L.prof) { HIP_TRY(hipEventCreate(&L.ev.a)); HIP_TRY(hipEventCreate(&L.ev.b)); HIP_TRY(hipEventCreate(&L.ev.c)); }
+    p->kernels.clear();
+    for (const Group &gr : p->groups) {
+        if (!gr.n_vecs) continue;
+        if (!gr.zip4)
+            if (int rc = L.mark_a()) return rc;
+        const int rc = gr.big    ? (gr.bigvec ? L.matvec_chain(gr) : L.gemm_chain(gr))
+                       : gr.zip2 ? (gr.zip4 ? L.zip4(gr) : L.zip32(gr))
+                       : gr.zip  ? L.zpropagate(gr)
+                                 : L.propagate(gr);
+        if (rc) return rc;
+    }
+    if (int rc = L.mark_a()) return rc;
+    if (L.prof) HIP_TRY(hipEventRecord(L.ev.b, stream));
+    if (L.split_used) L.note("table-split");
+    if (L.tail_used) L.note("fused-tail");
+    if (!L.tail_used)
+        if (int rc = L.stitch()) return rc;
+    if (L.prof) {
+        HIP_TRY(hipEventRecord(L.ev.c, stream));
+        g.events.push_back(L.ev);
     }
     if (cap == hipStreamCaptureStatusNone) {
         // one event per call, behind its last kernel (an event record holds the queue for ~5 us: not in front of the
@@ -2686,7 +2679,7 @@ int imc_set_device(int device)
         model_release();
         (void)hipStreamDestroy(g.stream);
         g.ready = false;
-        reset_kernel_attributes();   // the dynamic-LDS opt-in is per device
+        g.lds_opted.clear();         // the dynamic-LDS opt-in is per device
     }
     g.device = device;
     return ensure_ctx();
