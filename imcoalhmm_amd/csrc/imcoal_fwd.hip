@@ -5,18 +5,19 @@
 // Algorithm (see DESIGN.md for the derivation and the roofline accounting)
 // ---------------------------------------------------------------------
 // The forward recursion  a_t = (T' a_{t-1}) .* E[:,o_t]  is a serial chain per alignment file, so a
-// file is cut into K segments ("parallel in time").  Segment 0 propagates the single vector
-// pi .* E[:,o_0]; every later segment propagates the N unit vectors e_c, which yields the segment's
-// exact N x N transfer operator column by column.  A short second kernel stitches the operators in
-// order.  All rescaling is by exact powers of two (integer exponents are summed), so the only
-// difference from the textbook recursion is fp64 rounding order.
+// file is cut into K segments ("parallel in time").  A chunk's first segment propagates the single vector
+// pi .* E[:,o_0]; every later segment yields the segment's exact N x N transfer operator.  The stitch
+// (kernels_stitch.hpp, or the blocked scan's fused tail) applies the operators in order.  All rescaling is by
+// exact powers of two (integer exponents are summed), so the only difference from the textbook recursion is
+// fp64 rounding order.
 //
-// Two propagate kernels share that frame:
-//   k_propagate  (kernels_plain.hpp)  one step per alignment COLUMN; the R x N block of T' a lane needs
-//                lives in VGPRs for the whole launch, the vector is exchanged through LDS broadcasts.
-//   k_zpropagate (kernels_zip.hpp)    one step per TOKEN of the pair-compressed stream (zipHMM idea,
-//                pair_dict.hpp); the per-token operators are built per evaluation in each CU's LDS.
-// MFMA is deliberately not used (north_star): the matrices are tiny and fp64 MFMA has the VALU's rate.
+// Which kernels run a segment - per alignment column or per token of the pair-compressed stream (pair_dict.hpp),
+// on the VALU or on fp64 MFMA, with the operator table in LDS or in global memory - is decided per launch group
+// (Group::Kind below); the kernel families themselves are described in DESIGN.md section 5.
+//
+// Host side, in the order of this file: context and device memory (dev_alloc, DevBuf), chunks and dictionaries,
+// the kernel table, the launch plan (Group / Level / Plan own their device buffers) and its builder, one enqueue
+// function per kernel family, the model layer, the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -288,6 +289,40 @@ void dev_free(void *p)
     // and a later launch faulted at an address nobody had computed; with the ranges kept, neither was seen again.)
     g_guard.erase(it);
 }
+
+// One device buffer and its owner: allocated by dev_alloc (so guard mode applies), freed by dev_free when the owner
+// is destroyed, re-assigned or reset().  Every device pointer of Plan, Level and Group is one of these, so erasing a
+// plan releases it.  NOT used for imc_obs (its token levels alias each other, and it checks the process id before it
+// frees), DictDev (its destructor runs at exit behind the same process-id check) and g_model (a static whose buffers
+// are released explicitly): those keep raw pointers.
+template <class T>
+class DevBuf {
+    T *p_ = nullptr;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        return dev_alloc((void **)&p_, bytes);
+    }
+    void reset()
+    {
+        dev_free(p_);
+        p_ = nullptr;
+    }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
 
 }  // namespace
 
@@ -646,54 +681,24 @@ KernelChoice *choose_kernel(int N, bool prefer_gemm)
 // ---- launch plan ----------------------------------------------------------------------------------
 
 struct Group {             // one propagate launch
-    bool big = false;      // large-N GEMM-chain kernel (one workgroup per segment)
-    bool bigvec = false;   // ... every chunk is one segment: mat-vec chain kernel (k_big_vector), no operators
-    bool zip2 = false;     // register-blocked token kernel (one 16-lane row per segment)
-    std::vector<uint32_t> seg_ids, seg_out;   // big: segment ids and their level-0 vector index
-    std::vector<Z2Block> blocks;              // zip2: one entry per workgroup
-    std::vector<BigBlock> big_blocks;         // big: one entry per (segment, column slab) workgroup
-    BigBlock *d_big_blocks = nullptr;
-    uint32_t *d_seg_ids = nullptr, *d_seg_out = nullptr;
-    Z2Block *d_blocks = nullptr;
-    bool zip4 = false;                        // blocked MFMA kernel with the hybrid table: alphabet beyond LDS, n_hot operators cached
-    bool wide_tokens = false;                 // ... its token stream holds 16-bit ids
-    bool stream_table = false;                // ... nothing cached in LDS: the launch's tables are small enough to stay cache resident
-    int n_hot = 0;
-    std::vector<uint16_t> hot;
-    uint16_t *d_hot = nullptr;
-    uint16_t *d_tab_order = nullptr;          // blocked MFMA kernel: merged tokens of the alphabet by dictionary depth
-    int *d_tab_lvl = nullptr;
-    int4 *d_tab_desc = nullptr;               // hybrid table: {token, left, right, 0} per entry of the depth order
-    int4 *d_tab_desc2 = nullptr;              // ... two int4 per entry of the two-depths-per-launch schedule (k_z4_level2)
-    std::vector<std::pair<int, int>> tab2;    // ... (first entry, entries) per launch
-    // fused tail (zip3_tail): per workgroup {chunk, unit, units of the chunk}; published operators, exponents, arrival counters
-    std::vector<Z2Tail> tails;
-    Z2Tail *d_tails = nullptr;
-    double *d_tailX = nullptr;
-    int *d_tailE = nullptr, *d_tail_arrive = nullptr;
-    int tail_stride = 0;
-    int4 *d_tab_desc3 = nullptr;              // ... three int4 per token of the three-depths-per-launch schedule (k_z4_level3): {token, leaves 0-2}, {leaves 3-6}, {leaf 7}
-    std::vector<std::pair<int, int>> tab3;
-    std::vector<int> tab_lvl;                 // host copy of the depth offsets
-    int tab_nlvl = 0;
-    std::vector<std::pair<int, int>> table_runs;   // GEMM chain: (first, count) in the dictionary's depth order per k_big_table_level launch
-    imc::PhaseTable phases;                   // hybrid table: the XCD-affine grid of the scan (used when B > 1)
-    double *d_Ctab = nullptr;
-    double *d_Cpack = nullptr;                // big groups that run the mat-vec chain: packed copy of the table ([B][A][N][TS])
-    int *d_cex = nullptr;
-    // rank-one hand-off (GEMM chain only): operator segments run on the GEMM chain in rounds that end at the
-    // checkpoints (token counts); after each round k_rank1_check tests the segments still on the chain, and those
-    // that collapsed to u alpha^T finish on the mat-vec chain from that checkpoint.  The schedule is fixed per plan,
-    // the decision per segment comes from the data of the evaluation: nothing is carried from call to call.
-    bool rank1 = false;
-    int head_len = 0;                         // the planner's estimate (cost model only)
-    std::vector<int> checkpoints;
-    std::vector<BigBlock> tail_blocks;        // one entry per segment (operator tails and first segments)
-    std::vector<std::pair<uint32_t, uint32_t>> r1_segs;   // (plan-wide id, length) of the operator segments
-    BigBlock *d_tail_blocks = nullptr;
-    int *d_r1flag = nullptr, *d_r1at = nullptr;
-    double *d_r1u = nullptr, *d_r1alpha = nullptr;
-    bool zip = false;
+    // Which kernel family runs the group: fixed once, at the end of PlanBuilder::choose_segment_lengths(); everything
+    // after that point reads `kind` or one of the predicates below.  enqueue() has one case per kind.
+    enum class Kind {
+        ColumnVector,    // k_propagate: one step per alignment column
+        TokenVector,     // k_zpropagate: one step per token, operator table in LDS
+        BlockedLds,      // register-blocked scan (one 16-lane row per segment), table in LDS: k_zpropagate3 / k_zpropagate2
+        BlockedGlobal,   // ... fp64-MFMA scan on the global (hybrid or streamed) table: k_zpropagate4, alphabets beyond LDS
+        GemmChain,       // large-N GEMM chain (one workgroup per segment and column slab): k_big_propagate
+        MatVecChain,     // ... every chunk is one segment: mat-vec chain (k_big_vector), no operators
+    };
+    Kind kind = Kind::ColumnVector;
+    bool is_chain() const { return kind == Kind::GemmChain || kind == Kind::MatVecChain; }
+    bool is_blocked() const { return kind == Kind::BlockedLds || kind == Kind::BlockedGlobal; }
+    bool global_table() const { return kind == Kind::BlockedGlobal; }
+
+    // ---- what every family uses ----
+    bool tokens = false;   // the group's stream is a token level of its dictionary, not the raw columns (a raw stream can
+                           // run the blocked scan and the chains too)
     int level = -1, A = 0;
     std::shared_ptr<DictDev> dict;
     std::vector<int> chunks;
@@ -702,20 +707,65 @@ struct Group {             // one propagate launch
     double model_us = 0.0, model_tab_us = 0.0;   // the planner's estimate for this group's launches and the table's part of it (dictionary groups; compared by build_plan)
     uint64_t vsteps = 0;   // executed vector-steps per parameter set (columns or tokens)
     uint64_t stream_len = 0;
+    // operator table in global memory and its exponents: the chain families and the global-table scan
+    DevBuf<double> d_Ctab;
+    DevBuf<int> d_cex;
+
+    struct Chain {         // ---- GemmChain / MatVecChain ----
+        std::vector<uint32_t> seg_ids, seg_out;   // segment ids and their level-0 vector index
+        std::vector<BigBlock> big_blocks;         // one entry per (segment, column slab) workgroup
+        DevBuf<BigBlock> d_big_blocks;
+        std::vector<std::pair<int, int>> table_runs;   // (first, count) in the dictionary's depth order per k_big_table_level launch
+        DevBuf<double> d_Cpack;                   // groups that run the mat-vec chain: packed copy of the table ([B][A][N][TS])
+        // rank-one hand-off (GEMM chain only): operator segments run on the GEMM chain in rounds that end at the
+        // checkpoints (token counts); after each round k_rank1_check tests the segments still on the chain, and those
+        // that collapsed to u alpha^T finish on the mat-vec chain from that checkpoint.  The schedule is fixed per plan,
+        // the decision per segment comes from the data of the evaluation: nothing is carried from call to call.
+        bool rank1 = false;
+        std::vector<int> checkpoints;
+        std::vector<BigBlock> tail_blocks;        // one entry per segment (operator tails and first segments)
+        std::vector<std::pair<uint32_t, uint32_t>> r1_segs;   // (plan-wide id, length) of the operator segments
+        DevBuf<BigBlock> d_tail_blocks;
+        DevBuf<int> d_r1flag, d_r1at;
+        DevBuf<double> d_r1u, d_r1alpha;
+    } chain;
+
+    struct Blocked {       // ---- BlockedLds / BlockedGlobal ----
+        std::vector<Z2Block> blocks;              // one entry per workgroup
+        DevBuf<Z2Block> d_blocks;
+        DevBuf<uint16_t> d_tab_order;             // merged tokens of the alphabet by dictionary depth
+        DevBuf<int> d_tab_lvl;
+        std::vector<int> tab_lvl;                 // host copy of the depth offsets
+        int tab_nlvl = 0;
+        // global table: its build's descriptor lists with their launch lists (first entry, entries)
+        DevBuf<int4> d_tab_desc;                  // {token, left, right, 0} per entry of the depth order
+        DevBuf<int4> d_tab_desc2;                 // two int4 per entry of the two-depths-per-launch schedule (k_z4_level2)
+        std::vector<std::pair<int, int>> tab2;
+        DevBuf<int4> d_tab_desc3;                 // three int4 per token of the three-depths-per-launch schedule (k_z4_level3): {token, leaves 0-2}, {leaves 3-6}, {leaf 7}
+        std::vector<std::pair<int, int>> tab3;
+        bool wide_tokens = false;                 // the token stream holds 16-bit ids (set when the group is created, for every
+                                                  // group; only the global-table scan reads it)
+        bool stream_table = false;                // nothing cached in LDS: the launch's tables are small enough to stay cache resident
+        int n_hot = 0;                            // hybrid table: operators cached in LDS
+        std::vector<uint16_t> hot;
+        DevBuf<uint16_t> d_hot;
+        imc::PhaseTable phases;                   // the XCD-affine grid of the scan (used when B > 1)
+        // fused tail (zip3_tail): per workgroup {chunk, unit, units of the chunk}; published operators, exponents, arrival counters
+        std::vector<Z2Tail> tails;
+        DevBuf<Z2Tail> d_tails;
+        DevBuf<double> d_tailX;
+        DevBuf<int> d_tailE, d_tail_arrive;
+        int tail_stride = 0;
+    } blk;
 };
 
 struct Level {             // one level of the stitch hierarchy (level 0 = propagate output)
     uint32_t n_segs = 0, n_vecs = 0, n_chains = 0;
-    uint32_t *d_vec0 = nullptr;
-    uint8_t *d_first = nullptr;
-    ChainDesc *d_chains = nullptr;   // chains that produce THIS level from the previous one
-    double *d_P = nullptr;
-    int *d_EX = nullptr, *d_EMAX = nullptr;
-    void release()
-    {
-        dev_free(d_vec0); dev_free(d_first); dev_free(d_chains);
-        dev_free(d_P); dev_free(d_EX); dev_free(d_EMAX);
-    }
+    DevBuf<uint32_t> d_vec0;
+    DevBuf<uint8_t> d_first;
+    DevBuf<ChainDesc> d_chains;      // chains that produce THIS level from the previous one
+    DevBuf<double> d_P;
+    DevBuf<int> d_EX, d_EMAX;
 };
 
 struct Plan {
@@ -726,13 +776,13 @@ struct Plan {
     uint32_t n_segs = 0, n_vecs = 0;
     std::vector<Group> groups;
     size_t pstride = 0;
-    SegDesc *d_segs = nullptr;
-    VecDesc *d_vecs = nullptr;
+    DevBuf<SegDesc> d_segs;
+    DevBuf<VecDesc> d_vecs;
     std::vector<Level> levels;       // levels[0] holds the propagate output
-    int32_t *d_final_vec = nullptr;  // per chunk: vector index in the last level, -1 for an empty chunk
+    DevBuf<int32_t> d_final_vec;     // per chunk: vector index in the last level, -1 for an empty chunk
     uint64_t chain_steps = 0;        // serial depth of the stitch (sum over levels of the longest chain)
     bool finish_fused = false;       // the last chain level writes the log-likelihoods itself (no k_finish launch)
-    double *d_params = nullptr, *d_out = nullptr;
+    DevBuf<double> d_params, d_out;
     // pinned staging of the caller's parameters: two slots used alternately, each guarded by an event recorded behind
     // the call that read it, so a call only waits when the call issued two calls earlier is still running
     double *h_params[2] = {nullptr, nullptr};
@@ -757,19 +807,26 @@ struct Plan {
     uint64_t calls = 0;
     uint64_t lp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::string kernels;
-    void release()
+    Plan() = default;
+    Plan(const Plan &) = delete;
+    Plan &operator=(const Plan &) = delete;
+    // The device buffers free themselves (DevBuf members: after this body, so the pinned slots and events now go
+    // first where release() freed them last - no plan is busy or in flight when it is erased).
+    ~Plan()
     {
         if (graph) (void)hipGraphExecDestroy(graph);
-        dev_free(d_segs); dev_free(d_vecs); dev_free(d_final_vec);
-        for (auto &l : levels) l.release();
-        for (auto &gr : groups) { dev_free(gr.d_seg_ids); dev_free(gr.d_seg_out); dev_free(gr.d_blocks); dev_free(gr.d_hot); dev_free(gr.d_tab_desc); dev_free(gr.d_tab_desc2); dev_free(gr.d_tab_desc3); dev_free(gr.d_tails); dev_free(gr.d_tailX); dev_free(gr.d_tailE); dev_free(gr.d_tail_arrive); dev_free(gr.d_tab_order); dev_free(gr.d_tab_lvl); dev_free(gr.d_big_blocks); dev_free(gr.d_Ctab); dev_free(gr.d_Cpack); dev_free(gr.d_cex); dev_free(gr.d_tail_blocks); dev_free(gr.d_r1flag); dev_free(gr.d_r1at); dev_free(gr.d_r1u); dev_free(gr.d_r1alpha); }
-        dev_free(d_params); dev_free(d_out);
-        for (int k = 0; k < 2; ++k) { (void)hipHostFree(h_params[k]); if (ev_params[k]) (void)hipEventDestroy(ev_params[k]); }
-        (void)hipHostFree(h_out);
+        for (int k = 0; k < 2; ++k) {
+            if (h_params[k]) (void)hipHostFree(h_params[k]);
+            if (ev_params[k]) (void)hipEventDestroy(ev_params[k]);
+        }
+        if (h_out) (void)hipHostFree(h_out);      // (a plan that never reached upload() makes no HIP call here)
     }
 };
 
-std::list<std::unique_ptr<Plan>> g_plans;   // most recent first
+// Most recent first.  Erasing a plan from the list releases everything it holds.  The list itself is never destroyed
+// (the idiom of g_guard): a static's destructor would free device memory at process exit - and in a forked child of an
+// initialised parent, where a HIP call can hang; as before, no plan is released on either path.
+std::list<std::unique_ptr<Plan>> &g_plans = *new std::list<std::unique_ptr<Plan>>();
 constexpr size_t MAX_PLANS = 4;
 
 // Wait (g_mu held through `lk`) until no synchronous call is waiting on any plan: callers that release plans.
@@ -782,10 +839,24 @@ void wait_all_idle(std::unique_lock<std::mutex> &lk)
     });
 }
 
-void drop_plans()
+void drop_plans() { g_plans.clear(); }
+
+// Drop every plan that uses one of these chunks - plans hold raw pointers into the chunks' device buffers (g_mu held,
+// no plan busy: wait_all_idle).
+void drop_plans_using(imc_obs *const *obs, size_t n)
 {
-    for (auto &p : g_plans) p->release();
-    g_plans.clear();
+    for (auto it = g_plans.begin(); it != g_plans.end();) {
+        bool uses = false;
+        for (size_t k = 0; k < (size_t)(*it)->n_chunks; ++k)
+            for (size_t q = 0; q < n; ++q) uses |= (*it)->key[k] == obs[q]->id;
+        it = uses ? g_plans.erase(it) : std::next(it);
+    }
+}
+
+void publish_last(const Plan *p)     // what imc_last_plan() / imc_last_kernels() report: the plan just enqueued
+{
+    for (int k = 0; k < 8; ++k) g.last_plan[k] = p->lp[k];
+    g.last_kernels = p->kernels;
 }
 
 size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
@@ -878,6 +949,32 @@ static HandoffEstimate estimate_handoff(double seglen, double nseg, int B, doubl
     return best;
 }
 
+// Device allocations of one upload with a sticky error: after the first failure the later calls do nothing, and the
+// caller checks `e` once at the end.  (Host-side work between the calls - schedules, block lists - still runs after a
+// failure; only the device calls become no-ops, and the error reported is the first one.)
+struct DevUpload {
+    hipError_t e = hipSuccess;
+    template <class T> void alloc(DevBuf<T> &d, size_t bytes)             // uninitialised
+    {
+        if (e == hipSuccess) e = d.alloc(std::max<size_t>(bytes, 16));
+    }
+    template <class T> void zeroed(DevBuf<T> &d, size_t bytes)            // zero-filled (padded operator columns stay 0)
+    {
+        alloc(d, bytes);
+        if (e == hipSuccess) e = hipMemset(d.get(), 0, std::max<size_t>(bytes, 16));
+    }
+    template <class T, class V> void put(DevBuf<T> &d, const std::vector<V> &h)   // a host vector's device copy
+    {
+        static_assert(sizeof(T) == sizeof(V), "the device buffer holds the host vector's elements");
+        alloc(d, h.size() * sizeof(V));
+        if (e == hipSuccess && !h.empty()) e = hipMemcpy(d.get(), h.data(), h.size() * sizeof(V), hipMemcpyHostToDevice);
+    }
+    template <class F> void then(F f)                                     // any other step that returns a hipError_t
+    {
+        if (e == hipSuccess) e = f();
+    }
+};
+
 // Builds one launch plan in phases; every phase reads what the earlier ones left in the members.
 struct PlanBuilder {
     const imc_obs *const *chunks = nullptr;
@@ -889,7 +986,10 @@ struct PlanBuilder {
     bool wide = false, wide_ok = true;
     bool mfma() const { return kc->use3() || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
     std::unique_ptr<Plan> p;
-    bool big = false;                   // GEMM-chain / mat-vec chain kernels (global-memory operator table)
+    // What the first two phases know of a group's kind before choose_segment_lengths() fixes Group::kind; nothing
+    // after that phase reads these.
+    bool chain_tentative = false;       // the plan's kernel entry is the large-N one: every group ends as GemmChain or MatVecChain
+    std::vector<char> global_tentative; // per group: its level was chosen for the global-table scan (alphabet beyond LDS, or 16-bit tokens)
     std::vector<int> chunk_group;       // chunk -> index into p->groups
     std::vector<SegDesc> segs;          // all segments, chunk order
     std::vector<uint8_t> seg_first;
@@ -916,7 +1016,7 @@ struct PlanBuilder {
     size_t handoff_head(const Group &gr) const
     {
         double cols = 0.0, toks = 0.0;
-        for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.zip ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
+        for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
         const double span = toks > 0.0 ? cols / toks : 1.0;
         return round_up(std::max<size_t>(R1_MIN_HEAD, (size_t)(R1_HEAD_COLUMNS / span)), 16);
     }
@@ -924,7 +1024,7 @@ struct PlanBuilder {
     void assign_groups()
     {
         // ---- assign chunks to launch groups: plain, or (dictionary, level) ----
-        big = kc->R == 0;
+        const bool big = chain_tentative = kc->R == 0;
         int a_max = 0;   // largest alphabet whose operator table fits LDS for this N (no limit on the large-N path)
         if (big) a_max = imc::kMaxAlphabet;
         else
@@ -1077,20 +1177,19 @@ struct PlanBuilder {
             int gi = -1;
             for (size_t q = 0; q < p->groups.size(); ++q) {
                 Group &gr = p->groups[q];
-                if (level < 0 ? !gr.zip : (gr.zip && gr.level == level && gr.dict == o->dict)) gi = (int)q;
+                if (level < 0 ? !gr.tokens : (gr.tokens && gr.level == level && gr.dict == o->dict)) gi = (int)q;
             }
             if (gi < 0) {
                 Group gr;
-                gr.zip = level >= 0;
+                gr.tokens = level >= 0;
                 gr.level = level;
-                gr.big = big;
                 gr.A = S;
-                if (gr.zip) { gr.dict = o->dict; gr.A = o->alphabet[level]; }
+                if (gr.tokens) { gr.dict = o->dict; gr.A = o->alphabet[level]; }
                 // an alphabet beyond LDS can only have been chosen for the hybrid-table kernel
-                gr.zip4 = gr.zip && mfma_blocked && (wide || kc->blocked_lds(gr.A) > LDS_BUDGET || o->wide[level]);
-                if (gr.zip) { gr.model_us = dict_cost[o->dict.get()]; gr.model_tab_us = dict_tab[o->dict.get()]; }
-                gr.wide_tokens = gr.zip && o->wide[level];
-                p->groups.push_back(gr);
+                global_tentative.push_back(gr.tokens && mfma_blocked && (wide || kc->blocked_lds(gr.A) > LDS_BUDGET || o->wide[level]));
+                if (gr.tokens) { gr.model_us = dict_cost[o->dict.get()]; gr.model_tab_us = dict_tab[o->dict.get()]; }
+                gr.blk.wide_tokens = gr.tokens && o->wide[level];
+                p->groups.push_back(std::move(gr));
                 gi = (int)p->groups.size() - 1;
             }
             p->groups[gi].chunks.push_back(f);
@@ -1101,10 +1200,14 @@ struct PlanBuilder {
     void choose_segment_lengths()
     {
         // ---- segment length per group ----
-        for (Group &gr : p->groups) {
+        for (size_t q = 0; q < p->groups.size(); ++q) {
+            Group &gr = p->groups[q];
+            const bool global = global_tentative[q] != 0;
+            bool matvec = false;    // (chain plans) granted by the cost comparison below, revoked if a forced segment length cuts a chunk
+            bool blocked = false;   // (other plans) the register-blocked scan instead of the vector kernel
             std::vector<size_t> lens;
-            for (int f : gr.chunks) lens.push_back(gr.zip ? chunks[f]->ntok[gr.level] : chunks[f]->L);
-            if (gr.big) {
+            for (int f : gr.chunks) lens.push_back(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L);
+            if (chain_tentative) {
                 // every segment costs N^3 per step whatever the split (one workgroup = one CU's worth of LDS), so
                 // one equal-length segment per CU is both balanced and the fewest operators for the stitch
                 size_t total = 0;
@@ -1141,16 +1244,16 @@ struct PlanBuilder {
                                  gr.seglen, cost_gemm, cost_vec);
                 // (no chunk longer than a segment: there would be no operator segments anyway)
                 if (!op_mode && (g.kernel_pref == 1 || (g.kernel_pref == 0 && (cost_vec < cost_gemm || lmax <= gr.seglen)))) {
-                    gr.bigvec = true;
+                    matvec = true;
                     gr.seglen = std::max<size_t>(16, round_up(lmax, 16));
                 }
                 // (build_plan's comparison: the level estimate's table part + this, the refined estimate of the chain that was taken)
-                if (gr.zip) gr.model_us = gr.model_tab_us + (gr.bigvec ? cost_vec : cost_gemm) / 2200.0;
+                if (gr.tokens) gr.model_us = gr.model_tab_us + (matvec ? cost_vec : cost_gemm) / 2200.0;
             } else {
                 // vector kernel (one vector per lane group) ...
                 double cost_vec = 0.0;
                 size_t seg_vec;
-                if (gr.zip) {
+                if (gr.tokens) {
                     // LDS-bound: a workgroup of ZWAVES wavefronts serialises on one CU's LDS
                     const double lds_cycles = ((double)kc->R * kc->NP / 2 + kc->NP / 2.0) * 4.0 + kc->R * 6.0 + 40.0;
                     seg_vec = choose_seglen(lens, N, B, kc->VPW, (double)g.cus * ZWAVES, lds_cycles * ZWAVES, &cost_vec);   // measured: 4600 cycles per wavefront-step at N=20
@@ -1162,7 +1265,7 @@ struct PlanBuilder {
                 gr.seglen = seg_vec;
                 // ... or the register-blocked kernel (one operator per 16-lane row): fill every row of the machine
                 // once; first segments waste 1 - 1/N of their row, which the cost comparison accounts for
-                if ((kc->zip2 || (wide && gr.zip4)) && g.kernel_pref != 1 && (gr.zip4 || kc->blocked_lds(gr.A) <= LDS_BUDGET) && (gr.zip || (S == gr.A && S <= imc::kByteAlphabet))) {
+                if ((kc->zip2 || (wide && global)) && g.kernel_pref != 1 && (global || kc->blocked_lds(gr.A) <= LDS_BUDGET) && (gr.tokens || (S == gr.A && S <= imc::kByteAlphabet))) {
                     const int SL = kc->z4_slots(), WV = kc->z4_waves;   // segments / wavefronts per workgroup
                     size_t total = 0;
                     for (size_t L : lens) total += L;
@@ -1170,7 +1273,7 @@ struct PlanBuilder {
                     // CU (four wavefronts per SIMD), i.e. the machine has twice the rows, each step taking ~1.85x as long
                     // (measured at 10 states, 100 x 1e6 columns: 500 workgroups of 44-token segments 102 us, 200 workgroups
                     // of 104-token segments 113 us).
-                    const bool two_per_cu = gr.zip4 && kc->use3() && kc->NP <= 12 &&
+                    const bool two_per_cu = global && kc->use3() && kc->NP <= 12 &&
                                             z4_streamed((double)B * (gr.A + 1) * kc->tok_doubles * 8.0, B);
                     const double rows = (double)g.cus * SL * (two_per_cu ? 2.0 : 1.0);
                     const double rb = kc->NP / 4.0;
@@ -1236,7 +1339,7 @@ struct PlanBuilder {
                         // (table: the VALU form builds token by token; the MFMA form one dictionary depth per pass,
                         // ~10 depths; with the hybrid table a workgroup only copies its hot set from L2)
                         const double table = !mfma() ? (double)(gr.A - S) * (400.0 + (double)kc->NP * kc->NP * kc->NP / 64.0)
-                                             : gr.zip4 ? 9000.0 : 2600.0 * std::min(12.0, (double)(gr.A - S));
+                                             : global ? 9000.0 : 2600.0 * std::min(12.0, (double)(gr.A - S));
                         const double fixed = table + 5.0 * (WV / 4.0) * step_cycles;
                         // A segment length that is not a multiple of 16 ends in a MASKED block (the pipeline is re-primed per
                         // run of it: ~3.5 us; measured at 10 states, 100 x 1e6 columns: 48-token segments 101.9 us, 44-token
@@ -1252,52 +1355,55 @@ struct PlanBuilder {
                     if (std::getenv("IMC_DEBUG"))
                         std::fprintf(stderr, "[imc] plan: vector kernel seg %zu cost %.3g cycles; blocked kernel seg %zu slots %.0f cost %.3g cycles\n",
                                      seg_vec, cost_vec, seg_blk, slots, cost_blk);
-                    const bool vec_fits = !gr.zip || kc->zip_lds(gr.A) <= LDS_BUDGET;   // the table may only fit the blocked kernel
-                    if (g.kernel_pref == 2 || cost_blk < cost_vec || !vec_fits || gr.zip4) { gr.zip2 = true; gr.seglen = seg_blk; }
+                    const bool vec_fits = !gr.tokens || kc->zip_lds(gr.A) <= LDS_BUDGET;   // the table may only fit the blocked kernel
+                    if (g.kernel_pref == 2 || cost_blk < cost_vec || !vec_fits || global) { blocked = true; gr.seglen = seg_blk; }
                 }
-                if (gr.zip && !gr.zip2) gr.model_us = gr.model_tab_us + cost_vec / 2200.0;   // (build_plan's comparison)
+                if (gr.tokens && !blocked) gr.model_us = gr.model_tab_us + cost_vec / 2200.0;   // (build_plan's comparison)
             }
             if (g.seg_override) gr.seglen = round_up(std::max<size_t>(g.seg_override, 16), 16);   // tests: force stitching
-            if (gr.bigvec)
-                for (size_t L : lens) gr.bigvec = gr.bigvec && L <= gr.seglen && !op_mode;
+            if (matvec)
+                for (size_t L : lens) matvec = matvec && L <= gr.seglen && !op_mode;
             // rank-one hand-off: worth a test once segments are much longer than the HMM's memory (tens of thousands
             // of columns); a quarter of the segment on the GEMM chain, then the certified test
-            if (gr.big && !gr.bigvec && g.rank1_handoff && gr.seglen >= R1_MIN_SEGLEN) {
+            if (chain_tentative && !matvec && g.rank1_handoff && gr.seglen >= R1_MIN_SEGLEN) {
                 // head: ~R1_HEAD_COLUMNS alignment columns on the GEMM chain (the HMM's memory is a property of the
                 // model, not of the segmentation).  The tails then cost a mat-vec per step, so MORE, shorter
                 // segments pay: m times the segments = m rounds of heads, tails 1/m as long.  Pick m by the model;
                 // if the test fails at run time the GEMM chain does the same total work as with m = 1.
                 double cols = 0.0, toks = 0.0;
-                for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.zip ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
+                for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
                 const double span = toks > 0.0 ? cols / toks : 1.0;
                 const size_t head = handoff_head(gr);
                 const double nseg = std::max(1.0, toks / (double)gr.seglen);
                 if (g.seg_override) {                 // tests: one checkpoint at a quarter of the forced segment length
                     if (gr.seglen >= 4 * R1_MIN_HEAD) {
-                        gr.rank1 = true;
-                        gr.head_len = (int)round_up(gr.seglen / 4, 16);
-                        gr.checkpoints.assign(1, gr.head_len);
+                        gr.chain.rank1 = true;
+                        gr.chain.checkpoints.assign(1, (int)round_up(gr.seglen / 4, 16));
                     }
                 } else {
                     const int best_m = estimate_handoff((double)gr.seglen, nseg, B, (double)head, kc->NP, kc->big_nslab, gr.A, g.cus).m;
                     if (best_m) {
-                        gr.rank1 = true;
-                        gr.head_len = (int)head;
+                        gr.chain.rank1 = true;
                         gr.seglen = std::max<size_t>(16, round_up(gr.seglen / best_m, 16));
                         // checkpoints: from ~8k alignment columns, each ~1.125x the previous (multiples of 16 tokens)
                         // up to ~100k columns - where the operators of the measured models collapse; a failing check
                         // is a quick reject and costs two near-empty launches - then 1.5x, while at least an eighth
                         // of the segment would still be left for the mat-vec chain
                         size_t c = round_up(std::max<size_t>(64, (size_t)(R1_HEAD_MIN_COLUMNS / span)), 16);
-                        while ((int)gr.checkpoints.size() < R1_MAX_ROUNDS && c + gr.seglen / 8 < gr.seglen) {
-                            gr.checkpoints.push_back((int)c);
+                        while ((int)gr.chain.checkpoints.size() < R1_MAX_ROUNDS && c + gr.seglen / 8 < gr.seglen) {
+                            gr.chain.checkpoints.push_back((int)c);
                             const size_t step = (double)c * span < R1_DENSE_COLUMNS ? c / 8 : c / 2;
                             c = round_up(c + std::max<size_t>(16, step), 16);
                         }
-                        if (gr.checkpoints.empty()) gr.rank1 = false;
+                        if (gr.chain.checkpoints.empty()) gr.chain.rank1 = false;
                     }
                 }
             }
+            // the one statement of what the group is (a global-table level is always taken by the blocked scan)
+            gr.kind = chain_tentative ? (matvec ? Group::Kind::MatVecChain : Group::Kind::GemmChain)
+                      : blocked       ? (global ? Group::Kind::BlockedGlobal : Group::Kind::BlockedLds)
+                      : gr.tokens     ? Group::Kind::TokenVector
+                                      : Group::Kind::ColumnVector;
         }
     }
 
@@ -1308,14 +1414,14 @@ struct PlanBuilder {
         for (int f = 0; f < n_chunks; ++f) {
             chunk_seg[f] = (uint32_t)segs.size();
             const Group &gr = p->groups[chunk_group[f]];
-            const size_t L = gr.zip ? chunks[f]->ntok[gr.level] : chunks[f]->L;
-            const uint8_t *base = gr.zip ? chunks[f]->d_tok[gr.level] : chunks[f]->d_sym;
+            const size_t L = gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L;
+            const uint8_t *base = gr.tokens ? chunks[f]->d_tok[gr.level] : chunks[f]->d_sym;
             if (!L) continue;
             const size_t K0 = (L + gr.seglen - 1) / gr.seglen;
-            const size_t sl = round_up((L + K0 - 1) / K0, gr.zip2 ? Z2GRAN : 16);   // equalised; a multiple of 16 (16-byte aligned
+            const size_t sl = round_up((L + K0 - 1) / K0, gr.is_blocked() ? Z2GRAN : 16);   // equalised; a multiple of 16 (16-byte aligned
                                                                                    // loads) except for the blocked kernels
             for (size_t off = 0, k = 0; off < L; off += sl, ++k) {
-                const bool wide = gr.zip ? chunks[f]->wide[gr.level] : chunks[f]->wide_raw;
+                const bool wide = gr.tokens ? chunks[f]->wide[gr.level] : chunks[f]->wide_raw;
                 const bool fst = k == 0 && !op_mode;   // operator mode: the chunk's own first segment is an operator too
                 segs.push_back(SegDesc{base + off * (wide ? 2 : 1), (uint32_t)std::min(sl, L - off),
                                        (fst ? SEG_FIRST : 0u) | (wide ? SEG_WIDE : 0u)});
@@ -1333,7 +1439,7 @@ struct PlanBuilder {
         chunk_units.assign(n_chunks, {});   // per chunk: (seg0, nsegs)
         for (int f = 0; f < n_chunks; ++f) {
             const Group &gr = p->groups[chunk_group[f]];
-            const uint32_t step = gr.zip2 ? (uint32_t)kc->z4_slots() : 1u;
+            const uint32_t step = gr.is_blocked() ? (uint32_t)kc->z4_slots() : 1u;
             for (uint32_t sid = chunk_seg[f]; sid < chunk_seg[f + 1]; sid += step)
                 chunk_units[f].push_back({sid, std::min(step, chunk_seg[f + 1] - sid)});
         }
@@ -1344,7 +1450,7 @@ struct PlanBuilder {
         for (Group &gr : p->groups) {
             gr.vec_begin = (uint32_t)vecs.size();
             for (int f : gr.chunks) {
-                gr.stream_len += gr.zip ? chunks[f]->ntok[gr.level] : chunks[f]->L;
+                gr.stream_len += gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L;
                 for (size_t u = 0; u < chunk_units[f].size(); ++u) {
                     const uint32_t sid = chunk_units[f][u].first, ns = chunk_units[f][u].second;
                     const uint32_t uid = chunk_unit[f] + (uint32_t)u;
@@ -1353,27 +1459,28 @@ struct PlanBuilder {
                     unit_vec0[uid] = (uint32_t)vecs.size();
                     const int nv = fst ? 1 : N;
                     for (int c = 0; c < nv; ++c) vecs.push_back(VecDesc{sid, (uint32_t)c});
-                    if (gr.big) { gr.seg_ids.push_back(sid); gr.seg_out.push_back(unit_vec0[uid]); }
-                    if (gr.zip2) {
+                    if (gr.is_chain()) { gr.chain.seg_ids.push_back(sid); gr.chain.seg_out.push_back(unit_vec0[uid]); }
+                    if (gr.is_blocked()) {
+                        std::vector<Z2Block> &blocks = gr.blk.blocks;
                         // A chunk that is ONE segment needs no fold: up to 32 consecutive such chunks share a workgroup, each
                         // in a slot of its own (Z2Block::first == 2).  One workgroup per chunk left 31 of 32 rows idle when
                         // the chunks are short (10000 chunks of 1e4 columns, 20 states: 39 rounds of workgroups, 1.97 ms).
                         const bool whole = mfma() && fst && ns == 1 && chunk_units[f].size() == 1;
-                        if (whole && !gr.blocks.empty() && gr.blocks.back().first == 2 && gr.blocks.back().n < (uint32_t)kc->z4_slots() &&
-                            gr.blocks.back().seg0 + gr.blocks.back().n == sid && gr.blocks.back().out_vec0 + gr.blocks.back().n == unit_vec0[uid])
-                            ++gr.blocks.back().n;
+                        if (whole && !blocks.empty() && blocks.back().first == 2 && blocks.back().n < (uint32_t)kc->z4_slots() &&
+                            blocks.back().seg0 + blocks.back().n == sid && blocks.back().out_vec0 + blocks.back().n == unit_vec0[uid])
+                            ++blocks.back().n;
                         else
-                            gr.blocks.push_back(Z2Block{sid, ns, unit_vec0[uid], whole ? 2u : fst ? 1u : 0u});
+                            blocks.push_back(Z2Block{sid, ns, unit_vec0[uid], whole ? 2u : fst ? 1u : 0u});
                     }
                     for (uint32_t q2 = 0; q2 < ns; ++q2)
-                        gr.vsteps += (uint64_t)((seg_first[sid + q2] && !gr.zip2) ? 1 : N) * segs[sid + q2].len;
+                        gr.vsteps += (uint64_t)((seg_first[sid + q2] && !gr.is_blocked()) ? 1 : N) * segs[sid + q2].len;
                 }
             }
             gr.n_vecs = (uint32_t)vecs.size() - gr.vec_begin;
         }
         // fused tail: one blocked-MFMA group holds every chunk, no chunk is empty or longer than a workgroup has slots
-        if (p->groups.size() == 1 && p->groups[0].zip2 && mfma() && !op_mode && n_chunks > 0) {
-            Group &gr = p->groups[0];
+        if (p->groups.size() == 1 && p->groups[0].is_blocked() && mfma() && !op_mode && n_chunks > 0) {
+            Group::Blocked &bl = p->groups[0].blk;
             bool ok = true;
             size_t most = 0;
             for (int f = 0; f < n_chunks; ++f) {
@@ -1381,13 +1488,13 @@ struct PlanBuilder {
                 most = std::max(most, chunk_units[f].size());
             }
             if (ok) {
-                for (int f : gr.chunks)
+                for (int f : p->groups[0].chunks)
                     for (size_t u = 0; u < chunk_units[f].size(); ++u)
-                        gr.tails.push_back(Z2Tail{(uint32_t)f, (uint32_t)u, (uint32_t)chunk_units[f].size(), 0u});
-                gr.tail_stride = (int)most;
-                if (gr.tails.size() != gr.blocks.size()) gr.tails.clear();      // packed blocks: several chunks share a workgroup
+                        bl.tails.push_back(Z2Tail{(uint32_t)f, (uint32_t)u, (uint32_t)chunk_units[f].size(), 0u});
+                bl.tail_stride = (int)most;
+                if (bl.tails.size() != bl.blocks.size()) bl.tails.clear();      // packed blocks: several chunks share a workgroup
                 else
-                    for (Z2Block &bk : gr.blocks)                               // (a packed block of ONE chunk is an ordinary first block,
+                    for (Z2Block &bk : bl.blocks)                               // (a packed block of ONE chunk is an ordinary first block,
                         if (bk.first == 2) bk.first = 1;                        //  and the fused tail writes that chunk's result)
             }
         }
@@ -1465,118 +1572,106 @@ struct PlanBuilder {
             for (auto it = g_plans.begin(); it != g_plans.end(); ++it)
                 if (!(*it)->busy) victim = it;
             if (victim == g_plans.end()) break;
-            (*victim)->release();
             g_plans.erase(victim);
         }
 
         Plan *q = p.get();
-        auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
-            hipError_t e = dev_alloc(d, std::max<size_t>(bytes, 16));
-            if (e != hipSuccess) return e;
-            if (bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-            return e;
-        };
-        auto zalloc = [&](void **d, size_t bytes) -> hipError_t {
-            hipError_t e = dev_alloc(d, std::max<size_t>(bytes, 16));
-            if (e == hipSuccess) e = hipMemset(*d, 0, std::max<size_t>(bytes, 16));   // padded operator columns stay 0
-            return e;
-        };
-        hipError_t e = hipSuccess;
-        if (e == hipSuccess) e = up((void **)&q->d_segs, segs.data(), segs.size() * sizeof(SegDesc));
-        if (e == hipSuccess) e = up((void **)&q->d_vecs, vecs.data(), vecs.size() * sizeof(VecDesc));
-        if (e == hipSuccess) e = up((void **)&q->d_final_vec, final_vec.data(), final_vec.size() * 4);
+        DevUpload u;
+        u.put(q->d_segs, segs);
+        u.put(q->d_vecs, vecs);
+        u.put(q->d_final_vec, final_vec);
         q->levels.resize(hl.size());
-        for (size_t l = 0; l < hl.size() && e == hipSuccess; ++l) {
+        for (size_t l = 0; l < hl.size(); ++l) {
             Level &lv = q->levels[l];
             lv.n_segs = (uint32_t)hl[l].vec0.size();
             lv.n_vecs = hl[l].n_vecs;
             lv.n_chains = (uint32_t)hl[l].chains.size();
             const size_t nv = std::max<size_t>(lv.n_vecs, 1), ns = std::max<size_t>(lv.n_segs, 1);
-            e = up((void **)&lv.d_vec0, hl[l].vec0.data(), hl[l].vec0.size() * 4);
-            if (e == hipSuccess) e = up((void **)&lv.d_first, hl[l].first.data(), hl[l].first.size());
-            if (e == hipSuccess) e = up((void **)&lv.d_chains, hl[l].chains.data(), hl[l].chains.size() * sizeof(ChainDesc));
-            if (e == hipSuccess) e = zalloc((void **)&lv.d_P, (size_t)B * nv * kc->NP * 8);
-            if (e == hipSuccess) e = zalloc((void **)&lv.d_EX, (size_t)B * nv * 4);
-            if (e == hipSuccess) e = zalloc((void **)&lv.d_EMAX, (size_t)B * ns * 4);
+            u.put(lv.d_vec0, hl[l].vec0);
+            u.put(lv.d_first, hl[l].first);
+            u.put(lv.d_chains, hl[l].chains);
+            u.zeroed(lv.d_P, (size_t)B * nv * kc->NP * 8);
+            u.zeroed(lv.d_EX, (size_t)B * nv * 4);
+            u.zeroed(lv.d_EMAX, (size_t)B * ns * 4);
         }
         for (Group &gr : q->groups) {
-            if (gr.zip2 && e == hipSuccess) e = up((void **)&gr.d_blocks, gr.blocks.data(), gr.blocks.size() * sizeof(Z2Block));
-            if (!gr.tails.empty() && e == hipSuccess) {
-                const size_t slots = (size_t)B * n_chunks * gr.tail_stride;
-                e = up((void **)&gr.d_tails, gr.tails.data(), gr.tails.size() * sizeof(Z2Tail));
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_tailX, slots * kc->tok_doubles * 8);
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_tailE, slots * 128);
-                if (e == hipSuccess) e = zalloc((void **)&gr.d_tail_arrive, (size_t)B * n_chunks * 4);
+            Group::Blocked &bl = gr.blk;
+            Group::Chain &ch = gr.chain;
+            if (gr.is_blocked()) u.put(bl.d_blocks, bl.blocks);
+            if (!bl.tails.empty()) {
+                const size_t slots = (size_t)B * n_chunks * bl.tail_stride;
+                u.put(bl.d_tails, bl.tails);
+                u.alloc(bl.d_tailX, slots * kc->tok_doubles * 8);
+                u.alloc(bl.d_tailE, slots * 128);
+                u.zeroed(bl.d_tail_arrive, (size_t)B * n_chunks * 4);
             }
-            if (gr.zip4 && e == hipSuccess) {
+            if (gr.global_table()) {
                 // hot set: the most frequent tokens of this group's chunks, as many as LDS holds beside the identity
                 std::vector<uint64_t> cnt((size_t)gr.A, 0);
                 for (int f : gr.chunks)
                     for (size_t z = 0; z < chunks[f]->tok_count[gr.level].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[gr.level][z];
                 const std::vector<uint16_t> ids = imc::hot_order(cnt);
                 const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
-                gr.stream_table = wide || z4_streamed(tables, B);
-                gr.n_hot = gr.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
-                gr.hot.assign(ids.begin(), ids.begin() + gr.n_hot);
-                gr.phases = imc::xcd_phases(B, (int)gr.blocks.size());
-                e = up((void **)&gr.d_hot, gr.hot.data(), gr.hot.size() * sizeof(uint16_t));
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_Ctab, (size_t)B * (gr.A + 1) * kc->tok_doubles * 8);
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_cex, (size_t)B * (gr.A + 1) * 4 + 16);
+                bl.stream_table = wide || z4_streamed(tables, B);
+                bl.n_hot = bl.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
+                bl.hot.assign(ids.begin(), ids.begin() + bl.n_hot);
+                bl.phases = imc::xcd_phases(B, (int)bl.blocks.size());
+                u.put(bl.d_hot, bl.hot);
+                u.alloc(gr.d_Ctab, (size_t)B * (gr.A + 1) * kc->tok_doubles * 8);
+                u.alloc(gr.d_cex, (size_t)B * (gr.A + 1) * 4 + 16);
             }
-            if (gr.zip2 && gr.zip && e == hipSuccess) {
+            if (gr.is_blocked() && gr.tokens) {
                 // merged tokens of this level's alphabet (ids S .. A-1) grouped by dictionary depth, for the table build
                 const DictDev &dd = *gr.dict;
                 const imc::DepthOrder o = imc::depth_order_below(dd.order, dd.depth, gr.A);
-                gr.tab_nlvl = o.nlvl;
-                gr.tab_lvl = o.lvl;
-                e = up((void **)&gr.d_tab_order, o.order.data(), o.order.size() * sizeof(uint16_t));
-                if (e == hipSuccess) e = up((void **)&gr.d_tab_lvl, o.lvl.data(), o.lvl.size() * sizeof(int));
-                if (e == hipSuccess && gr.zip4) {
+                bl.tab_nlvl = o.nlvl;
+                bl.tab_lvl = o.lvl;
+                u.put(bl.d_tab_order, o.order);
+                u.put(bl.d_tab_lvl, o.lvl);
+                if (gr.global_table()) {
                     const std::vector<imc::Desc4> desc = imc::level_descriptors(dd.dict, o);
                     const imc::TableSchedule s2 = imc::pairs_schedule(dd.dict, dd.depth, o, S);
                     const imc::TableSchedule s3 = imc::triples_schedule(dd.dict, dd.depth, o, S, gr.A);
-                    gr.tab2 = s2.launches;
-                    gr.tab3 = s3.launches;
-                    e = up((void **)&gr.d_tab_desc, desc.data(), desc.size() * sizeof(int4));
-                    if (e == hipSuccess && !s2.desc.empty()) e = up((void **)&gr.d_tab_desc2, s2.desc.data(), s2.desc.size() * sizeof(int4));
-                    if (e == hipSuccess && !s3.desc.empty()) e = up((void **)&gr.d_tab_desc3, s3.desc.data(), s3.desc.size() * sizeof(int4));
+                    bl.tab2 = s2.launches;
+                    bl.tab3 = s3.launches;
+                    u.put(bl.d_tab_desc, desc);
+                    if (!s2.desc.empty()) u.put(bl.d_tab_desc2, s2.desc);
+                    if (!s3.desc.empty()) u.put(bl.d_tab_desc3, s3.desc);
                 }
             }
-            if (!gr.big || e != hipSuccess) continue;
+            if (!gr.is_chain()) continue;
             const size_t np2 = (size_t)kc->NP * kc->NP;
-            if (gr.zip) gr.table_runs = imc::depth_runs_below(gr.dict->order, gr.dict->depth, gr.A);
-            gr.big_blocks = imc::deal_slabs<BigBlock>(gr.seg_ids, gr.seg_out, seg_first, kc->big_nslab);
-            e = up((void **)&gr.d_big_blocks, gr.big_blocks.data(), gr.big_blocks.size() * sizeof(BigBlock));
-            if (e == hipSuccess) e = dev_alloc((void **)&gr.d_Ctab, (size_t)B * gr.A * np2 * 8);
-            if (e == hipSuccess && (gr.bigvec || gr.rank1) && N < kc->NP && g.pack_table)   // the mat-vec chain reads a packed copy
-                e = dev_alloc((void **)&gr.d_Cpack, (size_t)B * gr.A * N * (size_t)(N + (N & 1)) * 8);
-            if (e == hipSuccess) e = dev_alloc((void **)&gr.d_cex, (size_t)B * gr.A * 4 + 16);
-            if (gr.rank1) {
-                gr.tail_blocks = imc::tail_list<BigBlock>(gr.seg_ids, gr.seg_out);
-                for (uint32_t id : gr.seg_ids)
-                    if (!seg_first[id]) gr.r1_segs.push_back({id, segs[id].len});
+            if (gr.tokens) ch.table_runs = imc::depth_runs_below(gr.dict->order, gr.dict->depth, gr.A);
+            ch.big_blocks = imc::deal_slabs<BigBlock>(ch.seg_ids, ch.seg_out, seg_first, kc->big_nslab);
+            u.put(ch.d_big_blocks, ch.big_blocks);
+            u.alloc(gr.d_Ctab, (size_t)B * gr.A * np2 * 8);
+            if ((gr.kind == Group::Kind::MatVecChain || ch.rank1) && N < kc->NP && g.pack_table)   // the mat-vec chain reads a packed copy
+                u.alloc(ch.d_Cpack, (size_t)B * gr.A * N * (size_t)(N + (N & 1)) * 8);
+            u.alloc(gr.d_cex, (size_t)B * gr.A * 4 + 16);
+            if (ch.rank1) {
+                ch.tail_blocks = imc::tail_list<BigBlock>(ch.seg_ids, ch.seg_out);
+                for (uint32_t id : ch.seg_ids)
+                    if (!seg_first[id]) ch.r1_segs.push_back({id, segs[id].len});
                 const size_t nrec = (size_t)B * segs.size();
-                if (e == hipSuccess) e = up((void **)&gr.d_tail_blocks, gr.tail_blocks.data(), gr.tail_blocks.size() * sizeof(BigBlock));
-                if (e == hipSuccess) e = zalloc((void **)&gr.d_r1flag, nrec * 4);
-                if (e == hipSuccess) e = zalloc((void **)&gr.d_r1at, nrec * 4);
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_r1u, std::max<size_t>(nrec * kc->NP * 8, 16));
-                if (e == hipSuccess) e = dev_alloc((void **)&gr.d_r1alpha, std::max<size_t>(nrec * kc->NP * 8, 16));
+                u.put(ch.d_tail_blocks, ch.tail_blocks);
+                u.zeroed(ch.d_r1flag, nrec * 4);
+                u.zeroed(ch.d_r1at, nrec * 4);
+                u.alloc(ch.d_r1u, nrec * kc->NP * 8);
+                u.alloc(ch.d_r1alpha, nrec * kc->NP * 8);
             }
         }
-        if (e == hipSuccess) e = dev_alloc((void **)&q->d_params, (size_t)B * q->pstride * 8);
-        if (e == hipSuccess) e = dev_alloc((void **)&q->d_out, (size_t)B * std::max(n_chunks, 1) * 8);
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            e = hipHostMalloc((void **)&q->h_params[k], (size_t)B * q->pstride * 8, hipHostMallocMapped);
-            if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&q->h_params_dev[k], q->h_params[k], 0);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&q->ev_params[k], hipEventDisableTiming);
+        u.alloc(q->d_params, (size_t)B * q->pstride * 8);
+        u.alloc(q->d_out, (size_t)B * std::max(n_chunks, 1) * 8);
+        for (int k = 0; k < 2; ++k) {
+            u.then([&] { return hipHostMalloc((void **)&q->h_params[k], (size_t)B * q->pstride * 8, hipHostMallocMapped); });
+            u.then([&] { return hipHostGetDevicePointer((void **)&q->h_params_dev[k], q->h_params[k], 0); });
+            u.then([&] { return hipEventCreateWithFlags(&q->ev_params[k], hipEventDisableTiming); });
         }
-        if (e == hipSuccess) e = hipHostMalloc((void **)&q->h_out, (size_t)B * std::max(n_chunks, 1) * 8, hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&q->h_out_dev, q->h_out, 0);
-        if (e != hipSuccess) {
-            q->release();
-            return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
-                        std::string("plan allocation: ") + hipGetErrorString(e));
-        }
+        u.then([&] { return hipHostMalloc((void **)&q->h_out, (size_t)B * std::max(n_chunks, 1) * 8, hipHostMallocMapped); });
+        u.then([&] { return hipHostGetDevicePointer((void **)&q->h_out_dev, q->h_out, 0); });
+        if (u.e != hipSuccess)                           // (the half-built plan is released with this builder)
+            return fail(u.e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
+                        std::string("plan allocation: ") + hipGetErrorString(u.e));
         g_plans.push_front(std::move(p));
         *out = q;
         return IMC_OK;
@@ -1660,12 +1755,12 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
         for (const Group &gr : wb.p->groups) {
             bool cols = false;
             for (int f : gr.chunks) cols = cols || chunks[f]->L > 0;
-            if (gr.zip4) { any = true; us_wide += gr.model_us; }
+            if (gr.global_table()) { any = true; us_wide += gr.model_us; }
             else if (cols && kc->R == 0) all = false;
         }
         bool base_matvec = false, base_other = false;
         for (const Group &gr : pb.p->groups)
-            if (gr.zip) { us_base += gr.model_us; (gr.bigvec ? base_matvec : base_other) = true; }
+            if (gr.tokens) { us_base += gr.model_us; (gr.kind == Group::Kind::MatVecChain ? base_matvec : base_other) = true; }
         base_matvec = base_matvec && !base_other;
         if (std::getenv("IMC_DEBUG"))
             std::fprintf(stderr, "[imc] plan: blocked scan at %d states %s, model %.1f us; present kernels %.1f us%s\n", N,
@@ -1750,7 +1845,7 @@ struct Launch {
     void account(const Group &gr) const
     {
         uint64_t *lp = p->lp;
-        if (gr.zip) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
+        if (gr.tokens) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
         else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
     }
     int fetch_params();
@@ -1766,7 +1861,7 @@ struct Launch {
     int stitch() const;
 };
 
-const char *stream_tag(const Group &gr) { return gr.zip ? "[tokens]" : "[columns]"; }
+const char *stream_tag(const Group &gr) { return gr.tokens ? "[tokens]" : "[columns]"; }
 
 // Opt a kernel in to LDS_BUDGET bytes of dynamic LDS: one hipFuncSetAttribute per function and device (g.lds_opted).
 template <class Fn>
@@ -1792,22 +1887,22 @@ int Launch::fetch_params()
     for (const Group &gr : p->groups)
         if (gr.n_vecs) { ++active; only = &gr; }
     const size_t head_lds = p->pstride * 8;
-    fuse_head = g.fuse_head && active == 1 && only->zip4 && g.table_pairs && only->d_tab_desc2 && !only->tab2.empty() &&
+    fuse_head = g.fuse_head && active == 1 && only->global_table() && g.table_pairs && only->blk.d_tab_desc2 && !only->blk.tab2.empty() &&
                 kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
     // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
     // columns): each of its few workgroups fetches the parameter set itself
-    direct_params = g.fuse_head && active == 1 && only->zip2 && !only->zip4 && kc->use3() && pbytes <= STAGE_KERNEL_MAX_BYTES &&
-                    only->blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
+    direct_params = g.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3() && pbytes <= STAGE_KERNEL_MAX_BYTES &&
+                    only->blk.blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
                     ((kc->blocked_lds(only->A) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
     if (fuse_head || direct_params) {
         // (nothing to enqueue here)
     } else if (pbytes <= STAGE_KERNEL_MAX_BYTES) {
         const unsigned n2 = (unsigned)(pbytes / 16);
         hipLaunchKernelGGL(k_stage_params, dim3((n2 + 255) / 256), dim3(256), 0, stream,
-                           reinterpret_cast<const double2 *>(p->h_params_dev[p->slot]), reinterpret_cast<double2 *>(p->d_params), n2);
+                           reinterpret_cast<const double2 *>(p->h_params_dev[p->slot]), reinterpret_cast<double2 *>(p->d_params.get()), n2);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemcpyAsync(p->d_params, p->h_params[p->slot], pbytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(p->d_params.get(), p->h_params[p->slot], pbytes, hipMemcpyHostToDevice, stream));
     }
     return IMC_OK;
 }
@@ -1815,10 +1910,10 @@ int Launch::fetch_params()
 PropArgs prop_args(const Plan *p, const Group &gr)
 {
     PropArgs a;
-    a.segs = p->d_segs; a.vecs = p->d_vecs + gr.vec_begin; a.n_vecs = gr.n_vecs; a.vec_base = gr.vec_begin;
+    a.segs = p->d_segs.get(); a.vecs = p->d_vecs.get() + gr.vec_begin; a.n_vecs = gr.n_vecs; a.vec_base = gr.vec_begin;
     a.n_vecs_total = p->n_vecs; a.N = p->N; a.S = p->S;
-    a.params = p->d_params; a.pstride = p->pstride; a.P = p->levels[0].d_P; a.EX = p->levels[0].d_EX;
-    a.A = gr.A; a.tok_left = gr.zip ? gr.dict->d_left : nullptr; a.tok_right = gr.zip ? gr.dict->d_right : nullptr;
+    a.params = p->d_params.get(); a.pstride = p->pstride; a.P = p->levels[0].d_P.get(); a.EX = p->levels[0].d_EX.get();
+    a.A = gr.A; a.tok_left = gr.tokens ? gr.dict->d_left : nullptr; a.tok_right = gr.tokens ? gr.dict->d_right : nullptr;
     return a;
 }
 
@@ -1827,12 +1922,12 @@ PropArgs prop_args(const Plan *p, const Group &gr)
 BigArgs common_args(const Plan *p, const Group &gr)
 {
     BigArgs ba{};
-    ba.segs = p->d_segs;
+    ba.segs = p->d_segs.get();
     ba.n_vecs_total = p->n_vecs; ba.n_segs = p->n_segs; ba.n_chunks = p->n_chunks;
-    ba.N = p->N; ba.S = p->S; ba.A = gr.A; ba.params = p->d_params; ba.pstride = p->pstride; ba.PP = p->kc->NP;
-    ba.tok_left = gr.zip ? gr.dict->d_left : nullptr; ba.tok_right = gr.zip ? gr.dict->d_right : nullptr;
-    ba.Ctab = gr.d_Ctab; ba.cex = gr.d_cex;
-    ba.P = p->levels[0].d_P; ba.EX = p->levels[0].d_EX;
+    ba.N = p->N; ba.S = p->S; ba.A = gr.A; ba.params = p->d_params.get(); ba.pstride = p->pstride; ba.PP = p->kc->NP;
+    ba.tok_left = gr.tokens ? gr.dict->d_left : nullptr; ba.tok_right = gr.tokens ? gr.dict->d_right : nullptr;
+    ba.Ctab = gr.d_Ctab.get(); ba.cex = gr.d_cex.get();
+    ba.P = p->levels[0].d_P.get(); ba.EX = p->levels[0].d_EX.get();
     ba.t_to = INT_MAX;
     return ba;
 }
@@ -1842,21 +1937,20 @@ BigArgs common_args(const Plan *p, const Group &gr)
 BigArgs big_args(const Plan *p, const Group &gr)
 {
     BigArgs ba = common_args(p, gr);
-    ba.seg_ids = gr.d_seg_ids; ba.seg_vec0 = gr.d_seg_out;
-    ba.n_group_segs = (uint32_t)gr.seg_ids.size();
-    ba.Cpack = gr.d_Cpack; ba.TS = p->N + (p->N & 1);
-    ba.phase = gr.rank1 ? 1 : 0; ba.t_to = gr.rank1 ? gr.checkpoints[0] : INT_MAX;
-    ba.r1flag = gr.d_r1flag; ba.r1at = gr.d_r1at; ba.r1u = gr.d_r1u; ba.r1alpha = gr.d_r1alpha;
+    ba.n_group_segs = (uint32_t)gr.chain.seg_ids.size();
+    ba.Cpack = gr.chain.d_Cpack.get(); ba.TS = p->N + (p->N & 1);
+    ba.phase = gr.chain.rank1 ? 1 : 0; ba.t_to = gr.chain.rank1 ? gr.chain.checkpoints[0] : INT_MAX;
+    ba.r1flag = gr.chain.d_r1flag.get(); ba.r1at = gr.chain.d_r1at.get(); ba.r1u = gr.chain.d_r1u.get(); ba.r1alpha = gr.chain.d_r1alpha.get();
     return ba;
 }
 
 // Raw symbols, then the merged tokens: one launch per run of one dictionary depth (tokens of a depth are independent)
 int Launch::big_table(const Group &gr, const BigArgs &ba) const
 {
-    if (gr.rank1) HIP_TRY(hipMemsetAsync(gr.d_r1flag, 0, (size_t)p->B * p->n_segs * 4, stream));   // nothing certified yet
+    if (gr.chain.rank1) HIP_TRY(hipMemsetAsync(gr.chain.d_r1flag.get(), 0, (size_t)p->B * p->n_segs * 4, stream));   // nothing certified yet
     hipLaunchKernelGGL(kc->big_table_raw, dim3((unsigned)p->S, (unsigned)p->B), dim3(kc->G * 64), 0, stream, ba);
     HIP_TRY(hipGetLastError());
-    for (const auto &run : gr.table_runs) {
+    for (const auto &run : gr.chain.table_runs) {
         hipLaunchKernelGGL(kc->big_table_level, dim3((unsigned)run.second, (unsigned)p->B), dim3(kc->G * 64), 0,
                            stream, ba, (const uint16_t *)gr.dict->d_order, run.first);
         HIP_TRY(hipGetLastError());
@@ -1869,10 +1963,10 @@ int Launch::matvec_chain(const Group &gr)
 {
     const BigArgs ba = big_args(p, gr);
     if (int rc = big_table(gr, ba)) return rc;
-    const unsigned grid = B >= 8 ? 8u * (unsigned)gr.big_blocks.size() * (unsigned)((B + 7) / 8)
-                                 : (unsigned)gr.big_blocks.size() * (unsigned)B;
+    const unsigned grid = B >= 8 ? 8u * (unsigned)gr.chain.big_blocks.size() * (unsigned)((B + 7) / 8)
+                                 : (unsigned)gr.chain.big_blocks.size() * (unsigned)B;
     hipLaunchKernelGGL(kc->big_vec, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                       (const BigBlock *)gr.d_big_blocks, (int)gr.big_blocks.size(), B);
+                       (const BigBlock *)gr.chain.d_big_blocks.get(), (int)gr.chain.big_blocks.size(), B);
     note("k_big_vector<" + std::to_string(kc->G) + ">" + stream_tag(gr));
     account(gr);
     HIP_TRY(hipGetLastError());
@@ -1885,30 +1979,30 @@ int Launch::gemm_chain(const Group &gr)
     BigArgs ba = big_args(p, gr);
     if (int rc = big_table(gr, ba)) return rc;
     if (int rc = allow_lds_budget(kc->big_prop)) return rc;
-    const dim3 prop_grid((unsigned)gr.big_blocks.size(), (unsigned)B), prop_block(kc->big_prop_waves * 64);
-    hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.d_big_blocks);
+    const dim3 prop_grid((unsigned)gr.chain.big_blocks.size(), (unsigned)B), prop_block(kc->big_prop_waves * 64);
+    hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.chain.d_big_blocks.get());
     note(std::string(kc->big_prop_waves != kc->G ? "k_big_propagate_s<" : "k_big_propagate<") + std::to_string(kc->G) + ">" + stream_tag(gr));
-    if (gr.rank1 && !gr.tail_blocks.empty()) {
+    if (gr.chain.rank1 && !gr.chain.tail_blocks.empty()) {
         // The first round of heads is done.  Per checkpoint: certify which of the operators still on the GEMM
         // chain collapsed to rank one, then run the others up to the next checkpoint; after the last one the
         // certified segments finish on the mat-vec chain and the rest on the GEMM chain.  Every launch covers
         // all segments and a workgroup with nothing to do exits at once, so there is no host round trip.
-        for (size_t r = 0; r < gr.checkpoints.size(); ++r) {
+        for (size_t r = 0; r < gr.chain.checkpoints.size(); ++r) {
             HIP_TRY(hipGetLastError());
-            ba.t_to = gr.checkpoints[r];
-            hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
-                               (const BigBlock *)gr.d_tail_blocks, kc->NP);
+            ba.t_to = gr.chain.checkpoints[r];
+            hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.chain.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
+                               (const BigBlock *)gr.chain.d_tail_blocks.get(), kc->NP);
             HIP_TRY(hipGetLastError());
-            ba.t_from = gr.checkpoints[r];
-            ba.t_to = r + 1 < gr.checkpoints.size() ? gr.checkpoints[r + 1] : INT_MAX;
-            if (r + 1 == gr.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
-                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.tail_blocks.size() * (unsigned)((B + 7) / 8)
-                                             : (unsigned)gr.tail_blocks.size() * (unsigned)B;
+            ba.t_from = gr.chain.checkpoints[r];
+            ba.t_to = r + 1 < gr.chain.checkpoints.size() ? gr.chain.checkpoints[r + 1] : INT_MAX;
+            if (r + 1 == gr.chain.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
+                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.chain.tail_blocks.size() * (unsigned)((B + 7) / 8)
+                                             : (unsigned)gr.chain.tail_blocks.size() * (unsigned)B;
                 hipLaunchKernelGGL(kc->big_vec_tail, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                                   (const BigBlock *)gr.d_tail_blocks, (int)gr.tail_blocks.size(), B);
+                                   (const BigBlock *)gr.chain.d_tail_blocks.get(), (int)gr.chain.tail_blocks.size(), B);
                 HIP_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.d_big_blocks);
+            hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.chain.d_big_blocks.get());
         }
         note("rank1-handoff");
     }
@@ -1922,13 +2016,13 @@ int Launch::gemm_chain(const Group &gr)
 BigArgs Launch::blocked_args(const Group &gr)
 {
     BigArgs ba = common_args(p, gr);
-    ba.blocks = gr.d_blocks;
-    ba.n_group_segs = (uint32_t)gr.blocks.size();
-    ba.tab_order = gr.d_tab_order; ba.tab_lvl = gr.d_tab_lvl; ba.tab_nlvl = gr.tab_nlvl;
-    ba.hot = gr.d_hot; ba.n_hot = gr.n_hot; ba.tab_desc = gr.d_tab_desc;
-    if (gr.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.tail_stride <= 4)) && allow_tail && (p->kc->use3() || p->wide)) {
-        ba.tail = gr.d_tails; ba.tailX = gr.d_tailX; ba.tailE = gr.d_tailE; ba.tail_arrive = gr.d_tail_arrive;
-        ba.tail_out = out; ba.tail_stride = gr.tail_stride;
+    ba.blocks = gr.blk.d_blocks.get();
+    ba.n_group_segs = (uint32_t)gr.blk.blocks.size();
+    ba.tab_order = gr.blk.d_tab_order.get(); ba.tab_lvl = gr.blk.d_tab_lvl.get(); ba.tab_nlvl = gr.blk.tab_nlvl;
+    ba.hot = gr.blk.d_hot.get(); ba.n_hot = gr.blk.n_hot; ba.tab_desc = gr.blk.d_tab_desc.get();
+    if (gr.blk.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (p->kc->use3() || p->wide)) {
+        ba.tail = gr.blk.d_tails.get(); ba.tailX = gr.blk.d_tailX.get(); ba.tailE = gr.blk.d_tailE.get(); ba.tail_arrive = gr.blk.d_tail_arrive.get();
+        ba.tail_out = out; ba.tail_stride = gr.blk.tail_stride;
         tail_used = true;
     }
     return ba;
@@ -1944,46 +2038,46 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
         hipLaunchKernelGGL(kc->zip4_raw, dim3((unsigned)p->S + 1, (unsigned)B), dim3(256), 0, stream, ba);
         HIP_TRY(hipGetLastError());
     }
-    if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && kc->NP <= 12)) && gr.d_tab_desc3 && kc->zip4_level3) {
+    if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && kc->NP <= 12)) && gr.blk.d_tab_desc3 && kc->zip4_level3) {
         if (int rc = allow_lds_budget(kc->zip4_level3)) return rc;
         if (int rc = allow_lds_budget(kc->zip4_level3_first)) return rc;
-        for (const auto &lc : gr.tab3) {          // three dictionary depths per launch, one wavefront per token
+        for (const auto &lc : gr.blk.tab3) {          // three dictionary depths per launch, one wavefront per token
             const dim3 grid((unsigned)(lc.second + Z4L3_WAVES - 1) / Z4L3_WAVES, (unsigned)B);
             if (head)
                 hipLaunchKernelGGL(kc->zip4_level3_first, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(p->pstride), stream, ba,
-                                   (const int4 *)gr.d_tab_desc3, lc.first, lc.second, staged);
+                                   (const int4 *)gr.blk.d_tab_desc3.get(), lc.first, lc.second, staged);
             else
                 hipLaunchKernelGGL(kc->zip4_level3, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(0), stream, ba,
-                                   (const int4 *)gr.d_tab_desc3, lc.first, lc.second, none);
+                                   (const int4 *)gr.blk.d_tab_desc3.get(), lc.first, lc.second, none);
             head = false;
             HIP_TRY(hipGetLastError());
         }
-    } else if (g.table_pairs && gr.d_tab_desc2 && kc->zip4_level2) {
+    } else if (g.table_pairs && gr.blk.d_tab_desc2 && kc->zip4_level2) {
         const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
-        for (const auto &lc : gr.tab2) {          // two dictionary depths per launch
+        for (const auto &lc : gr.blk.tab2) {          // two dictionary depths per launch
             if (g.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
                 if (head)
                     hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
                                        dim3(Z4_SPLIT_WAVES_FIRST * 64), p->pstride * 8, stream, ba,
-                                       (const int4 *)gr.d_tab_desc2, lc.first, lc.second, staged);
+                                       (const int4 *)gr.blk.d_tab_desc2.get(), lc.first, lc.second, staged);
                 else
                     hipLaunchKernelGGL(kc->zip4_level2_split, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES - 1) / Z4_SPLIT_WAVES, (unsigned)B),
                                        dim3(Z4_SPLIT_WAVES * 64), 0, stream, ba,
-                                       (const int4 *)gr.d_tab_desc2, lc.first, lc.second, none);
+                                       (const int4 *)gr.blk.d_tab_desc2.get(), lc.first, lc.second, none);
                 split_used = true;
             } else if (head)
                 hipLaunchKernelGGL(kc->zip4_level2_first, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64),
                                    p->pstride * 8, stream, ba,
-                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, staged);
+                                   (const int4 *)gr.blk.d_tab_desc2.get(), lc.first, lc.second, staged);
             else
                 hipLaunchKernelGGL(kc->zip4_level2, dim3((unsigned)(lc.second + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba,
-                                   (const int4 *)gr.d_tab_desc2, lc.first, lc.second, none);
+                                   (const int4 *)gr.blk.d_tab_desc2.get(), lc.first, lc.second, none);
             head = false;
             HIP_TRY(hipGetLastError());
         }
     } else
-        for (int d = 0; d < gr.tab_nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
-            const int first = gr.tab_lvl[d], count = gr.tab_lvl[d + 1] - first;
+        for (int d = 0; d < gr.blk.tab_nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
+            const int first = gr.blk.tab_lvl[d], count = gr.blk.tab_lvl[d + 1] - first;
             hipLaunchKernelGGL(kc->zip4_level, dim3((unsigned)(count + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba, first, count);
             HIP_TRY(hipGetLastError());
         }
@@ -1995,20 +2089,20 @@ int Launch::zip4(const Group &gr)
 {
     BigArgs ba = blocked_args(gr);
     if (int rc = z4_table(gr, ba)) return rc;
-    void (*scan)(BigArgs) = gr.stream_table ? (gr.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.wide_tokens ? kc->zip4w : kc->zip4);
+    void (*scan)(BigArgs) = gr.blk.stream_table ? (gr.blk.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.blk.wide_tokens ? kc->zip4w : kc->zip4);
     if (int rc = allow_lds_budget(scan)) return rc;
     if (int rc = mark_a()) return rc;
     // XCD-affine grid (BigArgs::n_phases): with the two-dimensional grid every XCD's L2 sees the tables of all
     // B parameter sets
     dim3 scan_grid(ba.n_group_segs, (unsigned)B);
     if (g.xcd_affine && B > 1) {
-        const imc::PhaseTable &t = gr.phases;
+        const imc::PhaseTable &t = gr.blk.phases;
         ba.n_phases = t.n_phases;
         for (int k = 0; k < t.n_phases; ++k) { ba.ph_begin[k] = t.ph_begin[k]; ba.ph_first[k] = t.ph_first[k]; ba.ph_sets[k] = t.ph_sets[k]; }
         scan_grid = dim3((unsigned)t.grid);
     }
-    hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.n_hot), stream, ba);
-    note(std::string("k_zpropagate4<") + std::to_string(kc->NP / 4) + (gr.wide_tokens ? ",16" : "") + (gr.stream_table ? ",streamed>" : ">") + stream_tag(gr));
+    hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.blk.n_hot), stream, ba);
+    note(std::string("k_zpropagate4<") + std::to_string(kc->NP / 4) + (gr.blk.wide_tokens ? ",16" : "") + (gr.blk.stream_table ? ",streamed>" : ">") + stream_tag(gr));
     account(gr);
     HIP_TRY(hipGetLastError());
     return IMC_OK;
@@ -2070,20 +2164,20 @@ int Launch::stitch() const
         if (!in.n_segs || !ot.n_chains) continue;
         if (!kc->chain_self_emax) {   // (the single-wavefront chain kernels find the units' largest exponents themselves)
             hipLaunchKernelGGL(k_emax, dim3((in.n_segs + 255) / 256, (unsigned)B), dim3(256), 0, stream,
-                               in.d_vec0, in.d_first, in.n_segs, in.n_vecs, N, in.d_EX, in.d_EMAX);
+                               in.d_vec0.get(), in.d_first.get(), in.n_segs, in.n_vecs, N, in.d_EX.get(), in.d_EMAX.get());
             HIP_TRY(hipGetLastError());
         }
         const int threads = (int)round_up((size_t)NP, 64);
         const bool last_level = l + 2 == p->levels.size();
         hipLaunchKernelGGL(kc->chain, dim3(ot.n_chains, (unsigned)B), dim3(threads), 0, stream,
-                           ot.d_chains, N, in.d_vec0, in.n_segs, in.n_vecs, in.d_P, in.d_EX, in.d_EMAX,
-                           ot.n_vecs, ot.d_P, ot.d_EX, (last_level && p->finish_fused) ? out : (double *)nullptr, p->n_chunks);
+                           ot.d_chains.get(), N, in.d_vec0.get(), in.n_segs, in.n_vecs, in.d_P.get(), in.d_EX.get(), in.d_EMAX.get(),
+                           ot.n_vecs, ot.d_P.get(), ot.d_EX.get(), (last_level && p->finish_fused) ? out : (double *)nullptr, p->n_chunks);
         HIP_TRY(hipGetLastError());
     }
     if (p->n_chunks && !p->finish_fused) {
         const Level &last = p->levels.back();
         hipLaunchKernelGGL(k_finish, dim3((p->n_chunks + 63) / 64, (unsigned)B), dim3(64), 0, stream,
-                           p->d_final_vec, p->n_chunks, N, NP, last.n_vecs, last.d_P, last.d_EX, out);
+                           p->d_final_vec.get(), p->n_chunks, N, NP, last.n_vecs, last.d_P.get(), last.d_EX.get(), out);
         HIP_TRY(hipGetLastError());
     }
     return IMC_OK;
@@ -2108,12 +2202,17 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
     p->kernels.clear();
     for (const Group &gr : p->groups) {
         if (!gr.n_vecs) continue;
-        if (!gr.zip4)
+        if (!gr.global_table())
             if (int rc = L.mark_a()) return rc;
-        const int rc = gr.big    ? (gr.bigvec ? L.matvec_chain(gr) : L.gemm_chain(gr))
-                       : gr.zip2 ? (gr.zip4 ? L.zip4(gr) : L.zip32(gr))
-                       : gr.zip  ? L.zpropagate(gr)
-                                 : L.propagate(gr);
+        int rc = IMC_OK;
+        switch (gr.kind) {
+        case Group::Kind::ColumnVector: rc = L.propagate(gr); break;
+        case Group::Kind::TokenVector: rc = L.zpropagate(gr); break;
+        case Group::Kind::BlockedLds: rc = L.zip32(gr); break;
+        case Group::Kind::BlockedGlobal: rc = L.zip4(gr); break;
+        case Group::Kind::GemmChain: rc = L.gemm_chain(gr); break;
+        case Group::Kind::MatVecChain: rc = L.matvec_chain(gr); break;
+        }
         if (rc) return rc;
     }
     if (int rc = L.mark_a()) return rc;
@@ -2145,22 +2244,22 @@ void collect_rank1_stats(Plan *p)
 {
     g.r1_checked = g.r1_collapsed = 0;
     for (Group &gr : p->groups) {
-        if (!gr.rank1 || gr.r1_segs.empty() || gr.checkpoints.empty()) continue;
+        if (!gr.chain.rank1 || gr.chain.r1_segs.empty() || gr.chain.checkpoints.empty()) continue;
         std::vector<int> flags((size_t)p->B * p->n_segs);
-        if (hipMemcpy(flags.data(), gr.d_r1flag, flags.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
+        if (hipMemcpy(flags.data(), gr.chain.d_r1flag.get(), flags.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
         for (int b = 0; b < p->B; ++b)
-            for (const auto &sl : gr.r1_segs) {
-                if ((int)sl.second <= gr.checkpoints[0]) continue;
+            for (const auto &sl : gr.chain.r1_segs) {
+                if ((int)sl.second <= gr.chain.checkpoints[0]) continue;
                 ++g.r1_checked;
                 g.r1_collapsed += flags[(size_t)b * p->n_segs + sl.first] ? 1 : 0;
             }
         if (getenv("IMC_DEBUG_R1")) {          // where each head was certified (diagnostics only)
             std::vector<int> at((size_t)p->B * p->n_segs);
-            if (hipMemcpy(at.data(), gr.d_r1at, at.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
+            if (hipMemcpy(at.data(), gr.chain.d_r1at.get(), at.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
             std::map<int, int> hist;
-            for (const auto &sl : gr.r1_segs) hist[flags[sl.first] ? at[sl.first] : -1]++;
+            for (const auto &sl : gr.chain.r1_segs) hist[flags[sl.first] ? at[sl.first] : -1]++;
             fprintf(stderr, "[imc] rank-one hand-off: segment length %zu tokens, checkpoints", (size_t)gr.seglen);
-            for (int c : gr.checkpoints) fprintf(stderr, " %d", c);
+            for (int c : gr.chain.checkpoints) fprintf(stderr, " %d", c);
             fprintf(stderr, "\n[imc]   certified at (tokens: segments)");
             for (auto &kv : hist) fprintf(stderr, " %d:%d", kv.first, kv.second);
             fprintf(stderr, "\n");
@@ -2231,8 +2330,7 @@ int run_batch(const imc_obs *const *chunks, int n_chunks, int B, int N, int S, c
     if (use_graph) HIP_TRY(hipGraphLaunch(p->graph, g.stream));
     else if (int rc = enqueue(p, g.stream, p->h_out_dev)) return rc;
     ++p->calls;
-    for (int k = 0; k < 8; ++k) g.last_plan[k] = p->lp[k];
-    g.last_kernels = p->kernels;
+    publish_last(p);
     const auto h3 = now();
     const hipStream_t st = g.stream;
     lk.unlock();                                 // other threads may enqueue their evaluations while this one waits
@@ -2279,27 +2377,24 @@ int run_state(const imc_obs *const *chunks, int n_chunks, bool op_mode, int B, i
     Plan *p = nullptr;
     if (int rc = build_plan(chunks, n_chunks, N, S, B, op_mode, &p)) return rc;
     if (int rc = stage_params(p, pis, Ts, Es, g.use_graphs)) return rc;
-    if (int rc = enqueue(p, g.stream, p->d_out, false)) return rc;      // (the log-likelihoods are not read here; the state comes from the stitch levels)
+    if (int rc = enqueue(p, g.stream, p->d_out.get(), false)) return rc;      // (the log-likelihoods are not read here; the state comes from the stitch levels)
     ++p->calls;
-    for (int k = 0; k < 8; ++k) g.last_plan[k] = p->lp[k];
-    g.last_kernels = p->kernels;
+    publish_last(p);
     const size_t per = op_mode ? (size_t)N * N : (size_t)N, pere = op_mode ? (size_t)N : 1;
     const size_t n_state = (size_t)B * n_chunks * per, n_exp = (size_t)B * n_chunks * pere;
-    double *d_state = nullptr;
-    int *d_exp = nullptr;
-    hipError_t e = dev_alloc((void **)&d_state, std::max<size_t>(n_state * 8, 16));
-    if (e == hipSuccess) e = dev_alloc((void **)&d_exp, std::max<size_t>(n_exp * 4, 16));
+    DevBuf<double> d_state;
+    DevBuf<int> d_exp;
+    hipError_t e = d_state.alloc(std::max<size_t>(n_state * 8, 16));
+    if (e == hipSuccess) e = d_exp.alloc(std::max<size_t>(n_exp * 4, 16));
     if (e == hipSuccess) {
         const Level &last = p->levels.back();
-        hipLaunchKernelGGL(k_export, dim3((unsigned)n_chunks, (unsigned)B), dim3(256), 0, g.stream, p->d_final_vec, n_chunks, N,
-                           p->kc->NP, last.n_vecs, last.d_P, last.d_EX, op_mode ? 1 : 0, d_state, d_exp);
+        hipLaunchKernelGGL(k_export, dim3((unsigned)n_chunks, (unsigned)B), dim3(256), 0, g.stream, p->d_final_vec.get(), n_chunks, N,
+                           p->kc->NP, last.n_vecs, last.d_P.get(), last.d_EX.get(), op_mode ? 1 : 0, d_state.get(), d_exp.get());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_state, d_state, n_state * 8, hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_exp, d_exp, n_exp * 4, hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_state, d_state.get(), n_state * 8, hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_exp, d_exp.get(), n_exp * 4, hipMemcpyDeviceToHost, g.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    dev_free(d_state);
-    dev_free(d_exp);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP, std::string("state export: ") + hipGetErrorString(e));
     return IMC_OK;
 }
@@ -2890,12 +2985,7 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
         wait_all_idle(lk);
         HIP_TRY(hipSetDevice(g.device));
         HIP_TRY(hipDeviceSynchronize());                 // nothing of these chunks is in flight any more
-        for (auto it = g_plans.begin(); it != g_plans.end();) {      // plans hold raw pointers into the old streams
-            bool uses = false;
-            for (size_t k = 0; k < (size_t)(*it)->n_chunks; ++k)
-                for (imc_obs *o : obs) uses |= (*it)->key[k] == o->id;
-            if (uses) { (*it)->release(); it = g_plans.erase(it); } else ++it;
-        }
+        drop_plans_using(obs.data(), obs.size());        // plans hold raw pointers into the old streams
         if (!zipped) continue;                           // (incompressible sample: keep what the chunks have)
         if (int rc = upload_dictionary(nd)) return rc;
         g.dicts[nsym] = nd;                              // later chunks of this alphabet share it too
@@ -2913,13 +3003,7 @@ int imc_obs_free(imc_obs *obs)
     std::unique_lock<std::mutex> lk(g_mu);
     wait_all_idle(lk);
     if (obs->pid == getpid() && g.ready) {
-        // plans hold raw pointers into this chunk's device buffers
-        for (auto it = g_plans.begin(); it != g_plans.end();) {
-            bool uses = false;
-            for (size_t k = 0; k < (size_t)(*it)->n_chunks; ++k)
-                if ((*it)->key[k] == obs->id) uses = true;
-            if (uses) { (*it)->release(); it = g_plans.erase(it); } else ++it;
-        }
+        drop_plans_using(&obs, 1);
         (void)hipSetDevice(obs->device);
         obs_release(obs);
     }
@@ -2971,11 +3055,10 @@ int imc_forward_batch_device(const imc_obs *const *chunks, int n_chunks, int B, 
     // no stream synchronisation here: the parameters go through the two-slot pinned staging (stage_params waits only
     // for the upload issued two calls ago), and nothing is read back - the call returns once everything is enqueued
     if (int rc = stage_params(p, pis, Ts, Es, g.use_graphs)) return rc;
-    if (int rc = enqueue(p, st, p->d_out)) return rc;
+    if (int rc = enqueue(p, st, p->d_out.get())) return rc;
     ++p->calls;
-    for (int k = 0; k < 8; ++k) g.last_plan[k] = p->lp[k];
-    g.last_kernels = p->kernels;
-    hipLaunchKernelGGL(k_sum_chunks, dim3((B + 63) / 64), dim3(64), 0, st, p->d_out, n_chunks, B, d_out_partial);
+    publish_last(p);
+    hipLaunchKernelGGL(k_sum_chunks, dim3((B + 63) / 64), dim3(64), 0, st, p->d_out.get(), n_chunks, B, d_out_partial);
     HIP_TRY(hipGetLastError());
     return IMC_OK;
 }
