@@ -13,7 +13,8 @@
 //
 // Which kernels run a segment - per alignment column or per token of the pair-compressed stream (pair_dict.hpp),
 // on the VALU or on fp64 MFMA, with the operator table in LDS or in global memory - is decided per launch group
-// (Group::Kind below); the kernel families themselves are described in DESIGN.md section 5.
+// (imc::GroupKind) by the host-only planner in planner_host.hpp; the kernel families themselves are described in
+// DESIGN.md section 5.
 //
 // Host side, in the order of this file: context and device memory (dev_alloc, DevBuf), chunks and dictionaries,
 // the kernel table, the launch plan (Group / Level / Plan own their device buffers) and its builder, one enqueue
@@ -51,6 +52,7 @@
 #include "kernels_zip4.hpp"
 #include "pair_dict.hpp"
 #include "plan_host.hpp"
+#include "planner_host.hpp"
 #include "model_host.hpp"
 #include "kernels_model.hpp"
 #include "../../include/imcoal_model.h"
@@ -78,13 +80,13 @@ int fail(int code, const std::string &msg)
                         std::string(#expr) + ": " + hipGetErrorString(_e));                             \
     } while (0)
 
-// k_zpropagate4 caches nothing in LDS while the operator tables of one launch (all parameter sets) fit this many bytes -
-// they then stay in L2 / the Infinity Cache and a step's operands arrive from there a step ahead (IMC_Z4_STREAM=0/1
-// forces the hybrid / the streamed form).  With more than one parameter set and the XCD-affine grid the streamed form is
-// used whatever the total (PlanBuilder::z4_streamed).
-constexpr double Z4_STREAM_MAX_BYTES = 32.0e6;
+// the planner's constants and helpers that the rest of this file uses too (planner_host.hpp)
+using imc::HYBRID_MAX_ALPHABET;
+using imc::LDS_BUDGET;
+using imc::Z2GRAN;
+using imc::round_up;
+
 constexpr size_t STAGE_KERNEL_MAX_BYTES = 1u << 20;   // parameter sets up to this size are fetched by k_stage_params (enqueue)
-constexpr size_t LDS_BUDGET = 160 * 1024 - 1024;   // bytes of LDS a compressed-path workgroup may use
 constexpr size_t ZIP_MIN_COLUMNS = 4096;           // shorter chunks are not worth compressing
 constexpr size_t DICT_TRAIN_MIN = 32768;           // first chunk at least this long trains the dictionary
 constexpr size_t DICT_TRAIN_MAX = 8u << 20;        // byte tokens (< 256): train on at most this prefix
@@ -94,21 +96,6 @@ constexpr int DICT_MAX_DEPTH = 0;                  // 0: no limit on a token's d
                                                    // their 11 depths - a cap of 10 saves one launch at 149.5 instead of 150.2 columns per
                                                    // token, 9 already costs 13 % of the compression, 8 leaves 208 tokens)
 constexpr size_t DICT_WIDE_MIN_COUNT = 6;          // ... in which a pair must occur this often
-constexpr size_t CTAB_BUDGET = (size_t)24 << 30;   // largest operator table (all parameter sets) a plan may allocate
-#ifndef IMC_HYBRID_MAX_ALPHABET
-#define IMC_HYBRID_MAX_ALPHABET 4096
-#endif
-// hybrid table (k_zpropagate4): largest dictionary level considered.  Measured at N = 20 on the bench alignment: 1024 tokens
-// (3.3 MB of operators, resident in every XCD's 4 MB L2) 0.360 ms per evaluation, 1536: 0.347, 4096 (13 MB, Infinity
-// Cache): 0.342 - the columns per token saturate (133 / 139 / 150) while a cold step gets dearer
-constexpr int HYBRID_MAX_ALPHABET = IMC_HYBRID_MAX_ALPHABET;
-constexpr size_t Z2GRAN = 4;                       // blocked kernels: segment lengths are multiples of this many tokens
-constexpr size_t R1_MIN_SEGLEN = 1024;             // rank-one hand-off: segments at least this long (stream elements) ...
-constexpr size_t R1_MIN_HEAD = 256;                // ... run at least this many on the GEMM chain before the test
-constexpr double R1_HEAD_COLUMNS = 65536.0;        // planner's estimate of the columns a head needs before it collapses
-constexpr double R1_HEAD_MIN_COLUMNS = 8192.0;     // first checkpoint of the hand-off test, in alignment columns
-constexpr int R1_MAX_ROUNDS = 24;                  // checkpoints per evaluation
-constexpr double R1_DENSE_COLUMNS = 1.0e5;         // ... spaced 1.125x up to this many alignment columns, 1.5x beyond
 
 hipError_t dev_alloc(void **p, size_t bytes);
 void dev_free(void *p);
@@ -541,11 +528,9 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
 using ChainFn = void (*)(const ChainDesc *, int, const uint32_t *, uint32_t, uint32_t, const double *, const int *,
                          const int *, uint32_t, double *, int *, double *, int);
 
-struct KernelChoice {
-    int R = 0, G = 0, NP = 0, VPW = 0, minw = 1;   // R == 0: large-N GEMM-chain path (kernels_big.hpp), NP = 16 * G
+struct KernelChoice : imc::KernelFacts {   // the planner's facts of the entry (planner_host.hpp) + the kernels themselves
     void (*plain)(PropArgs) = nullptr;
     void (*zip)(PropArgs) = nullptr;
-    size_t (*zip_lds)(int) = nullptr;
     ChainFn chain = nullptr;
     void (*big_table_raw)(BigArgs) = nullptr;
     void (*big_table_level)(BigArgs, const uint16_t *, int) = nullptr;
@@ -554,12 +539,8 @@ struct KernelChoice {
     void (*big_vec)(BigArgs, const BigBlock *, int, int) = nullptr;
     void (*big_vec_tail)(BigArgs, const BigBlock *, int, int) = nullptr;   // rank-one hand-off: mat-vec chain over segment tails
     int big_vec_waves = 0;
-    int big_nslab = 0;
-    size_t big_lds = 0;
     void (*zip2)(BigArgs) = nullptr;   // register-blocked token kernel (NP = 4 RB <= 24), else null
-    size_t (*zip2_lds)(int) = nullptr;
     void (*zip3)(BigArgs) = nullptr;   // ... its fp64-MFMA form (same launch geometry and block list)
-    size_t (*zip3_lds)(int) = nullptr;
     void (*zip4)(BigArgs) = nullptr;   // ... with the hybrid LDS / L2 operator table, and the kernels that build that table
     void (*zip4w)(BigArgs) = nullptr;  // ... on 16-bit token streams (dictionary levels beyond 256 tokens)
     void (*zip4s)(BigArgs) = nullptr, (*zip4sw)(BigArgs) = nullptr;   // ... with the STREAMED table (nothing cached in LDS)
@@ -572,16 +553,13 @@ struct KernelChoice {
     void (*zip4_level3)(BigArgs, const int4 *, int, int, const double *) = nullptr;        // three dictionary depths per launch
     void (*zip4_level3_first)(BigArgs, const int4 *, int, int, const double *) = nullptr;
     size_t (*zip4_level3_lds)(size_t) = nullptr;
-    size_t (*zip4_lds)(int, int) = nullptr;
-    int (*zip4_max_hot)(int, size_t) = nullptr;
-    int tok_doubles = 0;               // doubles per table entry of the MFMA kernels
-    int z4_waves = Z2WAVES;            // wavefronts per workgroup of the blocked scan (Zip4Shape); segments per workgroup = 4 x
-    bool wide_blocked = false;         // 25-32 states: of the blocked family only the streamed scan and the one-depth table build exist
-    int z4_slots() const { return z4_waves * 4; }
     bool chain_self_emax = false;      // the stitch kernel finds the units' largest exponents itself (no k_emax launch)
-    // the blocked kernel in use (g.blocked_variant) and its LDS need for an alphabet of A tokens
-    bool use3() const;
-    size_t blocked_lds(int A) const { return use3() ? zip3_lds(A) : zip2_lds(A); }
+    // (KernelFacts' flags say which of the planner's kernels the entry has)
+    void note_kernels()
+    {
+        has_zip2 = zip2 != nullptr; has_zip3 = zip3 != nullptr; has_zip4 = zip4 != nullptr; has_zip4s = zip4s != nullptr;
+        has_level2 = zip4_level2 != nullptr;
+    }
 };
 
 template <int R, int G, int MW>
@@ -590,6 +568,8 @@ KernelChoice make_kc()
     constexpr int NP = R * G;
     KernelChoice k;
     k.R = R; k.G = G; k.NP = NP; k.VPW = 64 / G; k.minw = MW;
+    k.zwaves = ZWAVES;
+    k.z4_waves = Z2WAVES;
     k.plain = k_propagate<R, G, MW>;
     k.zip = k_zpropagate<R, G>;
     k.zip_lds = &ZipGeom<R, G>::lds_bytes;
@@ -629,6 +609,7 @@ KernelChoice make_kc()
         k.z4_waves = Zip4Shape<NP / 4>::WAVES;
         k.wide_blocked = true;
     }
+    k.note_kernels();
     return k;
 }
 
@@ -639,6 +620,7 @@ KernelChoice make_big()
     constexpr bool dealt = NT > 4 && NT % 4 != 0;
     KernelChoice k;
     k.G = NT; k.NP = 16 * NT;          // NT wavefronts per workgroup
+    k.z4_waves = Z2WAVES;
     k.chain = k_chain<16 * NT, 0>;
     k.big_table_raw = k_big_table_raw<NT>;
     k.big_table_level = k_big_table_level<NT>;
@@ -652,8 +634,6 @@ KernelChoice make_big()
     k.big_lds = BigSlab<NT, NSLAB>::bytes;
     return k;
 }
-
-bool KernelChoice::use3() const { return zip3 && g.blocked_variant >= 3; }
 
 KernelChoice kChoices[] = {
     make_kc<4, 1, 2>(), make_kc<4, 2, 2>(), make_kc<4, 3, 2>(), make_kc<4, 4, 2>(), make_kc<4, 5, 2>(),
@@ -681,16 +661,9 @@ KernelChoice *choose_kernel(int N, bool prefer_gemm)
 // ---- launch plan ----------------------------------------------------------------------------------
 
 struct Group {             // one propagate launch
-    // Which kernel family runs the group: fixed once, at the end of PlanBuilder::choose_segment_lengths(); everything
-    // after that point reads `kind` or one of the predicates below.  enqueue() has one case per kind.
-    enum class Kind {
-        ColumnVector,    // k_propagate: one step per alignment column
-        TokenVector,     // k_zpropagate: one step per token, operator table in LDS
-        BlockedLds,      // register-blocked scan (one 16-lane row per segment), table in LDS: k_zpropagate3 / k_zpropagate2
-        BlockedGlobal,   // ... fp64-MFMA scan on the global (hybrid or streamed) table: k_zpropagate4, alphabets beyond LDS
-        GemmChain,       // large-N GEMM chain (one workgroup per segment and column slab): k_big_propagate
-        MatVecChain,     // ... every chunk is one segment: mat-vec chain (k_big_vector), no operators
-    };
+    // Which kernel family runs the group: decided by imc::decide_groups (planner_host.hpp); everything after that reads
+    // `kind` or one of the predicates below.
+    using Kind = imc::GroupKind;
     Kind kind = Kind::ColumnVector;
     bool is_chain() const { return kind == Kind::GemmChain || kind == Kind::MatVecChain; }
     bool is_blocked() const { return kind == Kind::BlockedLds || kind == Kind::BlockedGlobal; }
@@ -859,96 +832,6 @@ void publish_last(const Plan *p)     // what imc_last_plan() / imc_last_kernels(
     g.last_kernels = p->kernels;
 }
 
-size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
-
-// Pick the segment length (in stream elements) that minimises a simple machine model: equal-length
-// wavefront tasks run in rounds of `resident` wavefronts at `step_cost` cycles per step; the serial
-// stitch adds ~stitch_cost per segment of the longest chunk.
-size_t choose_seglen(const std::vector<size_t> &lens, int N, int B, int VPW, double resident, double step_cost,
-                     double *cost_out = nullptr)
-{
-    size_t maxlen = 0;
-    for (size_t L : lens) maxlen = std::max(maxlen, L);
-    if (cost_out) *cost_out = (double)maxlen * step_cost;
-    if (maxlen <= 256) return std::max<size_t>(round_up(maxlen, 16), 16);
-    const double stitch_cost = 12.0 * N + 300.0;   // cycles per stitched segment
-    double best = 1e300;
-    size_t best_seg = maxlen;
-    for (double s = 128.0;; s *= 1.189207115) {
-        const size_t seg = std::min(round_up((size_t)s, 16), round_up(maxlen, 16));
-        double vecs = 0.0, kmax = 0.0;
-        for (size_t L : lens) {
-            if (!L) continue;
-            const double K = std::ceil((double)L / (double)seg);
-            vecs += 1.0 + (K - 1.0) * N;
-            kmax = std::max(kmax, K);
-        }
-        const double waves = std::ceil(vecs * B / VPW);
-        const double rounds = std::ceil(waves / resident);
-        const double cost = rounds * (double)seg * step_cost + kmax * stitch_cost;
-        if (cost < best) { best = cost; best_seg = seg; }
-        if (seg >= maxlen) break;
-    }
-    if (cost_out) *cost_out = best;
-    return best_seg;
-}
-
-// Cycles per chain step and CU of the mat-vec chain kernel (k_big_vector): NP^2 doubles streamed per step.
-// Measured at N=150, 2048 chains: ~NP^2/3 cycles while one parameter set's table stays within ~6 MB (its share of
-// an XCD's L2), growing by ~3 % per further MB as reads fall through to the Infinity Cache, up to the HBM rate.
-// GEMM chain: cycles (at ~2.2 GHz) a CU needs to advance ONE segment by one step - all column slabs of the segment, chip
-// full.  Measured round 3 on every built tile count below (profiles/r03_e_calib_big.txt: one 1e7-column chunk, all CUs
-// busy): 0.55 us at NP = 32, 1.52 at 48, 2.9 at 64, 9.4 at 96, 15.0 at 112, 33 at 160.  Rounds 1-2 used
-// 0.027 NP^3 + 20000 cycles, fitted at NP = 160 on round 1's kernel: 1.8x too high there and 16x too high at NP = 32, so
-// that 24 < N <= 64 with a handful of chunks x parameter sets took the mat-vec chain (one workgroup per chain, 10-40
-// workgroups on 256 CUs) at 3-9x the GEMM chain's time.
-static double gemm_cu_step_cycles(int np)
-{
-    const int nt = np / 16;
-    double us;
-    switch (nt) {
-    case 2: us = 0.55; break;
-    case 3: us = 1.52; break;
-    case 4: us = 2.9; break;
-    case 6: us = 9.4; break;
-    case 7: us = 15.0; break;
-    case 8: us = 22.4; break;
-    case 9: us = 24.1; break;
-    default: us = 33.0 * (nt / 10.0) * (nt / 10.0) * (nt / 10.0); break;
-    }
-    return us * 2200.0;
-}
-
-static double matvec_step_cycles(double np2, int alphabet)
-{
-    const double table_mb = (double)alphabet * np2 * 8.0 / 1.0e6;
-    return np2 / 3.0 * std::min(2.2, 1.0 + 0.03 * std::max(0.0, table_mb - 6.0));
-}
-
-// Rank-one hand-off estimate for a GEMM-chain group whose base plan has `nseg` segments of `seglen` elements (one
-// round of workgroups): m times the segments = m rounds of `head`-long GEMM heads, tails 1/m as long on the mat-vec
-// chain.  A tail step streams NP^2 doubles; with many chains that is the memory system's bandwidth (measured: 256
-// chains of a 1.6 GB table read 7 TB/s), with few it is one workgroup's latency.  Returns the best m (0: not
-// worth it) and its cycles.
-struct HandoffEstimate { int m; double cycles; };
-static HandoffEstimate estimate_handoff(double seglen, double nseg, int B, double head, double np, int nslab, int alphabet, int cus)
-{
-    // (a segment's GEMM step is shared by its nslab column-slab workgroups)
-    const double np2 = np * np, t_gemm = 1.15 * gemm_cu_step_cycles((int)np) / nslab;   // (a head step of one slab's workgroup)
-    const double table_mb = (double)alphabet * np2 * 8.0 / 1.0e6;
-    const double bw = table_mb > 128.0 ? 7.0e12 : table_mb > 16.0 ? 8.6e12 : 15.0e12;   // bytes/s: HBM, Infinity Cache, L2
-    HandoffEstimate best{0, 1e300};
-    for (int m = 1; m <= 6; ++m) {
-        const double sl = seglen / m;
-        if (sl < 2.0 * head) break;
-        const double chains = m * nseg * B, active = std::min(chains, (double)cus);
-        const double t_vec = std::max(np2 / 4.5 + 1500.0, active * np2 * 8.0 * 2.1e9 / bw) * std::max(1.0, chains / cus);
-        const double est = m * head * t_gemm + (sl - head) * t_vec;
-        if (est < best.cycles) best = HandoffEstimate{m, est};
-    }
-    return best;
-}
-
 // Device allocations of one upload with a sticky error: after the first failure the later calls do nothing, and the
 // caller checks `e` once at the end.  (Host-side work between the calls - schedules, block lists - still runs after a
 // failure; only the device calls become no-ops, and the error reported is the first one.)
@@ -975,21 +858,19 @@ struct DevUpload {
     }
 };
 
-// Builds one launch plan in phases; every phase reads what the earlier ones left in the members.
+// Builds the launch descriptors of one plan from the planner's decision (build_plan fills p->groups and chunk_group from
+// imc::decide_groups), in phases; every phase reads what the earlier ones left in the members.
 struct PlanBuilder {
     const imc_obs *const *chunks = nullptr;
     int n_chunks = 0, N = 0, S = 0, B = 0;
     bool op_mode = false;               // imc_forward_state(as_operator): no segment is a chunk's "first"
+    imc::PlanOptions opt;               // the options the decision was taken under
     KernelChoice *kc = nullptr;
     // 25-32 states: kc is the vector kernels' entry and every dictionary's chunks run its streamed blocked scan
-    // (k_zpropagate4<7 | 8>); chunks without tokens stay on the vector kernels.  wide_ok: every dictionary had a level for it.
-    bool wide = false, wide_ok = true;
-    bool mfma() const { return kc->use3() || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
+    // (k_zpropagate4<7 | 8>); chunks without tokens stay on the vector kernels.
+    bool wide = false;
+    bool mfma() const { return kc->use3(opt.blocked_variant) || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
     std::unique_ptr<Plan> p;
-    // What the first two phases know of a group's kind before choose_segment_lengths() fixes Group::kind; nothing
-    // after that phase reads these.
-    bool chain_tentative = false;       // the plan's kernel entry is the large-N one: every group ends as GemmChain or MatVecChain
-    std::vector<char> global_tentative; // per group: its level was chosen for the global-table scan (alphabet beyond LDS, or 16-bit tokens)
     std::vector<int> chunk_group;       // chunk -> index into p->groups
     std::vector<SegDesc> segs;          // all segments, chunk order
     std::vector<uint8_t> seg_first;
@@ -1001,411 +882,6 @@ struct PlanBuilder {
     struct HostLevel { std::vector<uint32_t> chunk_seg, vec0; std::vector<uint8_t> first; std::vector<ChainDesc> chains; uint32_t n_vecs; };
     std::vector<HostLevel> hl;          // stitch hierarchy, level 0 = propagate output
     std::vector<int32_t> final_vec;     // chunk -> its single remaining unit at the last level (-1: empty chunk)
-
-    // k_zpropagate4 on the streamed table (nothing cached in LDS)?  With the XCD-affine grid (enqueue) an XCD reads one or
-    // two parameter sets' tables at a time whatever B is, and the streamed form then beat the hybrid one at every
-    // dictionary level and every B measured (profiles/r03_d_affine_levels.txt); without it, while all tables of the launch
-    // fit the L2s.
-    static bool z4_streamed(double tables_bytes, int n_sets)
-    {
-        if (g.z4_stream >= 0) return g.z4_stream == 1;
-        return (g.xcd_affine && n_sets > 1) || tables_bytes <= Z4_STREAM_MAX_BYTES;
-    }
-
-    // hand-off head of a group, in stream elements: ~R1_HEAD_COLUMNS alignment columns
-    size_t handoff_head(const Group &gr) const
-    {
-        double cols = 0.0, toks = 0.0;
-        for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
-        const double span = toks > 0.0 ? cols / toks : 1.0;
-        return round_up(std::max<size_t>(R1_MIN_HEAD, (size_t)(R1_HEAD_COLUMNS / span)), 16);
-    }
-
-    void assign_groups()
-    {
-        // ---- assign chunks to launch groups: plain, or (dictionary, level) ----
-        const bool big = chain_tentative = kc->R == 0;
-        int a_max = 0;   // largest alphabet whose operator table fits LDS for this N (no limit on the large-N path)
-        if (big) a_max = imc::kMaxAlphabet;
-        else
-            for (int A = 1; A <= imc::kByteAlphabet; ++A)   // (the LDS-table kernels read byte streams only)
-                if (kc->zip_lds(A) <= LDS_BUDGET || (kc->zip2 && g.kernel_pref != 1 && kc->blocked_lds(A) <= LDS_BUDGET)) a_max = A;
-        // One dictionary level per dictionary: the deepest level is not always the best - every workgroup rebuilds
-        // the operator table per evaluation ((A - S) dependent small products), which dominates on short inputs.
-        // Estimate: table build + main loop with all 16-lane rows of the machine busy.
-        std::map<const DictDev *, int> dict_level;
-        const bool mfma_blocked = !big && mfma() && g.kernel_pref != 1;
-        const int SL = kc->z4_slots();   // segments per workgroup of the blocked kernels
-        std::map<const DictDev *, double> dict_cost, dict_tab;     // per dictionary, microseconds: the chosen level's estimate, its table part
-        if (g.compression) {
-            std::map<const DictDev *, std::vector<int>> by_dict;
-            for (int f = 0; f < n_chunks; ++f)
-                if (chunks[f]->dict && chunks[f]->nsym == S) by_dict[chunks[f]->dict.get()].push_back(f);
-            for (auto &kv : by_dict) {
-                double best = 1e300;
-                int best_l = -1;
-                for (int l = 0; l < imc::kNumLevels; ++l) {
-                    const imc_obs *o0 = chunks[kv.second[0]];
-                    if (mfma_blocked) {
-                        // Blocked MFMA kernels, estimated in microseconds: the table is built one dictionary depth at
-                        // a time (32 tokens per pass), the scan advances cus * 32 segments per wavefront-step.  Levels
-                        // that fit LDS run k_zpropagate3; byte levels beyond that can run k_zpropagate4 (hybrid table:
-                        // one workgroup builds it in L2, steps on tokens outside the LDS-cached hot set cost ~12 % more).
-                        const int A = o0->alphabet[l];
-                        if (!(A > o0->nsym && A <= HYBRID_MAX_ALPHABET && o0->d_tok[l]) || o0->wide_raw) continue;
-                        const bool fits = !wide && !o0->wide[l] && kc->blocked_lds(A) <= LDS_BUDGET;   // (k_zpropagate3 reads byte streams)
-                        const int max_hot = kc->zip4 ? kc->zip4_max_hot(A, LDS_BUDGET) : 0;
-                        const double table_bytes = (double)B * (A + 1) * kc->tok_doubles * 8.0;
-                        // (25-32 states: the streamed form or nothing - a table it does not take stays off this path)
-                        const bool hybrid_ok = !fits && !o0->tok_count[l].empty() && table_bytes <= 2.0e9 &&
-                                               (wide ? kc->zip4s && z4_streamed(table_bytes, B) : kc->zip4 && g.blocked_variant >= 4 && max_hot >= 8);
-                        if (!fits && !hybrid_ok) continue;
-                        // (the scan's LDS: the fold's exchange area + the exponents and slot map of all A + 1 entries - at 24
-                        // states the exchange area alone is 152 KB and levels beyond 768 tokens do not fit)
-                        if (!fits && kc->zip4_lds(A, 0) > LDS_BUDGET) continue;
-                        int passes = 0;
-                        {
-                            std::map<int, int> per_depth;
-                            for (int z = o0->nsym; z < A; ++z) per_depth[kv.first->depth[z]]++;
-                            for (auto &pd : per_depth) passes += (pd.second + SL - 1) / SL;
-                        }
-                        // (up to 8 states a step is not MFMA time: measured round 3, 4 and 8 states, 64 sets - 0.08 / 0.14 us from
-                        // the LDS table, 0.19 / 0.22 from the global one; from 12 states on both follow the instruction count)
-                        const double nt = kc->NP / 4.0;
-                        // (a workgroup's step: its wavefronts share the SIMDs' matrix pipes two by two - or, four wavefronts, have one each)
-                        const double t_step = nt < 1.5 ? 0.08 : nt < 2.5 ? 0.14 : std::max(0.25, 1.88 * nt * nt * nt / 125.0) * (kc->z4_waves / 8.0);
-                        const double t_step_g = nt < 1.5 ? 0.19 : nt < 2.5 ? 0.22 : t_step;
-                        // Time of the scan itself: workgroups of 32 segments are dealt PER CHUNK (a chunk of u workgroups is cut
-                        // into 32 u segments), and a launch of more workgroups than CUs runs in rounds, each paying the
-                        // workgroup's fixed part again.  rounds x (fixed + segment length x step) for the best number of rounds -
-                        // not tokens / slots: 100 chunks x 1e6 columns fill 78 % of one round or 98 % of two.
-                        double maxtok = 0.0;
-                        for (int f : kv.second) maxtok = std::max(maxtok, (double)chunks[f]->ntok[l]);
-                        // (up to 12 states two workgroups of the global-table kernel share a CU: twice the slots, 1.85x the step)
-                        const bool two_per_cu = !fits && kc->NP <= 12 && z4_streamed(table_bytes, B);
-                        const double n_ch = (double)kv.second.size(), slots = (double)g.cus * SL * (two_per_cu ? 2.0 : 1.0);
-                        auto scan_time = [&](double fixed_us, double step_us) {
-                            if (two_per_cu) step_us *= 1.85;
-                            double best_t = 1e300;
-                            for (int r = 1; r <= 6; ++r) {
-                                const double units = std::max(1.0, std::floor(slots * r / (n_ch * B) / SL));
-                                const double seg = std::max(16.0, std::ceil(maxtok / (SL * units)));
-                                const double rounds = std::ceil(n_ch * B * units * SL / slots);
-                                best_t = std::min(best_t, rounds * (fixed_us + seg * step_us));
-                            }
-                            return best_t;
-                        };
-                        double cost;
-                        // LDS table: EVERY workgroup rebuilds it, one barrier-separated pass per 32 tokens of a depth
-                        // (measured round 3: ~1.9 us per pass at 10 states, ~2.8 at 20), plus launch and the in-kernel
-                        // fold (~14 us).  Round 2 priced a pass at 1.1 us and no fixed part: at 10 states and 100 x 1e6
-                        // columns it then preferred the 128-token LDS table (135 us) to the global table (102 us).
-                        if (fits) cost = 4.0 + scan_time(10.0 + passes * (1.6 + 1.2 * nt * nt * nt / 125.0), t_step);
-                        else {
-                            std::vector<uint64_t> cnt((size_t)A, 0);
-                            for (int f : kv.second)
-                                for (size_t z = 0; z < chunks[f]->tok_count[l].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[l][z];
-                            std::vector<uint64_t> sorted(cnt);
-                            std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
-                            uint64_t all = 0, top = 0;
-                            for (size_t z = 0; z < sorted.size(); ++z) { all += sorted[z]; if ((int)z < std::min(max_hot, A)) top += sorted[z]; }
-                            const double cold = all ? 1.0 - (double)top / (double)all : 0.0;
-                            const double depths = (double)std::max<int>(1, (int)std::set<int>(kv.first->depth.begin() + o0->nsym, kv.first->depth.begin() + A).size());
-                            // one ~4 us launch per depth; a cold step costs ~11 % more while one parameter set's table
-                            // stays in an XCD's L2, ~17 % from the Infinity Cache (scratch microbenchmark)
-                            // (hybrid form; the streamed form - tables of the launch cache resident - runs every step
-                            // from the global table at ~6 % over the LDS-table kernel's step: measured at config[1])
-                            const double cold_pen = table_bytes / B <= 3.6e6 ? 0.11 : 0.17;
-                            const bool streamed = z4_streamed(table_bytes, B);
-                            // (table: one ~4.5 us launch per depth, or one ~5.7 us launch per pair of depths)
-                            // (measured round 3: the first launch - it fetches the parameters - ~13 us, the others ~7.5)
-                            double t_table = g.table_pairs && kc->zip4_level2 ? 13.0 + (std::ceil(depths / 2.0) - 1.0) * 7.5 : 6.0 + depths * 4.9;
-                            // ... which is latency; B tables of A operators are also two reads and a write of an operator per
-                            // token and parameter set, at ~2.8 TB/s (measured round 3, 64 sets: 4096- against 512-token tables)
-                            t_table += std::max(0.0, table_bytes * 3.0 / 2.8e6 - 0.5 * t_table);
-                            cost = t_table + scan_time(8.0, t_step_g * (streamed ? 1.06 : 1.0 + cold_pen * cold));
-                        }
-                        if (cost < best) dict_cost[kv.first] = cost;
-                        if (g.blocked_variant == 5 && !fits) cost *= 1e-3;      // tests: the hybrid table wherever it is possible
-                        if (std::getenv("IMC_DEBUG_LEVELS"))
-                            std::fprintf(stderr, "[imc] level %d alphabet %d %s: model %.1f us\n", l, A,
-                                         fits ? "LDS table" : two_per_cu ? "global table, 2 per CU" : "global table", cost);
-                        if (cost < best) { best = cost; best_l = l; }
-                        continue;
-                    }
-                    if (!(o0->alphabet[l] <= a_max && o0->alphabet[l] > o0->nsym && o0->d_tok[l])) continue;
-                    if (big && (size_t)B * o0->alphabet[l] * kc->NP * kc->NP * 8 > CTAB_BUDGET) continue;   // table too large
-                    double toks = 0.0;
-                    for (int f : kv.second) toks += (double)chunks[f]->ntok[l];
-                    const double n3 = (double)kc->NP * kc->NP * kc->NP;
-                    double c_tab, c_main;   // cycles
-                    if (big) {   // one GEMM per step per workgroup, table built by depth
-                        const double gemm = gemm_cu_step_cycles(kc->NP);
-                        c_tab = ((o0->alphabet[l] - S) / (double)g.cus + 12.0) * gemm;   // one workgroup per token, ~12 depth launches
-                        c_main = std::max(16.0, toks * B / (double)g.cus) * gemm;
-                        double lmax = 0.0;   // or the mat-vec chain kernel, when no chunk needs splitting
-                        for (int f : kv.second) lmax = std::max(lmax, (double)chunks[f]->ntok[l]);
-                        const double np2 = (double)kc->NP * kc->NP;
-                        const double c_vec = std::max(lmax * (np2 / 4.5 + 1500.0), toks * B / (double)g.cus * matvec_step_cycles(np2, o0->alphabet[l]));
-                        if (!op_mode && (g.kernel_pref == 1 || (g.kernel_pref == 0 && c_vec < c_main))) c_main = c_vec;
-                    } else {     // ~5200 cycles per row-step at N=20; every workgroup rebuilds the table
-                        c_tab = (o0->alphabet[l] - S) * (400.0 + n3 / 64.0);
-                        c_main = std::max(16.0, toks * B / ((double)g.cus * 32.0)) * 0.65 * n3;
-                    }
-                    if (c_tab + c_main < best) { best = c_tab + c_main; best_l = l; dict_cost[kv.first] = best / 2200.0; dict_tab[kv.first] = c_tab / 2200.0; }
-                }
-                if (const char *fl = std::getenv("IMC_FORCE_LEVEL")) {   // experiments only: pin the dictionary level index
-                    const int l = std::atoi(fl);
-                    const imc_obs *o0 = chunks[kv.second[0]];
-                    const bool hybrid = mfma_blocked && (wide || (kc->zip4 && g.blocked_variant >= 4)) && !o0->wide_raw;
-                    const int amax_forced = hybrid ? HYBRID_MAX_ALPHABET : a_max;
-                    if (l >= 0 && l < imc::kNumLevels && o0->alphabet[l] <= amax_forced && !(hybrid && (wide || kc->blocked_lds(o0->alphabet[l]) > LDS_BUDGET) && kc->zip4_lds(o0->alphabet[l], 0) > LDS_BUDGET) && o0->alphabet[l] > o0->nsym && o0->d_tok[l] &&
-                        (hybrid ? !o0->tok_count[l].empty() : !o0->wide[l])) best_l = l;
-                }
-                dict_level[kv.first] = best_l;
-                if (wide && best_l < 0) wide_ok = false;
-            }
-        }
-        chunk_group.assign(n_chunks, -1);
-        for (int f = 0; f < n_chunks; ++f) {
-            const imc_obs *o = chunks[f];
-            int level = -1;
-            if (g.compression && o->dict && o->nsym == S) {
-                auto it = dict_level.find(o->dict.get());
-                if (it != dict_level.end()) level = it->second;
-            }
-            int gi = -1;
-            for (size_t q = 0; q < p->groups.size(); ++q) {
-                Group &gr = p->groups[q];
-                if (level < 0 ? !gr.tokens : (gr.tokens && gr.level == level && gr.dict == o->dict)) gi = (int)q;
-            }
-            if (gi < 0) {
-                Group gr;
-                gr.tokens = level >= 0;
-                gr.level = level;
-                gr.A = S;
-                if (gr.tokens) { gr.dict = o->dict; gr.A = o->alphabet[level]; }
-                // an alphabet beyond LDS can only have been chosen for the hybrid-table kernel
-                global_tentative.push_back(gr.tokens && mfma_blocked && (wide || kc->blocked_lds(gr.A) > LDS_BUDGET || o->wide[level]));
-                if (gr.tokens) { gr.model_us = dict_cost[o->dict.get()]; gr.model_tab_us = dict_tab[o->dict.get()]; }
-                gr.blk.wide_tokens = gr.tokens && o->wide[level];
-                p->groups.push_back(std::move(gr));
-                gi = (int)p->groups.size() - 1;
-            }
-            p->groups[gi].chunks.push_back(f);
-            chunk_group[f] = gi;
-        }
-    }
-
-    void choose_segment_lengths()
-    {
-        // ---- segment length per group ----
-        for (size_t q = 0; q < p->groups.size(); ++q) {
-            Group &gr = p->groups[q];
-            const bool global = global_tentative[q] != 0;
-            bool matvec = false;    // (chain plans) granted by the cost comparison below, revoked if a forced segment length cuts a chunk
-            bool blocked = false;   // (other plans) the register-blocked scan instead of the vector kernel
-            std::vector<size_t> lens;
-            for (int f : gr.chunks) lens.push_back(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L);
-            if (chain_tentative) {
-                // every segment costs N^3 per step whatever the split (one workgroup = one CU's worth of LDS), so
-                // one equal-length segment per CU is both balanced and the fewest operators for the stitch
-                size_t total = 0;
-                for (size_t L : lens) total += L;
-                const size_t per_cu = std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / kc->big_lds, (size_t)32 / (size_t)kc->G));
-                const size_t target = std::max<size_t>(1, (size_t)g.cus * per_cu / ((size_t)B * kc->big_nslab));
-                gr.seglen = std::max<size_t>(16, round_up((total + target - 1) / target, 16));
-                // Chunks are cut one by one (ceil(L / seglen) segments each): with several chunks the sum can exceed the
-                // target by a few segments - and one segment more than the machine holds is a second ROUND of workgroups,
-                // twice the time (measured round 3 at 150 states, 3 x 3e6 columns: 129 segments for 128 slots, 201 ms
-                // against 103).  Lengthen the segments until the launch fits.
-                {
-                    auto count = [&](size_t sl) { size_t c = 0; for (size_t L : lens) c += (L + sl - 1) / sl; return c; };
-                    size_t nonempty = 0;
-                    for (size_t L : lens) nonempty += L > 0;
-                    if (nonempty <= target)            // (more chunks than slots: rounds are unavoidable)
-                        for (int it = 0; it < 65536 && count(gr.seglen) > target; ++it) gr.seglen += 16;
-                }
-                // ... unless there are so many (chunk, parameter set) chains that no chunk needs splitting: then
-                // the mat-vec chain kernel streams NP^2 doubles per step instead of a GEMM (measured at N=150, 64 x 32
-                // chains: 8900 cycles per step per CU, i.e. ~12 TB/s of operator reads over the whole chip)
-                size_t lmax = 0;
-                for (size_t L : lens) lmax = std::max(lmax, L);
-                const double np2 = (double)kc->NP * kc->NP, per_cu_steps = (double)total * B / (double)g.cus;
-                const double cost_vec = std::max((double)lmax * (np2 / 4.5 + 1500.0), per_cu_steps * matvec_step_cycles(np2, gr.A));
-                double cost_gemm = std::max(16.0, per_cu_steps) * gemm_cu_step_cycles(kc->NP);
-                if (g.rank1_handoff && !g.seg_override && gr.seglen >= R1_MIN_SEGLEN) {   // GEMM heads + mat-vec tails
-                    const HandoffEstimate he = estimate_handoff((double)gr.seglen, std::max(1.0, (double)total / gr.seglen), B,
-                                                                (double)handoff_head(gr), kc->NP, kc->big_nslab, gr.A, g.cus);
-                    if (he.m) cost_gemm = std::min(cost_gemm, he.cycles);
-                }
-                if (std::getenv("IMC_DEBUG"))
-                    std::fprintf(stderr, "[imc] plan: GEMM chain seg %zu cost %.3g cycles; mat-vec chain cost %.3g cycles\n",
-                                 gr.seglen, cost_gemm, cost_vec);
-                // (no chunk longer than a segment: there would be no operator segments anyway)
-                if (!op_mode && (g.kernel_pref == 1 || (g.kernel_pref == 0 && (cost_vec < cost_gemm || lmax <= gr.seglen)))) {
-                    matvec = true;
-                    gr.seglen = std::max<size_t>(16, round_up(lmax, 16));
-                }
-                // (build_plan's comparison: the level estimate's table part + this, the refined estimate of the chain that was taken)
-                if (gr.tokens) gr.model_us = gr.model_tab_us + (matvec ? cost_vec : cost_gemm) / 2200.0;
-            } else {
-                // vector kernel (one vector per lane group) ...
-                double cost_vec = 0.0;
-                size_t seg_vec;
-                if (gr.tokens) {
-                    // LDS-bound: a workgroup of ZWAVES wavefronts serialises on one CU's LDS
-                    const double lds_cycles = ((double)kc->R * kc->NP / 2 + kc->NP / 2.0) * 4.0 + kc->R * 6.0 + 40.0;
-                    seg_vec = choose_seglen(lens, N, B, kc->VPW, (double)g.cus * ZWAVES, lds_cycles * ZWAVES, &cost_vec);   // measured: 4600 cycles per wavefront-step at N=20
-                } else {
-                    // VALU-bound, minw wavefronts share a SIMD: measured 555 cycles per wavefront-column per SIMD at N=20
-                    seg_vec = choose_seglen(lens, N, B, kc->VPW, (double)g.cus * 4.0 * kc->minw,
-                                            kc->minw * 1.7 * (4.0 * kc->R * kc->NP + 16.0), &cost_vec);
-                }
-                gr.seglen = seg_vec;
-                // ... or the register-blocked kernel (one operator per 16-lane row): fill every row of the machine
-                // once; first segments waste 1 - 1/N of their row, which the cost comparison accounts for
-                if ((kc->zip2 || (wide && global)) && g.kernel_pref != 1 && (global || kc->blocked_lds(gr.A) <= LDS_BUDGET) && (gr.tokens || (S == gr.A && S <= imc::kByteAlphabet))) {
-                    const int SL = kc->z4_slots(), WV = kc->z4_waves;   // segments / wavefronts per workgroup
-                    size_t total = 0;
-                    for (size_t L : lens) total += L;
-                    // Up to 12 states the global-table kernel needs 124 registers and no LDS to speak of: TWO workgroups share a
-                    // CU (four wavefronts per SIMD), i.e. the machine has twice the rows, each step taking ~1.85x as long
-                    // (measured at 10 states, 100 x 1e6 columns: 500 workgroups of 44-token segments 102 us, 200 workgroups
-                    // of 104-token segments 113 us).
-                    const bool two_per_cu = global && kc->use3() && kc->NP <= 12 &&
-                                            z4_streamed((double)B * (gr.A + 1) * kc->tok_doubles * 8.0, B);
-                    const double rows = (double)g.cus * SL * (two_per_cu ? 2.0 : 1.0);
-                    const double rb = kc->NP / 4.0;
-                    // per wavefront-step (4 segments): DPP/VALU form measured ~2900 at N=20; the MFMA form issues
-                    // (NP/4)^3 v_mfma_f64_4x4x4 at ~25.5 cycles each with two wavefronts per SIMD and nothing else
-                    const double step_cycles = (mfma() ? 25.5 * rb * rb * rb * 0.55 : 5.8 * rb * rb * kc->NP) * (two_per_cu ? 1.85 : 1.0);
-                    size_t seg_blk = 16;
-                    double slots = 0.0, cost_blk = 1e300;
-                    // a workgroup takes 32 consecutive segments of ONE chunk: rows are allocated per chunk in 32s
-                    // (... except chunks that are ONE segment: those are packed, a row each - make_units)
-                    const bool can_pack = mfma() && !op_mode;
-                    auto rows_used = [&](size_t sg) {
-                        double r = 0.0, singles = 0.0;
-                        for (size_t L : lens) {
-                            if (!L) continue;
-                            const double nseg = std::ceil((double)L / (double)sg);
-                            if (nseg <= 1.0 && can_pack) singles += 1.0;
-                            else r += std::ceil(nseg / SL) * SL;
-                        }
-                        return r + std::ceil(singles / SL) * SL;
-                    };
-                    // Candidates: fill the machine's rows `rounds` times - or, when chunks x parameter sets alone need more
-                    // rounds than that (every chunk takes at least one workgroup of 32 rows per parameter set: 100 chunks x 64
-                    // sets = 25 rounds), cut every chunk into u workgroups' worth of segments.  (Round 2 only had the first
-                    // family, up to 16 rounds; beyond that its search ran into its iteration limit and returned segments of
-                    // thousands of tokens with two of a workgroup's 32 rows in use: 100 x 1e6 columns x 64 proposals took
-                    // 446 us per proposal at 10 states against 64 us at 8 proposals.)
-                    size_t lmax = 0;
-                    for (size_t L : lens) lmax = std::max(lmax, L);
-                    std::vector<size_t> cands;
-                    for (int rounds = 1; rounds <= 16; ++rounds) {
-                        const double target = std::max((double)SL, std::floor(rows * rounds / B));
-                        // (the blocked kernels take segments of any multiple of 4 tokens - dword-aligned 16-byte
-                        // loads - so the machine's rows can be filled to within a per cent, not to within 16 tokens)
-                        size_t sg = std::max<size_t>(16, round_up((size_t)std::ceil((double)total / target), Z2GRAN));
-                        int it = 0;
-                        for (; it < 1024 && rows_used(sg) > target && sg < lmax + 16; ++it) sg += Z2GRAN;
-                        if (rows_used(sg) > target) continue;                    // this many rounds cannot hold the launch
-                        cands.push_back(sg);
-                    }
-                    for (size_t u = 1; u <= 8; ++u)
-                        cands.push_back(std::max<size_t>(16, round_up((lmax + SL * u - 1) / (SL * u), Z2GRAN)));
-                    // ... and, for mixes of one long chunk with many short ones, the same for the MEDIAN chunk plus a few fixed
-                    // short lengths: both families above follow the longest chunk, and when the short chunks alone need more
-                    // than 16 rounds (each takes a workgroup per parameter set whatever the segment length) every candidate
-                    // was hundreds of tokens long - 500 chunks of 1e5 columns beside one of 2.5e7, 8 sets, 20 states: 432-token
-                    // segments, two of a workgroup's 32 rows in use on 4000 workgroups, 5.7 ms against 2.5.
-                    {
-                        std::vector<size_t> sorted(lens);
-                        std::sort(sorted.begin(), sorted.end());
-                        const size_t med = sorted[sorted.size() / 2];
-                        for (size_t u = 1; u <= 4; ++u)
-                            cands.push_back(std::max<size_t>(16, round_up((med + SL * u - 1) / (SL * u), Z2GRAN)));
-                        for (size_t fixed_len : {16, 32, 48, 64, 96, 128, 192}) cands.push_back(fixed_len);
-                        // whole chunks as single segments (packed 32 to a workgroup): the length of the median, the 90 % and the
-                        // longest chunk
-                        if (can_pack)
-                            for (size_t qi : {sorted.size() / 2, sorted.size() * 9 / 10, sorted.size() - 1})
-                                cands.push_back(std::max<size_t>(16, round_up(sorted[qi], Z2GRAN)));
-                    }
-                    for (size_t sg : cands) {
-                        // per round of workgroups: the main loop, plus the table rebuild and the 5-level in-kernel fold
-                        // (table: the VALU form builds token by token; the MFMA form one dictionary depth per pass,
-                        // ~10 depths; with the hybrid table a workgroup only copies its hot set from L2)
-                        const double table = !mfma() ? (double)(gr.A - S) * (400.0 + (double)kc->NP * kc->NP * kc->NP / 64.0)
-                                             : global ? 9000.0 : 2600.0 * std::min(12.0, (double)(gr.A - S));
-                        const double fixed = table + 5.0 * (WV / 4.0) * step_cycles;
-                        // A segment length that is not a multiple of 16 ends in a MASKED block (the pipeline is re-primed per
-                        // run of it: ~3.5 us; measured at 10 states, 100 x 1e6 columns: 48-token segments 101.9 us, 44-token
-                        // ones 109.6) - so the next multiple of 16 is priced beside the exact fit.
-                        for (size_t cand : {sg, round_up(sg, 16)}) {
-                            const double u = rows_used(cand);
-                            double c = std::ceil(u * B / rows) * ((double)cand * (WV / 4.0) * step_cycles + fixed + (cand % 16 ? 7700.0 : 0.0));
-                            // (every chunk a single packed segment: measured 10 % behind the best split where the model has a tie)
-                            if (can_pack && cand >= lmax) c *= 1.15;
-                            if (c < cost_blk) { cost_blk = c; seg_blk = cand; slots = u; }
-                        }
-                    }
-                    if (std::getenv("IMC_DEBUG"))
-                        std::fprintf(stderr, "[imc] plan: vector kernel seg %zu cost %.3g cycles; blocked kernel seg %zu slots %.0f cost %.3g cycles\n",
-                                     seg_vec, cost_vec, seg_blk, slots, cost_blk);
-                    const bool vec_fits = !gr.tokens || kc->zip_lds(gr.A) <= LDS_BUDGET;   // the table may only fit the blocked kernel
-                    if (g.kernel_pref == 2 || cost_blk < cost_vec || !vec_fits || global) { blocked = true; gr.seglen = seg_blk; }
-                }
-                if (gr.tokens && !blocked) gr.model_us = gr.model_tab_us + cost_vec / 2200.0;   // (build_plan's comparison)
-            }
-            if (g.seg_override) gr.seglen = round_up(std::max<size_t>(g.seg_override, 16), 16);   // tests: force stitching
-            if (matvec)
-                for (size_t L : lens) matvec = matvec && L <= gr.seglen && !op_mode;
-            // rank-one hand-off: worth a test once segments are much longer than the HMM's memory (tens of thousands
-            // of columns); a quarter of the segment on the GEMM chain, then the certified test
-            if (chain_tentative && !matvec && g.rank1_handoff && gr.seglen >= R1_MIN_SEGLEN) {
-                // head: ~R1_HEAD_COLUMNS alignment columns on the GEMM chain (the HMM's memory is a property of the
-                // model, not of the segmentation).  The tails then cost a mat-vec per step, so MORE, shorter
-                // segments pay: m times the segments = m rounds of heads, tails 1/m as long.  Pick m by the model;
-                // if the test fails at run time the GEMM chain does the same total work as with m = 1.
-                double cols = 0.0, toks = 0.0;
-                for (int f : gr.chunks) { cols += (double)chunks[f]->L; toks += (double)(gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L); }
-                const double span = toks > 0.0 ? cols / toks : 1.0;
-                const size_t head = handoff_head(gr);
-                const double nseg = std::max(1.0, toks / (double)gr.seglen);
-                if (g.seg_override) {                 // tests: one checkpoint at a quarter of the forced segment length
-                    if (gr.seglen >= 4 * R1_MIN_HEAD) {
-                        gr.chain.rank1 = true;
-                        gr.chain.checkpoints.assign(1, (int)round_up(gr.seglen / 4, 16));
-                    }
-                } else {
-                    const int best_m = estimate_handoff((double)gr.seglen, nseg, B, (double)head, kc->NP, kc->big_nslab, gr.A, g.cus).m;
-                    if (best_m) {
-                        gr.chain.rank1 = true;
-                        gr.seglen = std::max<size_t>(16, round_up(gr.seglen / best_m, 16));
-                        // checkpoints: from ~8k alignment columns, each ~1.125x the previous (multiples of 16 tokens)
-                        // up to ~100k columns - where the operators of the measured models collapse; a failing check
-                        // is a quick reject and costs two near-empty launches - then 1.5x, while at least an eighth
-                        // of the segment would still be left for the mat-vec chain
-                        size_t c = round_up(std::max<size_t>(64, (size_t)(R1_HEAD_MIN_COLUMNS / span)), 16);
-                        while ((int)gr.chain.checkpoints.size() < R1_MAX_ROUNDS && c + gr.seglen / 8 < gr.seglen) {
-                            gr.chain.checkpoints.push_back((int)c);
-                            const size_t step = (double)c * span < R1_DENSE_COLUMNS ? c / 8 : c / 2;
-                            c = round_up(c + std::max<size_t>(16, step), 16);
-                        }
-                        if (gr.chain.checkpoints.empty()) gr.chain.rank1 = false;
-                    }
-                }
-            }
-            // the one statement of what the group is (a global-table level is always taken by the blocked scan)
-            gr.kind = chain_tentative ? (matvec ? Group::Kind::MatVecChain : Group::Kind::GemmChain)
-                      : blocked       ? (global ? Group::Kind::BlockedGlobal : Group::Kind::BlockedLds)
-                      : gr.tokens     ? Group::Kind::TokenVector
-                                      : Group::Kind::ColumnVector;
-        }
-    }
 
     void cut_segments()
     {
@@ -1612,7 +1088,7 @@ struct PlanBuilder {
                     for (size_t z = 0; z < chunks[f]->tok_count[gr.level].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[gr.level][z];
                 const std::vector<uint16_t> ids = imc::hot_order(cnt);
                 const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
-                bl.stream_table = wide || z4_streamed(tables, B);
+                bl.stream_table = wide || imc::z4_streamed(opt, tables, B);
                 bl.n_hot = bl.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
                 bl.hot.assign(ids.begin(), ids.begin() + bl.n_hot);
                 bl.phases = imc::xcd_phases(B, (int)bl.blocks.size());
@@ -1678,14 +1154,42 @@ struct PlanBuilder {
     }
 };
 
+// The planner's facts of a call's chunks; dictionaries are numbered in the order of their first appearance.
+void gather_facts(const imc_obs *const *chunks, int n_chunks, std::vector<imc::ChunkFacts> &cf, std::vector<imc::DictFacts> &df,
+                  std::vector<std::shared_ptr<DictDev>> &dict_of)
+{
+    cf.resize(n_chunks);
+    for (int f = 0; f < n_chunks; ++f) {
+        const imc_obs *o = chunks[f];
+        imc::ChunkFacts &c = cf[f];
+        c.L = o->L; c.nsym = o->nsym; c.wide_raw = o->wide_raw;
+        if (o->dict) {
+            c.dict = (int)(std::find(dict_of.begin(), dict_of.end(), o->dict) - dict_of.begin());
+            if (c.dict == (int)dict_of.size()) { dict_of.push_back(o->dict); df.push_back(imc::DictFacts{&o->dict->depth}); }
+        }
+        for (int l = 0; l < imc::kNumLevels; ++l)
+            c.level[l] = imc::ChunkFacts::Level{o->d_tok[l] != nullptr, o->wide[l], o->ntok[l], o->alphabet[l], &o->tok_count[l]};
+    }
+}
+
 int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, bool op_mode, Plan **out)
 {
+    // What the planner reads of the context and the environment.  The three variables are read here, once per call, not
+    // at context creation: tests set IMC_FORCE_LEVEL between calls.
+    const char *force_level = std::getenv("IMC_FORCE_LEVEL");   // (experiments / tests)
+    imc::PlanOptions opt;
+    opt.cus = g.cus; opt.compression = g.compression; opt.kernel_pref = g.kernel_pref; opt.blocked_variant = g.blocked_variant;
+    opt.wide_blocked = g.wide_blocked; opt.z4_stream = g.z4_stream; opt.xcd_affine = g.xcd_affine; opt.table_pairs = g.table_pairs;
+    opt.rank1_handoff = g.rank1_handoff; opt.seg_override = g.seg_override;
+    opt.force_level = force_level ? std::atoi(force_level) : -1;
+    opt.debug = std::getenv("IMC_DEBUG") != nullptr;
+    opt.debug_levels = std::getenv("IMC_DEBUG_LEVELS") != nullptr;
     std::vector<uint64_t> key;
-    key.reserve(n_chunks + 5);
+    key.reserve(n_chunks + 6);
     for (int f = 0; f < n_chunks; ++f) key.push_back(chunks[f]->id);
     key.push_back((uint64_t)N); key.push_back((uint64_t)S); key.push_back((uint64_t)B);
     key.push_back((uint64_t)g.seg_override); key.push_back((uint64_t)(g.compression * 4 + g.kernel_pref + (op_mode ? 64 : 0) + g.blocked_variant * 128 + (g.z4_stream + 1) * 1024 + (g.wide_blocked + 1) * 4096));
-    { const char *fl = std::getenv("IMC_FORCE_LEVEL"); key.push_back(fl ? (uint64_t)(std::atoi(fl) + 1) : 0u); }   // (experiments / tests)
+    key.push_back(force_level ? (uint64_t)(opt.force_level + 1) : 0u);
     for (auto it = g_plans.begin(); it != g_plans.end(); ++it) {
         if ((*it)->key == key) {
             g_plans.splice(g_plans.begin(), g_plans, it);
@@ -1693,82 +1197,42 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
             return IMC_OK;
         }
     }
-    // 24 < N <= 64: the GEMM-chain kernels beat the vector kernels by 5-100x when chunks are long enough to be
-    // cut into many operator segments; short-chunk / many-theta launches keep the vector kernels
-    bool prefer_gemm = g.kernel_pref == 2;
-    if (g.kernel_pref == 0 && N > 24 && N <= 64 && n_chunks > 0) {
-        double total = 0.0;
-        for (int f = 0; f < n_chunks; ++f) total += (double)chunks[f]->L;
-        bool tokens = g.compression != 0;   // on the raw column stream the vector kernel still wins up to N=40 (no padding to 16s)
-        for (int f = 0; f < n_chunks; ++f) tokens = tokens && chunks[f]->dict && chunks[f]->nsym == S;
-        // (round 3: 1e6 columns in all and 5e3 per chunk on average - it used to be 2e5 per chunk, and 100 chunks of 1e5
-        // columns then ran on the LDS-table vector kernels at 4-9x the GEMM chain's time, profiles/r03_e_calib_big.txt)
-        prefer_gemm = total >= 1.0e6 && total / n_chunks >= 5.0e3 && (tokens || N > 40);
-    }
+    std::vector<imc::ChunkFacts> cf;
+    std::vector<imc::DictFacts> df;
+    std::vector<std::shared_ptr<DictDev>> dict_of;
+    gather_facts(chunks, n_chunks, cf, df, dict_of);
 
-    KernelChoice *kc = choose_kernel(N, prefer_gemm);
+    KernelChoice *kc = choose_kernel(N, imc::prefer_gemm(opt, cf, N, S));
     if (!kc) return fail(IMC_ERR_ARG, "N exceeds the largest built kernel (" + std::to_string(IMC_MAX_N) + ")");
-    if (kc->R == 0 && (kc->G == 7 || kc->G == 9) && kc + 1 < kChoices + sizeof(kChoices) / sizeof(kChoices[0])) {
-        // The odd tile counts (NP = 112, 144) pad less, but run one workgroup per segment: their base segments are
-        // half as long as the next shape's (two column slabs per segment), which on mid-sized inputs can fall below
-        // what the rank-one hand-off needs.  Take the next shape when it can hand off and this one cannot.
-        double toks = 0.0, cols = 0.0;
-        for (int f = 0; f < n_chunks; ++f) {
-            size_t nt = chunks[f]->L;
-            if (g.compression && chunks[f]->dict && chunks[f]->nsym == S)
-                for (int l = 0; l < imc::kNumLevels; ++l)
-                    if (chunks[f]->d_tok[l]) nt = std::min(nt, chunks[f]->ntok[l]);
-            toks += (double)nt;
-            cols += (double)chunks[f]->L;
-        }
-        const double head = std::max<double>((double)R1_MIN_HEAD, R1_HEAD_COLUMNS / std::max(1.0, cols / std::max(1.0, toks)));
-        auto eligible = [&](const KernelChoice *k) {
-            const double per_cu = (double)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / k->big_lds, (size_t)32 / (size_t)k->G));
-            const double target = std::max(1.0, (double)g.cus * per_cu / ((double)B * k->big_nslab));
-            const double seglen = toks / target;
-            return seglen >= (double)R1_MIN_SEGLEN && seglen >= 2.0 * head;
-        };
-        if (g.rank1_handoff && !g.seg_override && !eligible(kc) && eligible(kc + 1)) kc = kc + 1;
-    }
-    // The first two phases (groups, dictionary levels, segment lengths: host arithmetic only) for a kernel family.
-    auto start = [&](PlanBuilder &b, KernelChoice *k, bool wide) {
-        b.chunks = chunks; b.n_chunks = n_chunks; b.N = N; b.S = S; b.B = B; b.op_mode = op_mode; b.kc = k; b.wide = wide;
-        b.p = std::make_unique<Plan>();
-        b.p->key = key; b.p->kc = k; b.p->wide = wide; b.p->N = N; b.p->S = S; b.p->B = B; b.p->n_chunks = n_chunks;
-        b.assign_groups();
-        b.choose_segment_lengths();
-    };
-    PlanBuilder pb;
-    start(pb, kc, false);
-    // 25-32 states, automatic mode: the blocked scan (k_zpropagate4<7 | 8>) is one more candidate for the chunks that have a
-    // dictionary - a second plan on the vector kernels' entry, whose dictionary groups take the scan.  It must take EVERY
-    // dictionary of the call, and, where today's plan is the GEMM chain's, every chunk that has columns: raw streams and
-    // uncompressed chunks stay on the kernels they have.  A plan that runs all of its dictionary groups on the mat-vec chain
-    // (many short chains) keeps that choice.  Otherwise the two plans' estimates for the dictionary groups decide - the
-    // scan's is the blocked kernels' own model (assign_groups), with four wavefronts and 16 segments per workgroup.
+    if (kc->R == 0 && (kc->G == 7 || kc->G == 9) && kc + 1 < kChoices + sizeof(kChoices) / sizeof(kChoices[0]) &&
+        imc::next_shape_hands_off(opt, *kc, *(kc + 1), cf, S, B))
+        kc = kc + 1;
+    imc::PlanDecision dec = imc::decide_groups(opt, *kc, false, cf, df, N, S, B, op_mode);
+    // 25-32 states, automatic mode: the blocked scan is one more candidate (imc::wide_plan_wins)
+    bool wide = false;
     KernelChoice *kw = (N > 24 && N <= 32) ? choose_kernel(N, false) : nullptr;
-    if (kw && kw->wide_blocked && g.wide_blocked != 0 && g.compression == 1 && g.kernel_pref == 0 && n_chunks > 0) {
-        PlanBuilder wb;
-        start(wb, kw, true);
-        bool any = false, all = wb.wide_ok;
-        double us_wide = 0.0, us_base = 0.0;
-        for (const Group &gr : wb.p->groups) {
-            bool cols = false;
-            for (int f : gr.chunks) cols = cols || chunks[f]->L > 0;
-            if (gr.global_table()) { any = true; us_wide += gr.model_us; }
-            else if (cols && kc->R == 0) all = false;
-        }
-        bool base_matvec = false, base_other = false;
-        for (const Group &gr : pb.p->groups)
-            if (gr.tokens) { us_base += gr.model_us; (gr.kind == Group::Kind::MatVecChain ? base_matvec : base_other) = true; }
-        base_matvec = base_matvec && !base_other;
-        if (std::getenv("IMC_DEBUG"))
-            std::fprintf(stderr, "[imc] plan: blocked scan at %d states %s, model %.1f us; present kernels %.1f us%s\n", N,
-                         any && all ? "possible" : "not possible", us_wide, us_base, base_matvec ? " (mat-vec chain)" : "");
-        if (any && all && (g.wide_blocked == 1 || (!base_matvec && us_wide < us_base))) {
-            pb = std::move(wb);
+    if (kw && kw->wide_blocked && opt.wide_blocked != 0 && opt.compression == 1 && opt.kernel_pref == 0 && n_chunks > 0) {
+        imc::PlanDecision wdec = imc::decide_groups(opt, *kw, true, cf, df, N, S, B, op_mode);
+        if (imc::wide_plan_wins(opt, dec, kc->R == 0, wdec, cf, N)) {
+            dec = std::move(wdec);
             kc = kw;
+            wide = true;
         }
+    }
+    PlanBuilder pb;
+    pb.chunks = chunks; pb.n_chunks = n_chunks; pb.N = N; pb.S = S; pb.B = B; pb.op_mode = op_mode; pb.opt = opt; pb.kc = kc; pb.wide = wide;
+    pb.p = std::make_unique<Plan>();
+    pb.p->key = key; pb.p->kc = kc; pb.p->wide = wide; pb.p->N = N; pb.p->S = S; pb.p->B = B; pb.p->n_chunks = n_chunks;
+    pb.chunk_group = std::move(dec.chunk_group);
+    for (imc::GroupDecision &gd : dec.groups) {
+        Group gr;
+        gr.kind = gd.kind; gr.tokens = gd.tokens; gr.level = gd.level; gr.A = gd.A;
+        if (gd.dict >= 0) gr.dict = dict_of[gd.dict];
+        gr.chunks = std::move(gd.chunks);
+        gr.seglen = gd.seglen; gr.model_us = gd.model_us; gr.model_tab_us = gd.model_tab_us;
+        gr.blk.wide_tokens = gd.wide_tokens;
+        gr.chain.rank1 = gd.rank1; gr.chain.checkpoints = std::move(gd.checkpoints);
+        pb.p->groups.push_back(std::move(gr));
     }
     pb.cut_segments();
     if (int rc = pb.make_units()) return rc;
@@ -1891,9 +1355,9 @@ int Launch::fetch_params()
                 kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
     // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
     // columns): each of its few workgroups fetches the parameter set itself
-    direct_params = g.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3() && pbytes <= STAGE_KERNEL_MAX_BYTES &&
+    direct_params = g.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3(g.blocked_variant) && pbytes <= STAGE_KERNEL_MAX_BYTES &&
                     only->blk.blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
-                    ((kc->blocked_lds(only->A) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
+                    ((kc->blocked_lds(only->A, g.blocked_variant) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
     if (fuse_head || direct_params) {
         // (nothing to enqueue here)
     } else if (pbytes <= STAGE_KERNEL_MAX_BYTES) {
@@ -2020,7 +1484,7 @@ BigArgs Launch::blocked_args(const Group &gr)
     ba.n_group_segs = (uint32_t)gr.blk.blocks.size();
     ba.tab_order = gr.blk.d_tab_order.get(); ba.tab_lvl = gr.blk.d_tab_lvl.get(); ba.tab_nlvl = gr.blk.tab_nlvl;
     ba.hot = gr.blk.d_hot.get(); ba.n_hot = gr.blk.n_hot; ba.tab_desc = gr.blk.d_tab_desc.get();
-    if (gr.blk.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (p->kc->use3() || p->wide)) {
+    if (gr.blk.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (p->kc->use3(g.blocked_variant) || p->wide)) {
         ba.tail = gr.blk.d_tails.get(); ba.tailX = gr.blk.d_tailX.get(); ba.tailE = gr.blk.d_tailE.get(); ba.tail_arrive = gr.blk.d_tail_arrive.get();
         ba.tail_out = out; ba.tail_stride = gr.blk.tail_stride;
         tail_used = true;
@@ -2112,10 +1576,10 @@ int Launch::zip4(const Group &gr)
 int Launch::zip32(const Group &gr)
 {
     BigArgs ba = blocked_args(gr);
-    const bool v3 = kc->use3();
+    const bool v3 = kc->use3(g.blocked_variant);
     void (*scan)(BigArgs) = v3 ? kc->zip3 : kc->zip2;
     if (int rc = allow_lds_budget(scan)) return rc;
-    size_t lds3 = kc->blocked_lds(gr.A);
+    size_t lds3 = kc->blocked_lds(gr.A, g.blocked_variant);
     if (direct_params) { ba.params_src = p->h_params_dev[p->slot]; lds3 = ((lds3 + 15) & ~(size_t)15) + p->pstride * 8; }
     hipLaunchKernelGGL(scan, dim3(ba.n_group_segs, (unsigned)p->B), dim3(Z2WAVES * 64), lds3, stream, ba);
     note(std::string(v3 ? "k_zpropagate3<" : "k_zpropagate2<") + std::to_string(kc->NP / 4) + ">" + stream_tag(gr));

@@ -201,7 +201,8 @@ int imc_dictionary_reset(void);
 int imc_profile_enable(int on);
 int imc_profile_read(double *ms_propagate, double *ms_stitch, uint64_t *n_propagate, uint64_t *n_stitch);
 /* Rank-one hand-off of the GEMM-chain kernels (long segments, N > 24): a segment's transfer operator is tested at a
- * fixed schedule of checkpoints (token counts, from ~8k alignment columns, each ~1.25x the previous); at the first one
+ * fixed schedule of checkpoints (token counts, from ~8k alignment columns, each ~1.125x the previous up to ~1e5 columns,
+ * then ~1.5x); at the first one
  * where every column has collapsed onto one direction (component-wise, within 2^-42) the rest of the segment
  * propagates that vector instead of the N x N operator.  The decision is taken per segment from the data of the
  * evaluation alone - no state is carried between calls, so identical calls return identical bits.  For the last
