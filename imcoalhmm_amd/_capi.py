@@ -37,6 +37,8 @@ SIGNATURES = [
     ("imc_obs_create", ctypes.c_int, [_u8p, ctypes.c_size_t, ctypes.c_int, _vpp]),
     ("imc_obs_create_i32", ctypes.c_int, [_i32p, ctypes.c_size_t, ctypes.c_int, _vpp]),
     ("imc_obs_create_from_text", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, _vpp]),
+    ("imc_obs_create_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _vpp]),
     ("imc_read_observations", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_int, _u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     ("imc_write_cache", ctypes.c_int, [ctypes.c_char_p, _u8p, ctypes.c_size_t, ctypes.c_int]),
@@ -50,6 +52,8 @@ SIGNATURES = [
     ("imc_obs_tokens", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
       ctypes.POINTER(ctypes.c_int)]),
+    ("imc_obs_token_counts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
     ("imc_obs_free", ctypes.c_int, [ctypes.c_void_p]),
     ("imc_forward", ctypes.c_int, [_vpp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),
     ("imc_forward_batch", ctypes.c_int,
@@ -65,6 +69,7 @@ SIGNATURES = [
     ("imc_set_segment_length", ctypes.c_int, [ctypes.c_size_t]),
     ("imc_set_compression", ctypes.c_int, [ctypes.c_int]),
     ("imc_dictionary_reset", ctypes.c_int, []),
+    ("imc_set_device_encoding", ctypes.c_int, [ctypes.c_int]),
     ("imc_profile_enable", ctypes.c_int, [ctypes.c_int]),
     ("imc_profile_read", ctypes.c_int, [_dp, _dp, _u64p, _u64p]),
     ("imc_last_rank1", ctypes.c_int, [_u64p, _u64p]),

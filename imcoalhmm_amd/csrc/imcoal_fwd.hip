@@ -51,6 +51,7 @@
 #include "kernels_zip3.hpp"
 #include "kernels_zip4.hpp"
 #include "pair_dict.hpp"
+#include "kernels_encode.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
 #include "model_host.hpp"
@@ -155,6 +156,9 @@ struct Ctx {
                               // workgroups of 20 states, where the chain's twenty parallel wavefronts win), 2 = wherever possible, 0 = never (IMC_FUSE_TAIL)
     bool fuse_head = true;    // IMC_FUSE_HEAD=0: k_stage_params + k_z4_raw as launches of their own (A/B measurements)
     bool pack_table = true;   // IMC_PACK_TABLE=0: the mat-vec chain reads the padded table (A/B measurements)
+    int device_encode = -1;   // token streams of new / recompressed chunks: 0 = encoded on the host (imc::encode_levels), 1 = on the
+                              // device from the symbols already there (kernels_encode.hpp; the same tokens).  -1: not set yet -
+                              // IMC_DEVICE_ENCODE at start-up, else 0 (imc_set_device_encoding)
     bool guard = false;       // IMC_GUARD=1: every device buffer ends flush against an unmapped guard range (dev_alloc)
     bool use_graphs = false;  // IMC_GRAPH=1: replay each plan's launch sequence as a hipGraph (measured: no gain, the
                               // per-evaluation latency is kernel time + kernel boundaries, not host launch cost)
@@ -209,6 +213,10 @@ int ensure_ctx()
     if (const char *ft = std::getenv("IMC_FUSE_TAIL")) g.fuse_tail = std::max(0, std::min(2, std::atoi(ft)));
     if (const char *xa = std::getenv("IMC_XCD_AFFINE")) g.xcd_affine = std::atoi(xa) != 0;
     if (const char *wb = std::getenv("IMC_WIDE_BLOCKED")) { const int v = std::atoi(wb); if (v >= -1 && v <= 1) g.wide_blocked = v; }
+    if (g.device_encode < 0) {
+        const char *de = std::getenv("IMC_DEVICE_ENCODE");
+        g.device_encode = de && std::atoi(de) == 1 ? 1 : 0;
+    }
     if (const char *zs = std::getenv("IMC_Z4_STREAM")) { const int v = std::atoi(zs); if (v >= -1 && v <= 1) g.z4_stream = v; }
     g.pid = me;
     g.ready = true;
@@ -459,15 +467,181 @@ int install_encoding(imc_obs *o, const std::shared_ptr<DictDev> &dd, const imc::
     return IMC_OK;
 }
 
+// ---- encoding on the device (kernels_encode.hpp) ------------------------------------------------------
+// The token streams of K chunks of one alphabet from their raw symbols (d_sym), with dd's dictionary: what
+// imc::encode_levels + install_encoding give, level for level and bit for bit, without the symbols leaving the device.
+// g_mu held, context ready; the chunks hold no token streams (new, or after release_tokens).  Every launch and copy is on
+// g.stream.  The concatenated chunks (first elements marked) go through the passes of imc::encode_schedule in two
+// ping-pong scratch streams; a level that install_encoding would upload is a snapshot between two passes.  The new
+// length comes back once per pass, the chunk starts once per snapshot.  The scratch streams and tile tables are freed
+// before the call returns.  On failure no chunk of the call keeps token streams (they evaluate on their raw symbols).
+constexpr size_t ENC_RUN_MAX_ELEMENTS = (size_t)1 << 30;   // per run of passes; a set beyond it goes in groups of whole chunks
+constexpr size_t ENC_RUN_MAX_CHUNKS = 4096;                // (the histogram's grid and count buffer are per chunk)
+static_assert(ENC_HIST_BINS >= HYBRID_MAX_ALPHABET, "every counted level must fit the histogram's LDS bins");
+
+int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K)
+{
+    const imc::PairDict &d = dd->dict;
+    const imc::EncodeSchedule sch = imc::encode_schedule(d);
+    const int nsym = d.nsym;
+    size_t total = 0;
+    int max_counted = 1;
+    for (size_t k = 0; k < K; ++k) total += obs[k]->L;
+    for (int l = 0; l < imc::kNumLevels; ++l)
+        if (!sch.is_wide[l] || sch.alphabet[l] <= HYBRID_MAX_ALPHABET) max_counted = std::max(max_counted, sch.alphabet[l]);
+    if (K == 0 || total == 0) return IMC_OK;
+    if (total >= (size_t)1 << 31 || K > ENC_RUN_MAX_CHUNKS) return fail(IMC_ERR_ARG, "device encoder: too many elements or chunks in one run");
+    const size_t tiles0 = (total + ENC_TILE - 1) / ENC_TILE;
+    DevBuf<uint16_t> buf[2], flags;
+    DevBuf<imc::TileSummary> sums;
+    DevBuf<uint2> tile_in;
+    DevBuf<uint32_t> new_n, pos, counts;
+    DevBuf<uint8_t *> dptr;
+    std::vector<uint32_t> hpos(K + 1), hcounts;
+    std::vector<uint8_t *> hptr(K);
+    uint32_t n = (uint32_t)total;
+    int cur = 0;
+
+    auto run_pass = [&](const imc::EncodeSchedule::Pass &p) -> int {
+        const EncPass ps{dd->d_left, dd->d_right, p.z0, p.nz};
+        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
+        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
+        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
+                           buf[cur ^ 1].get());
+        HIP_TRY(hipGetLastError());
+        uint32_t hn = 0;
+        HIP_TRY(hipMemcpyAsync(&hn, new_n.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device encoder: a pass returned an impossible length");
+        n = hn;
+        cur ^= 1;
+        return IMC_OK;
+    };
+    auto snapshot = [&](int l) -> int {
+        const bool wide = sch.is_wide[l];
+        const int alphabet = sch.alphabet[l];
+        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
+        hipLaunchKernelGGL(k_enc_mark_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
+        hipLaunchKernelGGL(k_enc_mark_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, tile_in.get(), pos.get(), (uint32_t)K);
+        HIP_TRY(hipGetLastError());
+        uint32_t marks = 0;
+        HIP_TRY(hipMemcpyAsync(&marks, new_n.get(), sizeof marks, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(hpos.data(), pos.get(), (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        bool sane = marks == K && hpos[0] == 0 && hpos[K] == n;
+        for (size_t k = 0; k < K && sane; ++k) sane = hpos[k] < hpos[k + 1];
+        if (!sane) return fail(IMC_ERR_HIP, "device encoder: chunk starts lost");
+        for (size_t k = 0; k < K; ++k) {                        // upload_padded()'s shape: rounded up to 256 B plus 256 B, padding zeroed
+            const size_t len = hpos[k + 1] - hpos[k], bytes = ((len * (wide ? sizeof(imc::tok_t) : 1) + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
+            HIP_TRY(dev_alloc((void **)&obs[k]->d_tok[l], bytes));
+            HIP_TRY(hipMemsetAsync(obs[k]->d_tok[l], 0, bytes, g.stream));
+            obs[k]->ntok[l] = len;
+            hptr[k] = obs[k]->d_tok[l];
+        }
+        HIP_TRY(hipMemcpyAsync(dptr.get(), hptr.data(), K * sizeof(uint8_t *), hipMemcpyHostToDevice, g.stream));
+        hipLaunchKernelGGL(k_enc_snapshot, dim3((n + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, pos.get(),
+                           (uint32_t)K, dptr.get(), wide ? 0 : 1);
+        HIP_TRY(hipGetLastError());
+        const bool counted = !wide || alphabet <= HYBRID_MAX_ALPHABET;
+        if (counted) {
+            uint32_t longest = 1;
+            for (size_t k = 0; k < K; ++k) longest = std::max(longest, hpos[k + 1] - hpos[k]);
+            const uint32_t bx = std::max<uint32_t>(1, std::min<uint32_t>(128, (longest + 8 * ENC_THREADS - 1) / (8 * ENC_THREADS)));
+            HIP_TRY(hipMemsetAsync(counts.get(), 0, K * (size_t)alphabet * sizeof(uint32_t), g.stream));
+            hipLaunchKernelGGL(k_enc_histogram, dim3(bx, (uint32_t)K), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), pos.get(), alphabet, counts.get());
+            HIP_TRY(hipGetLastError());
+            hcounts.resize(K * (size_t)alphabet);
+            HIP_TRY(hipMemcpyAsync(hcounts.data(), counts.get(), hcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (counted)
+            for (size_t k = 0; k < K; ++k) obs[k]->tok_count[l].assign(hcounts.begin() + k * (size_t)alphabet, hcounts.begin() + (k + 1) * (size_t)alphabet);
+        return IMC_OK;
+    };
+    auto body = [&]() -> int {
+        HIP_TRY(hipSetDevice(g.device));
+        for (int b = 0; b < 2; ++b) HIP_TRY(buf[b].alloc((tiles0 * ENC_TILE + ENC_ITEMS) * sizeof(uint16_t)));
+        HIP_TRY(flags.alloc(tiles0 * ENC_THREADS * sizeof(uint16_t)));
+        HIP_TRY(sums.alloc(tiles0 * sizeof(imc::TileSummary)));
+        HIP_TRY(tile_in.alloc(tiles0 * sizeof(uint2)));
+        HIP_TRY(new_n.alloc(sizeof(uint32_t)));
+        HIP_TRY(pos.alloc((K + 1) * sizeof(uint32_t)));
+        HIP_TRY(dptr.alloc(K * sizeof(uint8_t *)));
+        HIP_TRY(counts.alloc(K * (size_t)max_counted * sizeof(uint32_t)));
+        size_t off = 0;
+        for (size_t k = 0; k < K; ++k) {
+            const uint32_t L = (uint32_t)obs[k]->L;
+            if (!L) return fail(IMC_ERR_ARG, "device encoder: empty chunk");
+            hipLaunchKernelGGL(k_enc_load, dim3((L + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, (const void *)obs[k]->d_sym,
+                               obs[k]->wide_raw ? 2 : 1, L, buf[0].get() + off);
+            off += L;
+        }
+        HIP_TRY(hipGetLastError());
+        size_t applied = 0;
+        for (int l = 0; l < imc::kNumLevels; ++l) {             // install_encoding()'s rules, level by level
+            for (size_t k = 0; k < K; ++k) {
+                imc_obs *o = obs[k];
+                o->alphabet[l] = sch.alphabet[l];
+                o->wide[l] = sch.is_wide[l];
+                o->ntok[l] = o->L;
+                o->tok_count[l].clear();
+            }
+            if (l > 0 && sch.alphabet[l] == sch.alphabet[l - 1]) {
+                for (size_t k = 0; k < K; ++k) {
+                    imc_obs *o = obs[k];
+                    o->d_tok[l] = o->d_tok[l - 1]; o->wide[l] = o->wide[l - 1]; o->ntok[l] = o->ntok[l - 1]; o->tok_count[l] = o->tok_count[l - 1];
+                }
+                continue;
+            }
+            if (sch.alphabet[l] <= nsym) continue;              // raw stream: d_sym (d_tok stays null)
+            for (; applied < (size_t)sch.after[l]; ++applied)
+                if (int rc = run_pass(sch.passes[applied])) return rc;
+            if (int rc = snapshot(l)) return rc;
+        }
+        return IMC_OK;
+    };
+    const int rc = body();
+    if (rc != IMC_OK) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(g.stream);
+        for (size_t k = 0; k < K; ++k) release_tokens(obs[k]);
+        return fail(rc, msg);
+    }
+    for (size_t k = 0; k < K; ++k) obs[k]->dict = dd;
+    return IMC_OK;
+}
+
+int device_encode(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K)
+{
+    for (size_t first = 0; first < K;) {
+        size_t last = first, sum = 0;
+        while (last < K && last - first < ENC_RUN_MAX_CHUNKS && (last == first || sum + obs[last]->L <= ENC_RUN_MAX_ELEMENTS)) sum += obs[last++]->L;
+        if (int rc = device_encode_run(dd, obs + first, last - first)) {
+            const std::string msg = g_err;
+            for (size_t k = 0; k < first; ++k) release_tokens(obs[k]);
+            return fail(rc, msg);
+        }
+        first = last;
+    }
+    return IMC_OK;
+}
+
 int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym, imc_obs **out)
 {
     // exactly one of host (alphabets up to 256: bytes) and host16 (larger alphabets) is non-null when L > 0
     const bool wide_raw = nsym > imc::kByteAlphabet;
+    static const bool dbg_host = std::getenv("IMC_DEBUG_HOST") != nullptr;     // diagnostics: host time per phase
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
     std::shared_ptr<DictDev> dd;
-    bool want_zip = false, train = false;
+    bool want_zip = false, train = false, on_device = false;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (int rc = ensure_ctx()) return rc;
+        on_device = g.device_encode == 1;
         // ---- compression (the preprocess_raw_observations analogue, hmm.py:16) ----
         want_zip = g.compression && L >= ZIP_MIN_COLUMNS && nsym < imc::kMaxAlphabet / 2;
         if (want_zip) {
@@ -488,9 +662,12 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
             dd = nd;
         }
     }
+    const auto t1 = now();
     imc::EncodedLevels enc;
     const bool zipped = dd && dd->dict.alphabet > nsym;
-    if (zipped) imc::encode_levels(dd->dict, host, host16, L, enc);   // host only, unlocked (a published dictionary is immutable)
+    // host only, unlocked (a published dictionary is immutable) - or, with imc_set_device_encoding(1), on the device below
+    if (zipped && !on_device) imc::encode_levels(dd->dict, host, host16, L, enc);
+    const auto t2 = now();
 
     std::lock_guard<std::mutex> lk(g_mu);
     if (int rc = ensure_ctx()) return rc;
@@ -512,13 +689,135 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
         return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
                     std::string("observation upload: ") + hipGetErrorString(e));
     }
+    const auto t3 = now();
     if (zipped) {
-        if (int rc = install_encoding(o, dd, enc)) {
+        if (int rc = on_device ? device_encode(dd, &o, 1) : install_encoding(o, dd, enc)) {
             obs_release(o);
             delete o;
             return rc;
         }
     }
+    if (dbg_host)      // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
+        std::fprintf(stderr, "[imc host] create %zu columns: train %.1f ms, encode %.1f ms, upload %.1f ms, install %.1f ms (%s encoder)\n", L,
+                     ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()), on_device ? "device" : "host");
+    *out = o;
+    return IMC_OK;
+}
+
+// Columns of a chunk's head that make_dictionary() looks at: a dictionary trained on the head alone is the dictionary
+// trained on the whole chunk.
+size_t training_head(size_t L, bool wide_raw)
+{
+    return std::min(L, wide_raw ? DICT_WIDE_TRAIN_TOKENS * 8 + 1 : std::max(DICT_TRAIN_MAX + 1, DICT_WIDE_TRAIN_TOKENS * 96));
+}
+
+// d_sym must be device memory of the library's device, `bytes` long: an error, never a fault (g_mu held, context ready).
+int check_device_range(const void *p, size_t bytes)
+{
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(IMC_ERR_ARG, "d_sym is not device memory (hipPointerGetAttributes)");
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(IMC_ERR_ARG, "d_sym is not device memory");
+    if (at.device != g.device) return fail(IMC_ERR_ARG, "d_sym is memory of device " + std::to_string(at.device) + ", the library runs on device " + std::to_string(g.device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
+        if ((const char *)p + bytes > (const char *)base + size) return fail(IMC_ERR_ARG, "d_sym: the allocation ends before L symbols");
+    } else (void)hipGetLastError();
+    return IMC_OK;
+}
+
+// Build a chunk from symbols in device memory (imc_obs_create_device; arguments already checked).  The device work is on
+// the library's stream under g_mu; dictionary training - on a head copied back, only when the alphabet has no dictionary
+// yet - runs unlocked like obs_upload's.
+int obs_from_device(const void *d_src, size_t L, int nsym, int sym_bytes, hipStream_t user_stream, imc_obs **out)
+{
+    const bool wide_raw = nsym > imc::kByteAlphabet;
+    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
+    std::shared_ptr<DictDev> dd;
+    bool train = false;
+    imc_obs *o = nullptr;
+    std::vector<uint8_t> head;
+    auto drop = [&](int rc) {                       // (g_mu held)
+        const std::string msg = g_err;
+        obs_release(o);
+        delete o;
+        return fail(rc, msg);
+    };
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (int rc = ensure_ctx()) return rc;
+        HIP_TRY(hipSetDevice(g.device));
+        if (L)
+            if (int rc = check_device_range(d_src, L * (size_t)sym_bytes)) return rc;
+        HIP_TRY(hipStreamSynchronize(user_stream));   // what the caller queued on its stream has produced the symbols
+        o = new (std::nothrow) imc_obs();
+        if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+        o->id = g.next_obs_id++;
+        o->pid = g.pid;
+        o->device = g.device;
+        o->nsym = nsym;
+        o->L = L;
+        o->d_sym = nullptr;
+        o->wide_raw = wide_raw;
+        for (int l = 0; l < imc::kNumLevels; ++l) { o->d_tok[l] = nullptr; o->wide[l] = false; o->ntok[l] = 0; o->alphabet[l] = nsym; }
+        auto work = [&]() -> int {
+            const size_t bytes = ((L * unit + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
+            HIP_TRY(dev_alloc((void **)&o->d_sym, bytes));
+            HIP_TRY(hipMemsetAsync(o->d_sym, 0, bytes, g.stream));
+            if (!L) return hipStreamSynchronize(g.stream) == hipSuccess ? IMC_OK : fail(IMC_ERR_HIP, "stream synchronisation failed");
+            DevBuf<uint32_t> first_bad;
+            HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
+            const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
+            hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
+            hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, o->d_sym, wide_raw ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            uint32_t bad = 0;
+            HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            if (bad != 0xffffffffu) {
+                int32_t v = 0;
+                uint8_t raw[4] = {0, 0, 0, 0};
+                HIP_TRY(hipMemcpy(raw, (const char *)d_src + (size_t)bad * sym_bytes, sym_bytes, hipMemcpyDeviceToHost));
+                if (sym_bytes == 1) v = raw[0];
+                else if (sym_bytes == 2) { uint16_t u; std::memcpy(&u, raw, 2); v = u; }
+                else std::memcpy(&v, raw, 4);
+                return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(v) + " at column " + std::to_string(bad) + " outside [0,nsym)");
+            }
+            if (g.compression && L >= ZIP_MIN_COLUMNS && nsym < imc::kMaxAlphabet / 2) {
+                auto it = g.dicts.find(nsym);
+                if (it != g.dicts.end()) dd = it->second;
+                else train = L >= DICT_TRAIN_MIN;
+            }
+            if (train) {                              // only the head that training looks at comes back
+                head.resize(training_head(L, wide_raw) * unit);
+                HIP_TRY(hipMemcpy(head.data(), o->d_sym, head.size(), hipMemcpyDeviceToHost));
+            }
+            return IMC_OK;
+        };
+        if (int rc = work()) return drop(rc);
+    }
+    if (train) {                                        // host only, unlocked
+        auto nd = wide_raw ? make_dictionary(nullptr, reinterpret_cast<const imc::tok_t *>(head.data()), head.size() / unit, nsym)
+                           : make_dictionary(head.data(), nullptr, head.size(), nsym);
+        nd->trained_on = L;
+        std::vector<uint8_t>().swap(head);
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g.dicts.find(nsym);
+        if (it != g.dicts.end()) dd = it->second;
+        else {
+            if (int rc = upload_dictionary(nd)) return drop(rc);
+            g.dicts[nsym] = nd;
+            dd = nd;
+        }
+    }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (dd && dd->dict.alphabet > nsym)
+        if (int rc = device_encode(dd, &o, 1)) return drop(rc);
     *out = o;
     return IMC_OK;
 }
@@ -2382,10 +2681,12 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
 {
     if (n_chunks < 0 || (n_chunks > 0 && !chunks)) return fail(IMC_ERR_ARG, "chunks is null");
     std::map<int, std::vector<imc_obs *>> by_alphabet;
+    bool on_device = false;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (int rc = ensure_ctx()) return rc;
         if (!g.compression) return IMC_OK;
+        on_device = g.device_encode == 1;
         for (int f = 0; f < n_chunks; ++f) {
             imc_obs *o = chunks[f];
             if (!o) return fail(IMC_ERR_ARG, "chunk is null");
@@ -2403,6 +2704,10 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
         obs.erase(std::unique(obs.begin(), obs.end()), obs.end());
         const bool wide_raw = nsym > imc::kByteAlphabet;
         const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
+        static const bool dbg_host = std::getenv("IMC_DEBUG_HOST") != nullptr;     // diagnostics: host time per phase
+        auto now = [] { return std::chrono::steady_clock::now(); };
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        const auto t0 = now();
         size_t total = 0;
         for (imc_obs *o : obs) total += o->L;
         if (total < DICT_TRAIN_MIN) continue;
@@ -2413,38 +2718,47 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
             for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
             if (same && obs[0]->dict->trained_on >= total) continue;
         }
-        // ---- raw symbols back to the host (the chunks keep them on the device) ----
+        // ---- training sample: an equal share of every chunk (its head), up to the training budget ----
+        const size_t budget = wide_raw ? DICT_WIDE_TRAIN_TOKENS * 8 : std::max(DICT_TRAIN_MAX, DICT_WIDE_TRAIN_TOKENS * 96);
+        const size_t share = std::max<size_t>(DICT_TRAIN_MIN, budget / obs.size());
+        // ---- raw symbols back to the host (the chunks keep them on the device): all of them for the host encoder, only
+        //      the training heads when the device encodes ----
         std::vector<std::vector<uint8_t>> raw(obs.size());
         {
             std::lock_guard<std::mutex> lk(g_mu);
             HIP_TRY(hipSetDevice(g.device));
             for (size_t k = 0; k < obs.size(); ++k) {
-                raw[k].resize(obs[k]->L * unit);
+                raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
                 HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
             }
         }
-        // ---- training sample: an equal share of every chunk (its head), up to the training budget ----
-        const size_t budget = wide_raw ? DICT_WIDE_TRAIN_TOKENS * 8 : std::max(DICT_TRAIN_MAX, DICT_WIDE_TRAIN_TOKENS * 96);
-        const size_t share = std::max<size_t>(DICT_TRAIN_MIN, budget / obs.size());
         std::vector<uint8_t> sample;
         for (size_t k = 0; k < obs.size(); ++k) {
             const size_t n = std::min(obs[k]->L, share);
             sample.insert(sample.end(), raw[k].begin(), raw[k].begin() + n * unit);
         }
         const size_t ns = sample.size() / unit;
+        const auto t1 = now();
         auto nd = wide_raw ? make_dictionary(nullptr, reinterpret_cast<const imc::tok_t *>(sample.data()), ns, nsym)
                            : make_dictionary(sample.data(), nullptr, ns, nsym);
         std::vector<uint8_t>().swap(sample);
         nd->trained_on = total;
+        const auto t2 = now();
         // ---- re-encode (host, unlocked), then swap the streams in under the lock ----
         std::vector<imc::EncodedLevels> enc(obs.size());
         const bool zipped = nd->dict.alphabet > nsym;
-        if (zipped)
+        if (zipped && !on_device)
             for (size_t k = 0; k < obs.size(); ++k) {
                 if (wide_raw) imc::encode_levels(nd->dict, nullptr, reinterpret_cast<const imc::tok_t *>(raw[k].data()), obs[k]->L, enc[k]);
                 else imc::encode_levels(nd->dict, raw[k].data(), nullptr, obs[k]->L, enc[k]);
                 std::vector<uint8_t>().swap(raw[k]);
             }
+        const auto t3 = now();
+        auto report = [&] {
+            if (dbg_host)
+                std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder)\n",
+                             obs.size(), total, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()), on_device ? "device" : "host");
+        };
         std::unique_lock<std::mutex> lk(g_mu);
         wait_all_idle(lk);
         HIP_TRY(hipSetDevice(g.device));
@@ -2453,11 +2767,55 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
         if (!zipped) continue;                           // (incompressible sample: keep what the chunks have)
         if (int rc = upload_dictionary(nd)) return rc;
         g.dicts[nsym] = nd;                              // later chunks of this alphabet share it too
+        if (on_device) {                                 // all chunks of the alphabet in one batched run of passes
+            for (imc_obs *o : obs) release_tokens(o);
+            if (int rc = device_encode(nd, obs.data(), obs.size())) return rc;
+            report();
+            continue;
+        }
         for (size_t k = 0; k < obs.size(); ++k) {
             release_tokens(obs[k]);
             if (int rc = install_encoding(obs[k], nd, enc[k])) return rc;
         }
+        report();
     }
+    return IMC_OK;
+}
+
+int imc_obs_create_device(const void *d_sym, size_t L, int nsym, int sym_bytes, void *hip_stream, imc_obs **out)
+{
+    // every argument check before any HIP call
+    if (!out) return fail(IMC_ERR_ARG, "out is null");
+    if (sym_bytes != 1 && sym_bytes != 2 && sym_bytes != 4) return fail(IMC_ERR_ARG, "sym_bytes must be 1, 2 or 4");
+    if (nsym < 1 || nsym > imc::kMaxRawAlphabet) return fail(IMC_ERR_ARG, "nsym must be in [1," + std::to_string(imc::kMaxRawAlphabet) + "]");
+    if (sym_bytes == 1 && nsym > imc::kByteAlphabet) return fail(IMC_ERR_ARG, "byte symbols cannot carry more than 256 symbols");
+    if (L && !d_sym) return fail(IMC_ERR_ARG, "d_sym is null");
+    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    return obs_from_device(d_sym, L, nsym, sym_bytes, (hipStream_t)hip_stream, out);
+}
+
+int imc_obs_token_counts(const imc_obs *obs, int alphabet_limit, uint32_t *counts, size_t capacity, int *alphabet_used)
+{
+    if (!obs || !alphabet_used) return fail(IMC_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (obs->pid != getpid()) return fail(IMC_ERR_ARG, "chunk handle was created in another process");
+    int level = -1, used = obs->nsym;
+    if (obs->dict)
+        for (int l = 0; l < imc::kNumLevels; ++l)
+            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) { level = l; used = obs->alphabet[l]; }
+    *alphabet_used = used;
+    if (!counts) return IMC_OK;
+    if (capacity < (size_t)used) return fail(IMC_ERR_ARG, "capacity smaller than the alphabet");
+    for (int z = 0; z < used; ++z)
+        counts[z] = level >= 0 && (size_t)z < obs->tok_count[level].size() ? obs->tok_count[level][z] : 0u;   // (zeros where the level keeps no counts)
+    return IMC_OK;
+}
+
+int imc_set_device_encoding(int mode)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device encoding mode must be 0 (host encoder) or 1 (device encoder)");
+    g.device_encode = mode;
     return IMC_OK;
 }
 

@@ -97,6 +97,15 @@ def recompress(forwarders):
     _capi.check(_capi.lib().imc_obs_recompress(_capi.handle_array([f.handle for f in ours]), len(ours)))
 
 
+def set_device_encoding(mode):
+    """Where token streams are computed (``imc_set_device_encoding``): 0 = the host encoder (default), 1 = the device
+    encoder - the same tokens from the symbols already in HBM; ``recompress`` then copies back only the training heads."""
+    _capi.check(_capi.lib().imc_set_device_encoding(int(mode)))
+
+
+_DEVICE_SYMBOL_BYTES = {"|u1": 1, "<i2": 2, "<u2": 2, "<i4": 4}
+
+
 def forward_states(handles, pis, Ts, Es, as_operator):
     """State of every chunk instead of its log-likelihood (``imc_forward_state``).
 
@@ -138,7 +147,7 @@ class Forwarder(object):
     """``Forwarder(input_filename, NSYM)`` - same surface as the reference class (hmm.py:10-21).
 
     ``input_filename`` is a text file of whitespace-separated symbols as written by
-    scripts/prepare-alignments.py.  Extra, additive constructors: ``Forwarder.from_array``.
+    scripts/prepare-alignments.py.  Extra, additive constructors: ``Forwarder.from_array``, ``Forwarder.from_device``.
     """
 
     def __init__(self, input_filename, NSYM):
@@ -168,8 +177,49 @@ class Forwarder(object):
         self._pid = os.getpid()
         return self
 
+    @classmethod
+    def from_device(cls, obj, NSYM, stream=None):
+        """Build from symbols in device memory: ``obj`` is anything with ``__cuda_array_interface__`` (a torch ROCm tensor
+        has one) holding a one-dimensional contiguous array of uint8, int16 / uint16 or int32 symbols on the library's
+        device.  ``stream`` is the HIP stream the data was produced on (a handle, or an object with ``cuda_stream``;
+        default: the default stream); the call synchronises it, copies the symbols and keeps no reference to ``obj``."""
+        try:
+            cai = obj.__cuda_array_interface__
+        except AttributeError:
+            raise ValueError("from_device needs an object with __cuda_array_interface__")
+        shape, typestr, strides = tuple(cai["shape"]), cai["typestr"], cai.get("strides")
+        if typestr not in _DEVICE_SYMBOL_BYTES:
+            raise ValueError("from_device accepts uint8, int16 / uint16 and int32 symbols, got %r" % (typestr,))
+        size = _DEVICE_SYMBOL_BYTES[typestr]
+        if len(shape) != 1:
+            raise ValueError("from_device needs a one-dimensional array, got shape %r" % (shape,))
+        if strides is not None and shape[0] > 1 and tuple(strides) != (size,):
+            raise ValueError("from_device needs contiguous symbols, got strides %r" % (tuple(strides),))
+        ptr = cai["data"][0] if shape[0] else None
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self = cls.__new__(cls)
+        self.NSYM = int(NSYM)
+        self._h = None
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib().imc_obs_create_device(ptr, int(shape[0]), self.NSYM, size, stream or None, ctypes.byref(h)))
+        self._h = h.value
+        self._pid = os.getpid()
+        return self
+
     def __len__(self):
         return int(_capi.lib().imc_obs_length(self._h))
+
+    def token_counts(self, alphabet_limit=256):
+        """Occurrences of every token id at positions >= 1 of the stream ``compressed_length(alphabet_limit)`` describes
+        (``imc_obs_token_counts``): uint32[alphabet]; zeros where the level keeps no counts."""
+        L = _capi.lib()
+        used = ctypes.c_int(0)
+        _capi.check(L.imc_obs_token_counts(self._h, int(alphabet_limit), None, 0, ctypes.byref(used)))
+        out = np.zeros(max(used.value, 1), dtype=np.uint32)
+        _capi.check(L.imc_obs_token_counts(self._h, int(alphabet_limit), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), used.value,
+                                           ctypes.byref(used)))
+        return out[:used.value]
 
     def compressed_length(self, alphabet_limit=256):
         """(tokens, alphabet) of the pair-compressed stream - the (new_obs, new_nsyms) of hmm.py:16."""

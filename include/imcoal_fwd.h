@@ -30,7 +30,8 @@
  * launches); a synchronous call waits for its results without it, so other threads queue their evaluations behind it
  * (two synchronous calls on the SAME chunk list share a plan's result slots and run one after the other; a chunk is not
  * freed, and no plan released, while somebody waits on it).  The O(L) host work of imc_obs_create* (validation,
- * dictionary training, encoding) runs outside the mutex.
+ * dictionary training, encoding) runs outside the mutex; the device encoder (imc_set_device_encoding(1),
+ * imc_obs_create_device) runs on the library's stream with the mutex held.
  *
  * Environment (diagnostics only, read when a plan is built / the context is created):
  *   IMC_DEBUG=1        print the planner's cost estimates to stderr
@@ -40,6 +41,7 @@
  *                      unmapped range, so any access past a buffer's end faults at once (tests/test_gpu_guard.py)
  *   IMC_DEBUG_R1=1     print where each operator segment was certified rank one (hand-off checkpoints) to stderr
  *   IMC_DEBUG_HOST=1   print the host time per phase of the synchronous entry points (plan, stage, enqueue, wait)
+ *                      and of chunk creation / imc_obs_recompress (copy back, training, encoding, upload)
  *   A/B switches for measurements (the default is the faster setting): IMC_TABLE_PAIRS=0 (k_zpropagate4's table one
  *   dictionary depth per launch instead of two), IMC_PACK_TABLE=0 (the mat-vec chain reads the 16-padded operator
  *   table), IMC_Z4_STREAM / IMC_BLOCKED / IMC_RANK1 (see the setters below), IMC_DICT_MIN_COUNT=n and
@@ -95,6 +97,17 @@ int imc_obs_create_i32(const int32_t *sym, size_t L, int nsym, imc_obs **out);  
 /* File of whitespace-separated decimal tokens, the format written by
  * scripts/prepare-alignments.py:92-105 and read at hmm.py:13-14. */
 int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out);   /* also accepts imc_write_cache files */
+/* A chunk from symbols that are already in device memory (a simulated replicate, the output of another stage): d_sym
+ * points to L symbols of sym_bytes = 1 (uint8), 2 (16-bit) or 4 (int32) bytes each on the library's device.  The call
+ * synchronises hip_stream (a hipStream_t; NULL is the default stream), copies the symbols into a buffer of its own on
+ * the device (narrowed to bytes, or to 16 bits beyond 256 symbols) and keeps no reference to d_sym.  Validation and the
+ * token streams are computed on the device (csrc/kernels_encode.hpp; the tokens the host encoder would produce); only
+ * when the alphabet has no dictionary yet does the head that dictionary training looks at travel to the host.
+ * IMC_ERR_ARG - checked before any HIP call - for null pointers, another sym_bytes, nsym outside [1,4096], byte symbols
+ * with nsym > 256 and L >= 2^31; IMC_ERR_ARG as well for a pointer that is not device memory of the library's device
+ * (hipPointerGetAttributes: an error, never a fault); IMC_ERR_SYMBOL names the first column whose symbol is outside
+ * [0,nsym). */
+int imc_obs_create_device(const void *d_sym, size_t L, int nsym, int sym_bytes, void *hip_stream, imc_obs **out);
 size_t imc_obs_length(const imc_obs *obs);
 int imc_obs_nsym(const imc_obs *obs);
 /* Length of the chunk's pair-compressed token stream (the `new_obs` of hmm.py:16) at the deepest
@@ -122,6 +135,11 @@ int imc_obs_dictionary(const imc_obs *obs, int alphabet_limit, uint16_t *left, u
                        int *alphabet_used);
 int imc_obs_tokens(const imc_obs *obs, int alphabet_limit, uint16_t *tokens, size_t capacity, size_t *length,
                    int *alphabet_used);
+/* Inspection sibling of imc_obs_tokens: how often every token id occurs at positions >= 1 of the stream at the
+ * deepest level whose alphabet is <= alphabet_limit (the counts behind the hybrid table's hot set).  Call with
+ * counts = NULL to get *alphabet_used first, then with capacity >= *alphabet_used.  Levels that keep no counts (16-bit
+ * levels beyond 4096 tokens, uncompressed chunks) give zero entries. */
+int imc_obs_token_counts(const imc_obs *obs, int alphabet_limit, uint32_t *counts, size_t capacity, int *alphabet_used);
 int imc_obs_free(imc_obs *obs);
 
 /* Host-side ingestion helpers (no GPU needed) -------------------------------------------- */
@@ -193,6 +211,14 @@ int imc_set_compression(int mode);
 /* Forget the per-process pair dictionaries: the next sufficiently long chunk trains a new one.
  * Chunks that already exist keep the dictionary they were encoded with. */
 int imc_dictionary_reset(void);
+/* Where the token streams of a chunk are computed.  0 (default): on the host, one thread, one pass per merge over the
+ * whole chunk (imc::encode_levels) - imc_obs_recompress first copies every raw stream back for it.  1: on the device,
+ * from the symbols that are there anyway (csrc/kernels_encode.hpp): imc_obs_create* still validate and train on the
+ * host; imc_obs_recompress copies back only the training heads and encodes all chunks of an alphabet in one batched run.
+ * Dictionary training is the host's in both modes, and the device encoder produces exactly the host encoder's tokens, so
+ * dictionaries, streams and results are bit-identical; the mode changes set-up time only.  imc_obs_create_device always
+ * encodes on the device.  IMC_DEVICE_ENCODE=0|1 in the environment sets the mode at start-up. */
+int imc_set_device_encoding(int mode);
 /* Kernel timing with HIP events on the launch stream.  After imc_profile_enable(1) every
  * propagate/stitch launch is bracketed by events; imc_profile_read synchronises, returns the
  * accumulated device milliseconds and launch counts since the last reset, and resets.  ms_propagate is the
