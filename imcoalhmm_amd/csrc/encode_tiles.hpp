@@ -14,6 +14,8 @@
 // on, for both values of the bit (TileSummary).  Summaries compose associatively (tile_combine), so the carries and the
 // output offsets of all tiles come from one scan, and every tile then writes its part of the output independently.
 // The kernels (kernels_encode.hpp) and the CPU check (tests/encode_tiles_check.cpp) call the functions below.
+// The pass schedule (encode_schedule) and the rule for how a chunk stores each level (level_rules) are at the end;
+// tests/chunk_policy_check.cpp checks the rule against encode_levels().
 //
 // The stream the passes run on is 16-bit throughout.  Bit 15 (kChunkMark) marks the first element of a chunk; token
 // ids stay below kMaxAlphabet = 2^14, so a marked element compares unequal to every pair half.  That is the rule
@@ -22,6 +24,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <vector>
 
@@ -167,6 +170,30 @@ inline EncodeSchedule encode_schedule(const PairDict &d)
     }
     while (lvl < kNumLevels) put(std::max(d.nsym, d.alphabet), d.alphabet > kByteAlphabet);
     return s;
+}
+
+// ---- how a chunk stores its levels -------------------------------------------------------------------
+// The one rule for both encoders.  A level that repeats the alphabet of the level before it is that level's stream
+// (whatever that is); otherwise a level no larger than the raw alphabet is the chunk's raw symbols and any other level
+// owns a buffer.  Token occurrences (the hot-set choice of the hybrid table) are kept for the byte levels and for the
+// 16-bit levels up to counted_max tokens.
+enum LevelKind { kLevelRaw = 0, kLevelSame = 1, kLevelOwn = 2 };
+struct LevelRule {
+    LevelKind kind;
+    int alphabet;
+    bool is_wide;
+    bool counted;
+};
+
+inline std::array<LevelRule, kNumLevels> level_rules(const EncodeSchedule &s, int nsym, int counted_max)
+{
+    std::array<LevelRule, kNumLevels> r;
+    for (int l = 0; l < kNumLevels; ++l) {
+        if (l > 0 && s.alphabet[l] == s.alphabet[l - 1]) { r[l] = r[l - 1]; r[l].kind = kLevelSame; continue; }
+        const bool own = s.alphabet[l] > nsym;
+        r[l] = LevelRule{own ? kLevelOwn : kLevelRaw, s.alphabet[l], s.is_wide[l], own && (!s.is_wide[l] || s.alphabet[l] <= counted_max)};
+    }
+    return r;
 }
 
 }  // namespace imc

@@ -16,12 +16,15 @@
 // (imc::GroupKind) by the host-only planner in planner_host.hpp; the kernel families themselves are described in
 // DESIGN.md section 5.
 //
-// Host side, in the order of this file: context and device memory (dev_alloc, DevBuf), chunks and dictionaries,
-// the kernel table, the launch plan (Group / Level / Plan own their device buffers) and its builder, one enqueue
-// function per kernel family, the model layer, the C ABI.
+// Host side, in the order of this file: context and device memory (dev_alloc, DevBuf); chunks and dictionaries (the
+// pieces a chunk is made of - padded buffers, obs_new, dictionary_for - then the one level loop install_levels with its
+// host and device sources, obs_upload / obs_from_device, recompress_alphabet; the training policy is pair_dict.hpp's and
+// the level rule encode_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
+// and its builder, one enqueue function per kernel family, the model layer, the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cerrno>
 #include <climits>
 #include <cmath>
@@ -88,27 +91,16 @@ using imc::Z2GRAN;
 using imc::round_up;
 
 constexpr size_t STAGE_KERNEL_MAX_BYTES = 1u << 20;   // parameter sets up to this size are fetched by k_stage_params (enqueue)
-constexpr size_t ZIP_MIN_COLUMNS = 4096;           // shorter chunks are not worth compressing
-constexpr size_t DICT_TRAIN_MIN = 32768;           // first chunk at least this long trains the dictionary
-constexpr size_t DICT_TRAIN_MAX = 8u << 20;        // byte tokens (< 256): train on at most this prefix
-constexpr size_t DICT_WIDE_TRAIN_TOKENS = 1u << 19; // 16-bit tokens: train on at most this many byte-level tokens (~4e7 columns)
-constexpr int DICT_MAX_DEPTH = 0;                  // 0: no limit on a token's depth in the dictionary.  (IMC_DICT_MAX_DEPTH, experiments:
-                                                   // the table is built one depth per launch, but the bench alignment's 4096 tokens USE
-                                                   // their 11 depths - a cap of 10 saves one launch at 149.5 instead of 150.2 columns per
-                                                   // token, 9 already costs 13 % of the compression, 8 leaves 208 tokens)
-constexpr size_t DICT_WIDE_MIN_COUNT = 6;          // ... in which a pair must occur this often
 
 hipError_t dev_alloc(void **p, size_t bytes);
 void dev_free(void *p);
 
-struct DictDev {                                   // one trained dictionary + its device copy
-    imc::PairDict dict;
+struct DictDev : imc::TrainedDict {                // one trained dictionary (dict, depth, order: pair_dict.hpp) + its device copy
     uint16_t *d_left = nullptr, *d_right = nullptr;
-    uint16_t *d_order = nullptr;                   // merged tokens sorted by (depth, id)
-    std::vector<uint16_t> order;                   // host copy of d_order
-    std::vector<int> depth;                        // per token; raw symbols have depth 0
+    uint16_t *d_order = nullptr;                   // device copy of order
     uint64_t trained_on = 0;                       // columns of the chunk(s) the training sample was drawn from
     pid_t pid = 0;
+    DictDev(imc::TrainedDict t, uint64_t columns) : imc::TrainedDict(std::move(t)), trained_on(columns) {}
     ~DictDev()
     {
         if (pid == getpid()) { dev_free(d_left); dev_free(d_right); dev_free(d_order); }
@@ -171,6 +163,8 @@ struct Ctx {
 } g;
 
 void drop_plans();
+void drop_plans_using(imc_obs *const *obs, size_t n);
+void wait_all_idle(std::unique_lock<std::mutex> &lk);
 void model_release();
 
 int ensure_ctx()
@@ -322,45 +316,103 @@ public:
 }  // namespace
 
 struct imc_obs {
-    uint64_t id;
-    pid_t pid;
-    int device;
-    int nsym;
-    size_t L;
-    uint8_t *d_sym;                        // L raw symbols + zero padding (bytes, or 16-bit values when wide_raw)
-    bool wide_raw;                         // raw alphabet beyond 256 symbols
+    uint64_t id = 0;
+    pid_t pid = 0;
+    int device = 0;
+    int nsym = 0;
+    size_t L = 0;
+    uint8_t *d_sym = nullptr;              // L raw symbols + zero padding (bytes, or 16-bit values when wide_raw)
+    bool wide_raw = false;                 // raw alphabet beyond 256 symbols
     std::shared_ptr<DictDev> dict;         // null: not compressed
-    uint8_t *d_tok[imc::kNumLevels];       // token streams per level (aliases allowed), null if none
-    bool wide[imc::kNumLevels];            // ... holding 16-bit ids (alphabets beyond 256)
-    size_t ntok[imc::kNumLevels];
-    int alphabet[imc::kNumLevels];
+    uint8_t *d_tok[imc::kNumLevels] = {};  // token streams per level (aliases allowed), null if none
+    bool owns[imc::kNumLevels] = {};       // ... in a buffer of the level's own: release_tokens() frees exactly these
+    bool wide[imc::kNumLevels] = {};       // ... holding 16-bit ids (alphabets beyond 256)
+    size_t ntok[imc::kNumLevels] = {};
+    int alphabet[imc::kNumLevels] = {};
     std::vector<uint32_t> tok_count[imc::kNumLevels];   // byte levels: occurrences of every token id (hot-set choice of the hybrid table)
 };
 
 namespace {
 
+// ---- chunks and dictionaries --------------------------------------------------------------------------
+// What is compressed, what a dictionary is trained on and how (pair_dict.hpp: compressible, train_dictionary,
+// training_head, recompress_share / recompress_sample) and how a chunk stores each level (encode_tiles.hpp: level_rules)
+// are host-only rules checked on the CPU; here they meet the device.  Lock discipline: dictionary training and the host
+// encoder run WITHOUT g_mu (O(L) host work, ~1.4 s at 1e8 columns, while other threads keep evaluating); HIP calls and
+// the dictionary map g.dicts are touched only under it.
+
 constexpr size_t OBS_PAD = 256;
+
+// A device buffer for n bytes of symbols or tokens: rounded up to OBS_PAD plus OBS_PAD, all of it zeroed (queued on
+// g.stream).  *dptr is set as soon as the allocation succeeded, also when the call then fails.
+hipError_t alloc_padded(size_t n, uint8_t **dptr)
+{
+    const size_t bytes = ((n + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
+    const hipError_t e = dev_alloc((void **)dptr, bytes);
+    return e != hipSuccess ? e : hipMemsetAsync(*dptr, 0, bytes, g.stream);
+}
+
+// ... as level l of chunk o, in a buffer of the level's own
+hipError_t alloc_level(imc_obs *o, int l, size_t n)
+{
+    const hipError_t e = alloc_padded(n, &o->d_tok[l]);
+    o->owns[l] = o->d_tok[l] != nullptr;
+    return e;
+}
 
 hipError_t upload_padded(const uint8_t *host, size_t n, uint8_t **dptr)
 {
-    const size_t bytes = ((n + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
-    hipError_t e = dev_alloc((void **)dptr, bytes);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(*dptr, 0, bytes, g.stream);
+    hipError_t e = alloc_padded(n, dptr);
     if (e == hipSuccess && n) e = hipMemcpyAsync(*dptr, host, n, hipMemcpyHostToDevice, g.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
     return e;
 }
 
+// n symbols on the host: bytes (alphabets up to 256), or 16-bit values (larger alphabets) - exactly one pointer is set when n > 0
+struct HostSymbols {
+    const uint8_t *bytes;
+    const imc::tok_t *wide;
+    size_t n;
+};
+
+HostSymbols symbols_in(const std::vector<uint8_t> &raw, bool wide_raw)   // (raw: what a chunk's d_sym holds)
+{
+    if (wide_raw) return {nullptr, reinterpret_cast<const imc::tok_t *>(raw.data()), raw.size() / sizeof(imc::tok_t)};
+    return {raw.data(), nullptr, raw.size()};
+}
+
+// IMC_DEBUG_HOST (diagnostics): host time per phase of a chunk creation / a re-compression
+struct PhaseTimer {
+    using clock = std::chrono::steady_clock;
+    clock::time_point t[5];
+    int n = 0;
+    PhaseTimer() { mark(); }
+    void mark() { if (n < 5) t[n++] = clock::now(); }
+    double ms(int phase) const { return std::chrono::duration<double, std::milli>(t[phase + 1] - t[phase]).count(); }
+    static bool enabled() { static const bool on = std::getenv("IMC_DEBUG_HOST") != nullptr; return on; }
+};
+
+// A chunk that holds nothing on the device yet (g_mu held, context ready); null: out of host memory.
+imc_obs *obs_new(size_t L, int nsym)
+{
+    auto *o = new (std::nothrow) imc_obs();
+    if (!o) return nullptr;
+    o->id = g.next_obs_id++;
+    o->pid = g.pid;
+    o->device = g.device;
+    o->nsym = nsym;
+    o->L = L;
+    o->wide_raw = nsym > imc::kByteAlphabet;
+    std::fill(o->alphabet, o->alphabet + imc::kNumLevels, nsym);
+    return o;
+}
+
 void release_tokens(imc_obs *o)          // the chunk falls back to its raw symbols
 {
+    for (int l = 0; l < imc::kNumLevels; ++l)
+        if (o->owns[l]) dev_free(o->d_tok[l]);
     for (int l = 0; l < imc::kNumLevels; ++l) {
-        bool alias = false;
-        for (int m = 0; m < l; ++m) alias |= (o->d_tok[m] == o->d_tok[l]);
-        if (o->d_tok[l] && !alias) dev_free(o->d_tok[l]);
-    }
-    for (int l = 0; l < imc::kNumLevels; ++l) {
-        o->d_tok[l] = nullptr; o->wide[l] = false; o->ntok[l] = 0; o->alphabet[l] = o->nsym; o->tok_count[l].clear();
+        o->d_tok[l] = nullptr; o->owns[l] = false; o->wide[l] = false; o->ntok[l] = 0; o->alphabet[l] = o->nsym; o->tok_count[l].clear();
     }
     o->dict.reset();
 }
@@ -371,50 +423,14 @@ void obs_release(imc_obs *o)
     release_tokens(o);
 }
 
-// Build a chunk from validated host symbols.  Called WITHOUT g_mu: the O(L) host work (dictionary training, the
-// multi-level encoding: ~1.4 s at 1e8 columns) runs unlocked so that other threads keep evaluating; the lock is
-// taken only to read / publish the shared dictionary and for the HIP calls on the library's stream.
-// A pair becomes a 16-bit token when it occurs this often in the training sample: DICT_WIDE_MIN_COUNT in a full
-// sample, fewer in a short one - the dictionary of the FIRST chunk serves every later chunk of the alphabet, and a
-// workload of many 1e7-column chunks (BASELINE config[3]) trains on one of them: with the full-sample threshold it got
-// 1553 tokens (141 columns per token), with 3 occurrences 3473 (155) and a 3 % shorter evaluation; a token that turns
-// out to be rare costs one table entry.  (IMC_DICT_MIN_COUNT overrides: experiments.)
-size_t wide_min_count(size_t sample_tokens)
+// Train a pair dictionary on host symbols; host work only, called without g_mu.  The two experiment variables are read at
+// every training (imcoal_fwd.h).
+std::shared_ptr<DictDev> make_dictionary(const HostSymbols &sym, int nsym, uint64_t trained_on)
 {
-    if (const char *e = std::getenv("IMC_DICT_MIN_COUNT")) return (size_t)std::max(1, std::atoi(e));
-    return sample_tokens >= 400000 ? DICT_WIDE_MIN_COUNT : sample_tokens >= 200000 ? 4 : 3;
-}
-
-// Train a pair dictionary on host symbols (exactly one of host / host16 is non-null); host work only.
-std::shared_ptr<DictDev> make_dictionary(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym)
-{
-    auto nd = std::make_shared<DictDev>();
-    const int max_depth = std::getenv("IMC_DICT_MAX_DEPTH") ? std::atoi(std::getenv("IMC_DICT_MAX_DEPTH")) : DICT_MAX_DEPTH;
-    if (host16) {                                    // symbols are not bytes: straight to the 16-bit rounds on the raw stream
-        imc::init_dict(nd->dict, nsym);
-        const size_t nt = std::min(L - 1, DICT_WIDE_TRAIN_TOKENS * 8);
-        imc::train_dict_wide(nd->dict, std::vector<imc::tok_t>(host16 + 1, host16 + 1 + nt), DICT_WIDE_MIN_COUNT, max_depth);
-    } else {
-        const size_t n = std::min(L - 1, DICT_TRAIN_MAX);
-        imc::train_dict(nd->dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), 64, max_depth);
-        // The 16-bit rounds only start from a FULL byte dictionary.  On a large sample the byte phase can stop a few entries
-        // short (the best remaining pair under the depth cap has 63 occurrences) - and the chunk then has no level beyond
-        // ~250 tokens at all (seen once in a bench run: 96 instead of 150 columns per token, every evaluation 25-40 %
-        // slower).  Retrain with a lower threshold rather than lose the wide levels.
-        for (size_t min_count : {(size_t)8, (size_t)2}) {
-            if (nd->dict.alphabet >= imc::kByteAlphabet || nd->dict.alphabet < 3 * imc::kByteAlphabet / 4 || n < DICT_TRAIN_MIN) break;
-            imc::train_dict(nd->dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), min_count, max_depth);
-        }
-        if (nd->dict.alphabet >= imc::kByteAlphabet) {   // 16-bit tokens: rounds over the whole chunk's byte-level stream
-            const size_t cols = std::min(L, DICT_WIDE_TRAIN_TOKENS * 96);   // a byte-level token covers ~60-100 columns
-            const std::vector<uint8_t> lvl256 = imc::encode_bytes(nd->dict, host, cols, nullptr);
-            const size_t nt = std::min(lvl256.size() - 1, DICT_WIDE_TRAIN_TOKENS);
-            imc::train_dict_wide(nd->dict, std::vector<imc::tok_t>(lvl256.begin() + 1, lvl256.begin() + 1 + nt), wide_min_count(nt), max_depth);
-        }
-    }
-    nd->depth = imc::dict_depths(nd->dict);
-    nd->order = imc::dict_order(nd->dict, nd->depth);
-    return nd;
+    const char *min_count = std::getenv("IMC_DICT_MIN_COUNT"), *max_depth = std::getenv("IMC_DICT_MAX_DEPTH");
+    return std::make_shared<DictDev>(imc::train_dictionary(sym.bytes, sym.wide, sym.n, nsym, min_count ? (size_t)std::max(1, std::atoi(min_count)) : 0,
+                                                           max_depth ? std::atoi(max_depth) : imc::TrainLimits().max_depth),
+                                     trained_on);
 }
 
 // Device copy of a freshly trained dictionary (g_mu held, context ready).
@@ -435,60 +451,108 @@ int upload_dictionary(const std::shared_ptr<DictDev> &nd)
     return IMC_OK;
 }
 
-// The token streams of `enc` (encoded with dd's dictionary) become chunk o's (g_mu held).  On failure the chunk has no
-// token streams left (it evaluates on its raw symbols).
-int install_encoding(imc_obs *o, const std::shared_ptr<DictDev> &dd, const imc::EncodedLevels &enc)
+// nd becomes the dictionary that later chunks of the alphabet share (g_mu held, context ready).
+int publish_dictionary(int nsym, const std::shared_ptr<DictDev> &nd)
 {
-    const int nsym = o->nsym;
-    o->dict = dd;
-    for (int l = 0; l < imc::kNumLevels; ++l) {
-        o->alphabet[l] = enc.alphabet[l];
-        o->ntok[l] = enc.length[l];
-        o->wide[l] = enc.is_wide[l];
-        o->tok_count[l].clear();
-        if (l > 0 && enc.alphabet[l] == enc.alphabet[l - 1]) { o->d_tok[l] = o->d_tok[l - 1]; o->wide[l] = o->wide[l - 1]; o->tok_count[l] = o->tok_count[l - 1]; continue; }
-        if (enc.alphabet[l] <= nsym) { o->d_tok[l] = nullptr; continue; }   // raw stream: use d_sym
-        if (!enc.is_wide[l]) {
-            o->tok_count[l].assign((size_t)enc.alphabet[l], 0u);
-            for (size_t t = 1; t < enc.length[l]; ++t) o->tok_count[l][enc.bytes[l][t]]++;   // (position 0 is a raw symbol)
-        } else if (enc.alphabet[l] <= HYBRID_MAX_ALPHABET) {
-            o->tok_count[l].assign((size_t)enc.alphabet[l], 0u);
-            for (size_t t = 1; t < enc.length[l]; ++t) o->tok_count[l][enc.wide[l][t]]++;
-        }
-        hipError_t e3 = enc.is_wide[l]
-            ? upload_padded(reinterpret_cast<const uint8_t *>(enc.wide[l].data()), enc.length[l] * sizeof(imc::tok_t), &o->d_tok[l])
-            : upload_padded(enc.bytes[l].data(), enc.length[l], &o->d_tok[l]);
-        if (e3 != hipSuccess) {
-            release_tokens(o);
-            return fail(e3 == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
-                        std::string("token stream upload: ") + hipGetErrorString(e3));
-        }
-    }
+    if (int rc = upload_dictionary(nd)) return rc;
+    g.dicts[nsym] = nd;
     return IMC_OK;
 }
 
-// ---- encoding on the device (kernels_encode.hpp) ------------------------------------------------------
-// The token streams of K chunks of one alphabet from their raw symbols (d_sym), with dd's dictionary: what
-// imc::encode_levels + install_encoding give, level for level and bit for bit, without the symbols leaving the device.
-// g_mu held, context ready; the chunks hold no token streams (new, or after release_tokens).  Every launch and copy is on
-// g.stream.  The concatenated chunks (first elements marked) go through the passes of imc::encode_schedule in two
-// ping-pong scratch streams; a level that install_encoding would upload is a snapshot between two passes.  The new
-// length comes back once per pass, the chunk starts once per snapshot.  The scratch streams and tile tables are freed
-// before the call returns.  On failure no chunk of the call keeps token streams (they evaluate on their raw symbols).
+// The dictionary a new chunk of L columns is encoded with (the preprocess_raw_observations analogue, hmm.py:16): the
+// one published for its alphabet; else, for the first chunk long enough, one trained now; else none (*dd stays null).
+// Called and left with lk (g_mu) held and the context ready; the lock is released while training runs.  head(&symbols)
+// supplies the training symbols - at least imc::training_head() of the chunk - and is called, under the lock, only when
+// a dictionary has to be trained.
+template <class Head>
+int dictionary_for(std::unique_lock<std::mutex> &lk, size_t L, int nsym, Head &&head, std::shared_ptr<DictDev> *dd)
+{
+    if (!g.compression || !imc::compressible(L, nsym)) return IMC_OK;
+    auto it = g.dicts.find(nsym);
+    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }
+    if (L < imc::TrainLimits().train_min) return IMC_OK;
+    HostSymbols sym{};
+    if (int rc = head(&sym)) return rc;
+    lk.unlock();
+    const std::shared_ptr<DictDev> nd = make_dictionary(sym, nsym, L);   // host only, unlocked
+    lk.lock();
+    it = g.dicts.find(nsym);
+    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }        // another thread published one meanwhile: use that
+    if (int rc = publish_dictionary(nsym, nd)) return rc;
+    *dd = nd;
+    return IMC_OK;
+}
+
+// ---- token streams of a chunk -----------------------------------------------------------------------------
+// The levels of K chunks of one alphabet, stored by imc::level_rules (g_mu held; the chunks hold no token streams: new,
+// or after release_tokens).  A level that is the raw stream or the level before it is settled here; for a level with a
+// buffer of its own, materialise(l, rule) sets d_tok / owns / ntok - and tok_count where rule.counted - of every chunk:
+// the host encoder uploads what imc::encode_levels gave, the device encoder takes a snapshot between two passes; the
+// results are the same level for level and bit for bit (tests/test_gpu_device_encode.py).  On failure no chunk of the
+// call keeps token streams (they evaluate on their raw symbols).
+template <class Materialise>
+int install_levels(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K, const std::array<imc::LevelRule, imc::kNumLevels> &rules,
+                   Materialise &&materialise)
+{
+    int rc = IMC_OK;
+    for (int l = 0; l < imc::kNumLevels && rc == IMC_OK; ++l) {
+        const imc::LevelRule &r = rules[l];
+        for (size_t k = 0; k < K; ++k) {
+            imc_obs *o = obs[k];
+            o->alphabet[l] = r.alphabet;
+            o->wide[l] = r.is_wide;
+            o->ntok[l] = o->L;                                   // (raw stream: d_sym, d_tok stays null)
+            if (r.kind == imc::kLevelSame) { o->d_tok[l] = o->d_tok[l - 1]; o->ntok[l] = o->ntok[l - 1]; o->tok_count[l] = o->tok_count[l - 1]; }
+        }
+        if (r.kind == imc::kLevelOwn) rc = materialise(l, r);
+    }
+    if (rc != IMC_OK) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(g.stream);
+        for (size_t k = 0; k < K; ++k) release_tokens(obs[k]);
+        return fail(rc, msg);
+    }
+    for (size_t k = 0; k < K; ++k) obs[k]->dict = dd;
+    return IMC_OK;
+}
+
+// Host encoder: the token streams of `enc` (imc::encode_levels with dd's dictionary) become chunk o's.
+int install_encoding(imc_obs *o, const std::shared_ptr<DictDev> &dd, const imc::EncodedLevels &enc)
+{
+    const auto rules = imc::level_rules(imc::encode_schedule(dd->dict), o->nsym, HYBRID_MAX_ALPHABET);
+    return install_levels(dd, &o, 1, rules, [&](int l, const imc::LevelRule &r) -> int {
+        o->ntok[l] = enc.length[l];
+        if (r.counted) {
+            o->tok_count[l].assign((size_t)r.alphabet, 0u);
+            for (size_t t = 1; t < enc.length[l]; ++t) o->tok_count[l][r.is_wide ? enc.wide[l][t] : enc.bytes[l][t]]++;   // (position 0 is a raw symbol)
+        }
+        const hipError_t e = r.is_wide ? upload_padded(reinterpret_cast<const uint8_t *>(enc.wide[l].data()), enc.length[l] * sizeof(imc::tok_t), &o->d_tok[l])
+                                       : upload_padded(enc.bytes[l].data(), enc.length[l], &o->d_tok[l]);
+        o->owns[l] = o->d_tok[l] != nullptr;
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP, std::string("token stream upload: ") + hipGetErrorString(e));
+        return IMC_OK;
+    });
+}
+
+// Device encoder (kernels_encode.hpp): the token streams of K chunks of one alphabet from their raw symbols (d_sym),
+// without the symbols leaving the device.  g_mu held, context ready.  Every launch and copy is on g.stream.  The
+// concatenated chunks (first elements marked) go through the passes of imc::encode_schedule in two ping-pong scratch
+// streams; a level with a buffer of its own is a snapshot between two passes.  The new length comes back once per pass,
+// the chunk starts once per snapshot.  The scratch streams and tile tables are freed before the call returns.
 constexpr size_t ENC_RUN_MAX_ELEMENTS = (size_t)1 << 30;   // per run of passes; a set beyond it goes in groups of whole chunks
 constexpr size_t ENC_RUN_MAX_CHUNKS = 4096;                // (the histogram's grid and count buffer are per chunk)
 static_assert(ENC_HIST_BINS >= HYBRID_MAX_ALPHABET, "every counted level must fit the histogram's LDS bins");
 
 int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K)
 {
-    const imc::PairDict &d = dd->dict;
-    const imc::EncodeSchedule sch = imc::encode_schedule(d);
-    const int nsym = d.nsym;
+    const imc::EncodeSchedule sch = imc::encode_schedule(dd->dict);
+    const auto rules = imc::level_rules(sch, dd->dict.nsym, HYBRID_MAX_ALPHABET);
     size_t total = 0;
     int max_counted = 1;
     for (size_t k = 0; k < K; ++k) total += obs[k]->L;
-    for (int l = 0; l < imc::kNumLevels; ++l)
-        if (!sch.is_wide[l] || sch.alphabet[l] <= HYBRID_MAX_ALPHABET) max_counted = std::max(max_counted, sch.alphabet[l]);
+    for (const imc::LevelRule &r : rules)
+        if (r.counted) max_counted = std::max(max_counted, r.alphabet);
     if (K == 0 || total == 0) return IMC_OK;
     if (total >= (size_t)1 << 31 || K > ENC_RUN_MAX_CHUNKS) return fail(IMC_ERR_ARG, "device encoder: too many elements or chunks in one run");
     const size_t tiles0 = (total + ENC_TILE - 1) / ENC_TILE;
@@ -501,66 +565,9 @@ int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, s
     std::vector<uint8_t *> hptr(K);
     uint32_t n = (uint32_t)total;
     int cur = 0;
+    size_t applied = 0;
 
-    auto run_pass = [&](const imc::EncodeSchedule::Pass &p) -> int {
-        const EncPass ps{dd->d_left, dd->d_right, p.z0, p.nz};
-        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
-        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
-        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
-        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
-                           buf[cur ^ 1].get());
-        HIP_TRY(hipGetLastError());
-        uint32_t hn = 0;
-        HIP_TRY(hipMemcpyAsync(&hn, new_n.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device encoder: a pass returned an impossible length");
-        n = hn;
-        cur ^= 1;
-        return IMC_OK;
-    };
-    auto snapshot = [&](int l) -> int {
-        const bool wide = sch.is_wide[l];
-        const int alphabet = sch.alphabet[l];
-        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
-        hipLaunchKernelGGL(k_enc_mark_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, sums.get());
-        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
-        hipLaunchKernelGGL(k_enc_mark_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, tile_in.get(), pos.get(), (uint32_t)K);
-        HIP_TRY(hipGetLastError());
-        uint32_t marks = 0;
-        HIP_TRY(hipMemcpyAsync(&marks, new_n.get(), sizeof marks, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(hpos.data(), pos.get(), (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        bool sane = marks == K && hpos[0] == 0 && hpos[K] == n;
-        for (size_t k = 0; k < K && sane; ++k) sane = hpos[k] < hpos[k + 1];
-        if (!sane) return fail(IMC_ERR_HIP, "device encoder: chunk starts lost");
-        for (size_t k = 0; k < K; ++k) {                        // upload_padded()'s shape: rounded up to 256 B plus 256 B, padding zeroed
-            const size_t len = hpos[k + 1] - hpos[k], bytes = ((len * (wide ? sizeof(imc::tok_t) : 1) + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
-            HIP_TRY(dev_alloc((void **)&obs[k]->d_tok[l], bytes));
-            HIP_TRY(hipMemsetAsync(obs[k]->d_tok[l], 0, bytes, g.stream));
-            obs[k]->ntok[l] = len;
-            hptr[k] = obs[k]->d_tok[l];
-        }
-        HIP_TRY(hipMemcpyAsync(dptr.get(), hptr.data(), K * sizeof(uint8_t *), hipMemcpyHostToDevice, g.stream));
-        hipLaunchKernelGGL(k_enc_snapshot, dim3((n + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, pos.get(),
-                           (uint32_t)K, dptr.get(), wide ? 0 : 1);
-        HIP_TRY(hipGetLastError());
-        const bool counted = !wide || alphabet <= HYBRID_MAX_ALPHABET;
-        if (counted) {
-            uint32_t longest = 1;
-            for (size_t k = 0; k < K; ++k) longest = std::max(longest, hpos[k + 1] - hpos[k]);
-            const uint32_t bx = std::max<uint32_t>(1, std::min<uint32_t>(128, (longest + 8 * ENC_THREADS - 1) / (8 * ENC_THREADS)));
-            HIP_TRY(hipMemsetAsync(counts.get(), 0, K * (size_t)alphabet * sizeof(uint32_t), g.stream));
-            hipLaunchKernelGGL(k_enc_histogram, dim3(bx, (uint32_t)K), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), pos.get(), alphabet, counts.get());
-            HIP_TRY(hipGetLastError());
-            hcounts.resize(K * (size_t)alphabet);
-            HIP_TRY(hipMemcpyAsync(hcounts.data(), counts.get(), hcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        if (counted)
-            for (size_t k = 0; k < K; ++k) obs[k]->tok_count[l].assign(hcounts.begin() + k * (size_t)alphabet, hcounts.begin() + (k + 1) * (size_t)alphabet);
-        return IMC_OK;
-    };
-    auto body = [&]() -> int {
+    auto setup = [&]() -> int {
         HIP_TRY(hipSetDevice(g.device));
         for (int b = 0; b < 2; ++b) HIP_TRY(buf[b].alloc((tiles0 * ENC_TILE + ENC_ITEMS) * sizeof(uint16_t)));
         HIP_TRY(flags.alloc(tiles0 * ENC_THREADS * sizeof(uint16_t)));
@@ -579,38 +586,72 @@ int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, s
             off += L;
         }
         HIP_TRY(hipGetLastError());
-        size_t applied = 0;
-        for (int l = 0; l < imc::kNumLevels; ++l) {             // install_encoding()'s rules, level by level
-            for (size_t k = 0; k < K; ++k) {
-                imc_obs *o = obs[k];
-                o->alphabet[l] = sch.alphabet[l];
-                o->wide[l] = sch.is_wide[l];
-                o->ntok[l] = o->L;
-                o->tok_count[l].clear();
-            }
-            if (l > 0 && sch.alphabet[l] == sch.alphabet[l - 1]) {
-                for (size_t k = 0; k < K; ++k) {
-                    imc_obs *o = obs[k];
-                    o->d_tok[l] = o->d_tok[l - 1]; o->wide[l] = o->wide[l - 1]; o->ntok[l] = o->ntok[l - 1]; o->tok_count[l] = o->tok_count[l - 1];
-                }
-                continue;
-            }
-            if (sch.alphabet[l] <= nsym) continue;              // raw stream: d_sym (d_tok stays null)
-            for (; applied < (size_t)sch.after[l]; ++applied)
-                if (int rc = run_pass(sch.passes[applied])) return rc;
-            if (int rc = snapshot(l)) return rc;
-        }
         return IMC_OK;
     };
-    const int rc = body();
-    if (rc != IMC_OK) {
-        const std::string msg = g_err;
-        (void)hipStreamSynchronize(g.stream);
-        for (size_t k = 0; k < K; ++k) release_tokens(obs[k]);
-        return fail(rc, msg);
+    auto run_pass = [&](const imc::EncodeSchedule::Pass &p) -> int {
+        const EncPass ps{dd->d_left, dd->d_right, p.z0, p.nz};
+        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
+        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
+        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
+                           buf[cur ^ 1].get());
+        HIP_TRY(hipGetLastError());
+        uint32_t hn = 0;
+        HIP_TRY(hipMemcpyAsync(&hn, new_n.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device encoder: a pass returned an impossible length");
+        n = hn;
+        cur ^= 1;
+        return IMC_OK;
+    };
+    auto snapshot = [&](int l, const imc::LevelRule &r) -> int {
+        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
+        hipLaunchKernelGGL(k_enc_mark_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
+        hipLaunchKernelGGL(k_enc_mark_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, tile_in.get(), pos.get(), (uint32_t)K);
+        HIP_TRY(hipGetLastError());
+        uint32_t marks = 0;
+        HIP_TRY(hipMemcpyAsync(&marks, new_n.get(), sizeof marks, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(hpos.data(), pos.get(), (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        bool sane = marks == K && hpos[0] == 0 && hpos[K] == n;
+        for (size_t k = 0; k < K && sane; ++k) sane = hpos[k] < hpos[k + 1];
+        if (!sane) return fail(IMC_ERR_HIP, "device encoder: chunk starts lost");
+        for (size_t k = 0; k < K; ++k) {
+            const size_t len = hpos[k + 1] - hpos[k];
+            HIP_TRY(alloc_level(obs[k], l, len * (r.is_wide ? sizeof(imc::tok_t) : 1)));
+            obs[k]->ntok[l] = len;
+            hptr[k] = obs[k]->d_tok[l];
+        }
+        HIP_TRY(hipMemcpyAsync(dptr.get(), hptr.data(), K * sizeof(uint8_t *), hipMemcpyHostToDevice, g.stream));
+        hipLaunchKernelGGL(k_enc_snapshot, dim3((n + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, pos.get(),
+                           (uint32_t)K, dptr.get(), r.is_wide ? 0 : 1);
+        HIP_TRY(hipGetLastError());
+        if (r.counted) {
+            uint32_t longest = 1;
+            for (size_t k = 0; k < K; ++k) longest = std::max(longest, hpos[k + 1] - hpos[k]);
+            const uint32_t bx = std::max<uint32_t>(1, std::min<uint32_t>(128, (longest + 8 * ENC_THREADS - 1) / (8 * ENC_THREADS)));
+            HIP_TRY(hipMemsetAsync(counts.get(), 0, K * (size_t)r.alphabet * sizeof(uint32_t), g.stream));
+            hipLaunchKernelGGL(k_enc_histogram, dim3(bx, (uint32_t)K), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), pos.get(), r.alphabet, counts.get());
+            HIP_TRY(hipGetLastError());
+            hcounts.resize(K * (size_t)r.alphabet);
+            HIP_TRY(hipMemcpyAsync(hcounts.data(), counts.get(), hcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (r.counted)
+            for (size_t k = 0; k < K; ++k)
+                obs[k]->tok_count[l].assign(hcounts.begin() + k * (size_t)r.alphabet, hcounts.begin() + (k + 1) * (size_t)r.alphabet);
+        return IMC_OK;
+    };
+    if (int rc = setup()) {
+        (void)hipStreamSynchronize(g.stream);        // (the scratch streams are freed on return)
+        return rc;
     }
-    for (size_t k = 0; k < K; ++k) obs[k]->dict = dd;
-    return IMC_OK;
+    return install_levels(dd, obs, K, rules, [&](int l, const imc::LevelRule &r) -> int {
+        for (; applied < (size_t)sch.after[l]; ++applied)
+            if (int rc = run_pass(sch.passes[applied])) return rc;
+        return snapshot(l, r);
+    });
 }
 
 int device_encode(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K)
@@ -628,68 +669,38 @@ int device_encode(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_
     return IMC_OK;
 }
 
+// Build a chunk from validated host symbols (exactly one of host / host16 is non-null when L > 0).  Called WITHOUT g_mu.
 int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym, imc_obs **out)
 {
-    // exactly one of host (alphabets up to 256: bytes) and host16 (larger alphabets) is non-null when L > 0
-    const bool wide_raw = nsym > imc::kByteAlphabet;
-    static const bool dbg_host = std::getenv("IMC_DEBUG_HOST") != nullptr;     // diagnostics: host time per phase
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
+    const HostSymbols sym{host, host16, L};
+    PhaseTimer tm;
     std::shared_ptr<DictDev> dd;
-    bool want_zip = false, train = false, on_device = false;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        if (int rc = ensure_ctx()) return rc;
-        on_device = g.device_encode == 1;
-        // ---- compression (the preprocess_raw_observations analogue, hmm.py:16) ----
-        want_zip = g.compression && L >= ZIP_MIN_COLUMNS && nsym < imc::kMaxAlphabet / 2;
-        if (want_zip) {
-            auto it = g.dicts.find(nsym);
-            if (it != g.dicts.end()) dd = it->second;
-            else train = L >= DICT_TRAIN_MIN;
-        }
-    }
-    if (train) {                                        // host only, unlocked
-        auto nd = make_dictionary(host, host16, L, nsym);
-        nd->trained_on = L;
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g.dicts.find(nsym);
-        if (it != g.dicts.end()) dd = it->second;       // another thread published one meanwhile: use that
-        else {
-            if (int rc = upload_dictionary(nd)) return rc;
-            g.dicts[nsym] = nd;
-            dd = nd;
-        }
-    }
-    const auto t1 = now();
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    const bool on_device = g.device_encode == 1;
+    if (int rc = dictionary_for(lk, L, nsym, [&](HostSymbols *s) -> int { *s = sym; return IMC_OK; }, &dd)) return rc;
+    lk.unlock();
+    tm.mark();
     imc::EncodedLevels enc;
     const bool zipped = dd && dd->dict.alphabet > nsym;
     // host only, unlocked (a published dictionary is immutable) - or, with imc_set_device_encoding(1), on the device below
     if (zipped && !on_device) imc::encode_levels(dd->dict, host, host16, L, enc);
-    const auto t2 = now();
+    tm.mark();
 
-    std::lock_guard<std::mutex> lk(g_mu);
+    lk.lock();
     if (int rc = ensure_ctx()) return rc;
     HIP_TRY(hipSetDevice(g.device));
-    auto *o = new (std::nothrow) imc_obs();
+    imc_obs *o = obs_new(L, nsym);
     if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    o->id = g.next_obs_id++;
-    o->pid = g.pid;
-    o->device = g.device;
-    o->nsym = nsym;
-    o->L = L;
-    o->d_sym = nullptr;
-    o->wide_raw = wide_raw;
-    for (int l = 0; l < imc::kNumLevels; ++l) { o->d_tok[l] = nullptr; o->wide[l] = false; o->ntok[l] = 0; o->alphabet[l] = nsym; }
-    hipError_t e = wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(host16), L * sizeof(imc::tok_t), &o->d_sym)
-                            : upload_padded(host, L, &o->d_sym);
+    const hipError_t e = o->wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(host16), L * sizeof(imc::tok_t), &o->d_sym)
+                                     : upload_padded(host, L, &o->d_sym);
     if (e != hipSuccess) {
+        obs_release(o);
         delete o;
         return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
                     std::string("observation upload: ") + hipGetErrorString(e));
     }
-    const auto t3 = now();
+    tm.mark();
     if (zipped) {
         if (int rc = on_device ? device_encode(dd, &o, 1) : install_encoding(o, dd, enc)) {
             obs_release(o);
@@ -697,18 +708,12 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
             return rc;
         }
     }
-    if (dbg_host)      // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
+    tm.mark();
+    if (PhaseTimer::enabled())   // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
         std::fprintf(stderr, "[imc host] create %zu columns: train %.1f ms, encode %.1f ms, upload %.1f ms, install %.1f ms (%s encoder)\n", L,
-                     ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()), on_device ? "device" : "host");
+                     tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
     *out = o;
     return IMC_OK;
-}
-
-// Columns of a chunk's head that make_dictionary() looks at: a dictionary trained on the head alone is the dictionary
-// trained on the whole chunk.
-size_t training_head(size_t L, bool wide_raw)
-{
-    return std::min(L, wide_raw ? DICT_WIDE_TRAIN_TOKENS * 8 + 1 : std::max(DICT_TRAIN_MAX + 1, DICT_WIDE_TRAIN_TOKENS * 96));
 }
 
 // d_sym must be device memory of the library's device, `bytes` long: an error, never a fault (g_mu held, context ready).
@@ -731,94 +736,144 @@ int check_device_range(const void *p, size_t bytes)
 }
 
 // Build a chunk from symbols in device memory (imc_obs_create_device; arguments already checked).  The device work is on
-// the library's stream under g_mu; dictionary training - on a head copied back, only when the alphabet has no dictionary
-// yet - runs unlocked like obs_upload's.
+// the library's stream under g_mu; only the head that training looks at comes back to the host, and only when the
+// alphabet has no dictionary yet.
 int obs_from_device(const void *d_src, size_t L, int nsym, int sym_bytes, hipStream_t user_stream, imc_obs **out)
 {
-    const bool wide_raw = nsym > imc::kByteAlphabet;
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    HIP_TRY(hipSetDevice(g.device));
+    if (L)
+        if (int rc = check_device_range(d_src, L * (size_t)sym_bytes)) return rc;
+    HIP_TRY(hipStreamSynchronize(user_stream));   // what the caller queued on its stream has produced the symbols
+    imc_obs *o = obs_new(L, nsym);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    const bool wide_raw = o->wide_raw;
     const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
-    std::shared_ptr<DictDev> dd;
-    bool train = false;
-    imc_obs *o = nullptr;
-    std::vector<uint8_t> head;
-    auto drop = [&](int rc) {                       // (g_mu held)
+    auto work = [&]() -> int {
+        HIP_TRY(alloc_padded(L * unit, &o->d_sym));
+        if (!L) return hipStreamSynchronize(g.stream) == hipSuccess ? IMC_OK : fail(IMC_ERR_HIP, "stream synchronisation failed");
+        DevBuf<uint32_t> first_bad;
+        HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
+        const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
+        hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
+        hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, o->d_sym, wide_raw ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        uint32_t bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (bad != 0xffffffffu) {
+            int32_t v = 0;
+            uint8_t raw[4] = {0, 0, 0, 0};
+            HIP_TRY(hipMemcpy(raw, (const char *)d_src + (size_t)bad * sym_bytes, sym_bytes, hipMemcpyDeviceToHost));
+            if (sym_bytes == 1) v = raw[0];
+            else if (sym_bytes == 2) { uint16_t u; std::memcpy(&u, raw, 2); v = u; }
+            else std::memcpy(&v, raw, 4);
+            return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(v) + " at column " + std::to_string(bad) + " outside [0,nsym)");
+        }
+        std::shared_ptr<DictDev> dd;
+        std::vector<uint8_t> head;
+        auto copy_head = [&](HostSymbols *s) -> int {
+            head.resize(imc::training_head(L, wide_raw) * unit);
+            HIP_TRY(hipMemcpy(head.data(), o->d_sym, head.size(), hipMemcpyDeviceToHost));
+            *s = symbols_in(head, wide_raw);
+            return IMC_OK;
+        };
+        if (int rc = dictionary_for(lk, L, nsym, copy_head, &dd)) return rc;
+        std::vector<uint8_t>().swap(head);
+        return dd && dd->dict.alphabet > nsym ? device_encode(dd, &o, 1) : IMC_OK;
+    };
+    if (int rc = work()) {
         const std::string msg = g_err;
         obs_release(o);
         delete o;
         return fail(rc, msg);
-    };
+    }
+    *out = o;
+    return IMC_OK;
+}
+
+// The deepest level within alphabet_limit at which the chunk holds a token stream; -1: none, its raw symbols
+// (the imc_obs_* read-outs).
+int token_level(const imc_obs *obs, int alphabet_limit)
+{
+    int level = -1;
+    if (obs->dict)
+        for (int l = 0; l < imc::kNumLevels; ++l)
+            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) level = l;
+    return level;
+}
+
+// Joint re-compression of the chunks of one alphabet (imc_obs_recompress), called without g_mu: a new dictionary is
+// trained on a sample drawn evenly from ALL the chunks, they are re-encoded with it, and it replaces the alphabet's
+// dictionary.
+int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
+{
+    // (in creation order, not in address order: the training sample is the concatenation of the chunks' heads, and with
+    // pointer order the dictionary - alphabet, token counts, now and then whether the byte phase filled its 256 entries
+    // at all - changed from run to run of the same program)
+    std::sort(obs.begin(), obs.end(), [](const imc_obs *x, const imc_obs *y) { return x->id < y->id; });
+    obs.erase(std::unique(obs.begin(), obs.end()), obs.end());
+    const bool wide_raw = nsym > imc::kByteAlphabet;
+    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
+    PhaseTimer tm;
+    size_t total = 0;
+    for (imc_obs *o : obs) total += o->L;
+    if (total < imc::TrainLimits().train_min) return IMC_OK;
+    // ---- sample: the raw symbols come back to the host (the chunks keep them on the device) - all of them for the host
+    //      encoder, only the training heads when the device encodes ----
+    const size_t share = imc::recompress_share(obs.size(), wide_raw);
+    std::vector<std::vector<uint8_t>> raw(obs.size());
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        if (int rc = ensure_ctx()) return rc;
+        // nothing to gain if these chunks already share a dictionary trained on at least this much data
+        // (a second Likelihood over the same forwarders, a subset of a recompressed set)
+        bool same = obs[0]->dict != nullptr;
+        for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
+        if (same && obs[0]->dict->trained_on >= total) return IMC_OK;
         HIP_TRY(hipSetDevice(g.device));
-        if (L)
-            if (int rc = check_device_range(d_src, L * (size_t)sym_bytes)) return rc;
-        HIP_TRY(hipStreamSynchronize(user_stream));   // what the caller queued on its stream has produced the symbols
-        o = new (std::nothrow) imc_obs();
-        if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-        o->id = g.next_obs_id++;
-        o->pid = g.pid;
-        o->device = g.device;
-        o->nsym = nsym;
-        o->L = L;
-        o->d_sym = nullptr;
-        o->wide_raw = wide_raw;
-        for (int l = 0; l < imc::kNumLevels; ++l) { o->d_tok[l] = nullptr; o->wide[l] = false; o->ntok[l] = 0; o->alphabet[l] = nsym; }
-        auto work = [&]() -> int {
-            const size_t bytes = ((L * unit + OBS_PAD - 1) / OBS_PAD) * OBS_PAD + OBS_PAD;
-            HIP_TRY(dev_alloc((void **)&o->d_sym, bytes));
-            HIP_TRY(hipMemsetAsync(o->d_sym, 0, bytes, g.stream));
-            if (!L) return hipStreamSynchronize(g.stream) == hipSuccess ? IMC_OK : fail(IMC_ERR_HIP, "stream synchronisation failed");
-            DevBuf<uint32_t> first_bad;
-            HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
-            const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
-            hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
-            hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, o->d_sym, wide_raw ? 1 : 0);
-            HIP_TRY(hipGetLastError());
-            uint32_t bad = 0;
-            HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            if (bad != 0xffffffffu) {
-                int32_t v = 0;
-                uint8_t raw[4] = {0, 0, 0, 0};
-                HIP_TRY(hipMemcpy(raw, (const char *)d_src + (size_t)bad * sym_bytes, sym_bytes, hipMemcpyDeviceToHost));
-                if (sym_bytes == 1) v = raw[0];
-                else if (sym_bytes == 2) { uint16_t u; std::memcpy(&u, raw, 2); v = u; }
-                else std::memcpy(&v, raw, 4);
-                return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(v) + " at column " + std::to_string(bad) + " outside [0,nsym)");
-            }
-            if (g.compression && L >= ZIP_MIN_COLUMNS && nsym < imc::kMaxAlphabet / 2) {
-                auto it = g.dicts.find(nsym);
-                if (it != g.dicts.end()) dd = it->second;
-                else train = L >= DICT_TRAIN_MIN;
-            }
-            if (train) {                              // only the head that training looks at comes back
-                head.resize(training_head(L, wide_raw) * unit);
-                HIP_TRY(hipMemcpy(head.data(), o->d_sym, head.size(), hipMemcpyDeviceToHost));
-            }
-            return IMC_OK;
-        };
-        if (int rc = work()) return drop(rc);
-    }
-    if (train) {                                        // host only, unlocked
-        auto nd = wide_raw ? make_dictionary(nullptr, reinterpret_cast<const imc::tok_t *>(head.data()), head.size() / unit, nsym)
-                           : make_dictionary(head.data(), nullptr, head.size(), nsym);
-        nd->trained_on = L;
-        std::vector<uint8_t>().swap(head);
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g.dicts.find(nsym);
-        if (it != g.dicts.end()) dd = it->second;
-        else {
-            if (int rc = upload_dictionary(nd)) return drop(rc);
-            g.dicts[nsym] = nd;
-            dd = nd;
+        for (size_t k = 0; k < obs.size(); ++k) {
+            raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
+            HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
         }
     }
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (dd && dd->dict.alphabet > nsym)
-        if (int rc = device_encode(dd, &o, 1)) return drop(rc);
-    *out = o;
+    std::vector<uint8_t> sample = imc::recompress_sample(raw, share, unit);
+    tm.mark();
+    // ---- train (host, unlocked) ----
+    const std::shared_ptr<DictDev> nd = make_dictionary(symbols_in(sample, wide_raw), nsym, total);
+    std::vector<uint8_t>().swap(sample);
+    tm.mark();
+    // ---- encode (host encoder only; unlocked) ----
+    std::vector<imc::EncodedLevels> enc(obs.size());
+    const bool zipped = nd->dict.alphabet > nsym;
+    if (zipped && !on_device)
+        for (size_t k = 0; k < obs.size(); ++k) {
+            const HostSymbols sym = symbols_in(raw[k], wide_raw);
+            imc::encode_levels(nd->dict, sym.bytes, sym.wide, obs[k]->L, enc[k]);
+            std::vector<uint8_t>().swap(raw[k]);
+        }
+    tm.mark();
+    // ---- install: swap the streams in under the lock ----
+    std::unique_lock<std::mutex> lk(g_mu);
+    wait_all_idle(lk);
+    HIP_TRY(hipSetDevice(g.device));
+    HIP_TRY(hipDeviceSynchronize());                 // nothing of these chunks is in flight any more
+    drop_plans_using(obs.data(), obs.size());        // plans hold raw pointers into the old streams
+    if (!zipped) return IMC_OK;                      // (incompressible sample: keep what the chunks have)
+    if (int rc = publish_dictionary(nsym, nd)) return rc;   // later chunks of this alphabet share it too
+    if (on_device) {                                 // all chunks of the alphabet in one batched run of passes
+        for (imc_obs *o : obs) release_tokens(o);
+        if (int rc = device_encode(nd, obs.data(), obs.size())) return rc;
+    } else
+        for (size_t k = 0; k < obs.size(); ++k) {
+            release_tokens(obs[k]);
+            if (int rc = install_encoding(obs[k], nd, enc[k])) return rc;
+        }
+    tm.mark();
+    if (PhaseTimer::enabled())
+        std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder)\n",
+                     obs.size(), total, tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
     return IMC_OK;
 }
 
@@ -2622,22 +2677,15 @@ int imc_obs_nsym(const imc_obs *obs) { return obs ? obs->nsym : 0; }
 size_t imc_obs_compressed_length(const imc_obs *obs, int alphabet_limit, int *alphabet_used)
 {
     if (!obs) return 0;
-    size_t n = obs->L;
-    int used = obs->nsym;
-    if (obs->dict)
-        for (int l = 0; l < imc::kNumLevels; ++l)
-            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) { n = obs->ntok[l]; used = obs->alphabet[l]; }
-    if (alphabet_used) *alphabet_used = used;
-    return n;
+    const int level = token_level(obs, alphabet_limit);
+    if (alphabet_used) *alphabet_used = level >= 0 ? obs->alphabet[level] : obs->nsym;
+    return level >= 0 ? obs->ntok[level] : obs->L;
 }
 
 int imc_obs_dictionary(const imc_obs *obs, int alphabet_limit, uint16_t *left, uint16_t *right, size_t capacity, int *alphabet_used)
 {
     if (!obs || !alphabet_used) return fail(IMC_ERR_ARG, "null argument");
-    int used = obs->nsym;
-    if (obs->dict)
-        for (int l = 0; l < imc::kNumLevels; ++l)
-            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) used = obs->alphabet[l];
+    const int level = token_level(obs, alphabet_limit), used = level >= 0 ? obs->alphabet[level] : obs->nsym;
     *alphabet_used = used;
     if ((left || right) && capacity < (size_t)(used - obs->nsym)) return fail(IMC_ERR_ARG, "capacity smaller than the number of merged tokens");
     for (int z = obs->nsym; z < used; ++z) {
@@ -2652,13 +2700,10 @@ int imc_obs_tokens(const imc_obs *obs, int alphabet_limit, uint16_t *tokens, siz
     if (!obs || !length) return fail(IMC_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lk(g_mu);
     if (obs->pid != getpid()) return fail(IMC_ERR_ARG, "chunk handle was created in another process");
-    int level = -1, used = obs->nsym;
-    if (obs->dict)
-        for (int l = 0; l < imc::kNumLevels; ++l)
-            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) { level = l; used = obs->alphabet[l]; }
+    const int level = token_level(obs, alphabet_limit);
     const size_t n = level >= 0 ? obs->ntok[level] : obs->L;
     *length = n;
-    if (alphabet_used) *alphabet_used = used;
+    if (alphabet_used) *alphabet_used = level >= 0 ? obs->alphabet[level] : obs->nsym;
     if (!tokens) return IMC_OK;
     if (capacity < n) return fail(IMC_ERR_ARG, "capacity smaller than the stream");
     if (int rc = ensure_ctx()) return rc;
@@ -2675,8 +2720,8 @@ int imc_obs_tokens(const imc_obs *obs, int alphabet_limit, uint16_t *tokens, siz
 }
 
 // Joint re-compression (see the header).  The first sufficiently long chunk of an alphabet trains the dictionary that
-// every later chunk shares; when a data set arrives as many chunks, that sample is one chunk.  Here a new dictionary
-// is trained on a sample drawn evenly from ALL the given chunks and they are re-encoded with it.
+// every later chunk shares; when a data set arrives as many chunks, that sample is one chunk: recompress_alphabet()
+// replaces it, alphabet by alphabet.
 int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
 {
     if (n_chunks < 0 || (n_chunks > 0 && !chunks)) return fail(IMC_ERR_ARG, "chunks is null");
@@ -2691,94 +2736,11 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
             imc_obs *o = chunks[f];
             if (!o) return fail(IMC_ERR_ARG, "chunk is null");
             if (o->pid != g.pid) return fail(IMC_ERR_HIP, "chunk was created in another process");
-            if (o->L >= ZIP_MIN_COLUMNS && o->nsym < imc::kMaxAlphabet / 2) by_alphabet[o->nsym].push_back(o);
+            if (imc::compressible(o->L, o->nsym)) by_alphabet[o->nsym].push_back(o);
         }
     }
-    for (auto &kv : by_alphabet) {
-        const int nsym = kv.first;
-        std::vector<imc_obs *> &obs = kv.second;
-        // (in creation order, not in address order: the training sample is the concatenation of the chunks' heads, and with
-        // pointer order the dictionary - alphabet, token counts, now and then whether the byte phase filled its 256 entries
-        // at all - changed from run to run of the same program)
-        std::sort(obs.begin(), obs.end(), [](const imc_obs *x, const imc_obs *y) { return x->id < y->id; });
-        obs.erase(std::unique(obs.begin(), obs.end()), obs.end());
-        const bool wide_raw = nsym > imc::kByteAlphabet;
-        const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
-        static const bool dbg_host = std::getenv("IMC_DEBUG_HOST") != nullptr;     // diagnostics: host time per phase
-        auto now = [] { return std::chrono::steady_clock::now(); };
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        const auto t0 = now();
-        size_t total = 0;
-        for (imc_obs *o : obs) total += o->L;
-        if (total < DICT_TRAIN_MIN) continue;
-        {   // nothing to gain if these chunks already share a dictionary trained on at least this much data
-            // (a second Likelihood over the same forwarders, a subset of a recompressed set)
-            std::lock_guard<std::mutex> lk(g_mu);
-            bool same = obs[0]->dict != nullptr;
-            for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
-            if (same && obs[0]->dict->trained_on >= total) continue;
-        }
-        // ---- training sample: an equal share of every chunk (its head), up to the training budget ----
-        const size_t budget = wide_raw ? DICT_WIDE_TRAIN_TOKENS * 8 : std::max(DICT_TRAIN_MAX, DICT_WIDE_TRAIN_TOKENS * 96);
-        const size_t share = std::max<size_t>(DICT_TRAIN_MIN, budget / obs.size());
-        // ---- raw symbols back to the host (the chunks keep them on the device): all of them for the host encoder, only
-        //      the training heads when the device encodes ----
-        std::vector<std::vector<uint8_t>> raw(obs.size());
-        {
-            std::lock_guard<std::mutex> lk(g_mu);
-            HIP_TRY(hipSetDevice(g.device));
-            for (size_t k = 0; k < obs.size(); ++k) {
-                raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
-                HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
-            }
-        }
-        std::vector<uint8_t> sample;
-        for (size_t k = 0; k < obs.size(); ++k) {
-            const size_t n = std::min(obs[k]->L, share);
-            sample.insert(sample.end(), raw[k].begin(), raw[k].begin() + n * unit);
-        }
-        const size_t ns = sample.size() / unit;
-        const auto t1 = now();
-        auto nd = wide_raw ? make_dictionary(nullptr, reinterpret_cast<const imc::tok_t *>(sample.data()), ns, nsym)
-                           : make_dictionary(sample.data(), nullptr, ns, nsym);
-        std::vector<uint8_t>().swap(sample);
-        nd->trained_on = total;
-        const auto t2 = now();
-        // ---- re-encode (host, unlocked), then swap the streams in under the lock ----
-        std::vector<imc::EncodedLevels> enc(obs.size());
-        const bool zipped = nd->dict.alphabet > nsym;
-        if (zipped && !on_device)
-            for (size_t k = 0; k < obs.size(); ++k) {
-                if (wide_raw) imc::encode_levels(nd->dict, nullptr, reinterpret_cast<const imc::tok_t *>(raw[k].data()), obs[k]->L, enc[k]);
-                else imc::encode_levels(nd->dict, raw[k].data(), nullptr, obs[k]->L, enc[k]);
-                std::vector<uint8_t>().swap(raw[k]);
-            }
-        const auto t3 = now();
-        auto report = [&] {
-            if (dbg_host)
-                std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder)\n",
-                             obs.size(), total, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()), on_device ? "device" : "host");
-        };
-        std::unique_lock<std::mutex> lk(g_mu);
-        wait_all_idle(lk);
-        HIP_TRY(hipSetDevice(g.device));
-        HIP_TRY(hipDeviceSynchronize());                 // nothing of these chunks is in flight any more
-        drop_plans_using(obs.data(), obs.size());        // plans hold raw pointers into the old streams
-        if (!zipped) continue;                           // (incompressible sample: keep what the chunks have)
-        if (int rc = upload_dictionary(nd)) return rc;
-        g.dicts[nsym] = nd;                              // later chunks of this alphabet share it too
-        if (on_device) {                                 // all chunks of the alphabet in one batched run of passes
-            for (imc_obs *o : obs) release_tokens(o);
-            if (int rc = device_encode(nd, obs.data(), obs.size())) return rc;
-            report();
-            continue;
-        }
-        for (size_t k = 0; k < obs.size(); ++k) {
-            release_tokens(obs[k]);
-            if (int rc = install_encoding(obs[k], nd, enc[k])) return rc;
-        }
-        report();
-    }
+    for (auto &kv : by_alphabet)
+        if (int rc = recompress_alphabet(kv.first, kv.second, on_device)) return rc;
     return IMC_OK;
 }
 
@@ -2799,10 +2761,7 @@ int imc_obs_token_counts(const imc_obs *obs, int alphabet_limit, uint32_t *count
     if (!obs || !alphabet_used) return fail(IMC_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lk(g_mu);
     if (obs->pid != getpid()) return fail(IMC_ERR_ARG, "chunk handle was created in another process");
-    int level = -1, used = obs->nsym;
-    if (obs->dict)
-        for (int l = 0; l < imc::kNumLevels; ++l)
-            if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) { level = l; used = obs->alphabet[l]; }
+    const int level = token_level(obs, alphabet_limit), used = level >= 0 ? obs->alphabet[level] : obs->nsym;
     *alphabet_used = used;
     if (!counts) return IMC_OK;
     if (capacity < (size_t)used) return fail(IMC_ERR_ARG, "capacity smaller than the alphabet");

@@ -18,6 +18,8 @@
 //   * position 0 of a chunk is never merged (it is consumed by pi .* E[:,o_0]).
 // The result is exact whatever the parse: a token's operator is the ordered product of its two
 // halves' operators.
+// In the order of this file: the dictionary, training (one merge at a time, then rounds), encoding at
+// every level, and the training policy (which chunks, which sample, which thresholds).
 #pragma once
 
 #include <algorithm>
@@ -109,6 +111,15 @@ inline std::vector<int> dict_depths(const PairDict &d)
     std::vector<int> depth((size_t)d.alphabet, 0);
     for (int z = d.nsym; z < d.alphabet; ++z) depth[z] = 1 + std::max(depth[d.left[z]], depth[d.right[z]]);
     return depth;
+}
+
+// The dictionary's merged tokens (ids S .. alphabet-1) sorted by (depth, id); `depth` from dict_depths().
+inline std::vector<tok_t> dict_order(const PairDict &d, const std::vector<int> &depth)
+{
+    std::vector<tok_t> order;
+    for (int z = d.nsym; z < d.alphabet; ++z) order.push_back((tok_t)z);
+    std::stable_sort(order.begin(), order.end(), [&](tok_t x, tok_t y) { return depth[x] < depth[y]; });
+    return order;
 }
 
 inline void train_dict(PairDict &d, int nsym, std::vector<uint8_t> seq, size_t min_count, int max_depth = 0)
@@ -299,6 +310,97 @@ inline void encode_levels(const PairDict &d, const uint8_t *obs, const tok_t *ob
         out.length[lvl] = n;
         out.is_wide[lvl] = d.alphabet > kByteAlphabet;
     }
+}
+
+// ---- training policy ---------------------------------------------------------------------------------
+// Which chunks are compressed, what a dictionary is trained on and with which thresholds.  Host only and free of the
+// library's state: imcoal_fwd.hip reads IMC_DICT_MIN_COUNT / IMC_DICT_MAX_DEPTH at every training and passes them in,
+// tests/chunk_policy_check.cpp runs the same functions with scaled-down limits.
+struct TrainLimits {
+    size_t zip_min_columns = 4096;                 // ZIP_MIN_COLUMNS: shorter chunks are not worth compressing
+    size_t train_min = 32768;                      // first chunk at least this long trains the dictionary
+    size_t train_max = 8u << 20;                   // byte tokens (< 256): train on at most this prefix
+    size_t wide_train_tokens = 1u << 19;           // 16-bit tokens: train on at most this many byte-level tokens (~4e7 columns)
+    size_t wide_min_count = 6;                     // ... in which a pair must occur this often
+    int max_depth = 0;                             // 0: no limit on a token's depth in the dictionary.  (IMC_DICT_MAX_DEPTH, experiments:
+                                                   // the table is built one depth per launch, but the bench alignment's 4096 tokens USE
+                                                   // their 11 depths - a cap of 10 saves one launch at 149.5 instead of 150.2 columns per
+                                                   // token, 9 already costs 13 % of the compression, 8 leaves 208 tokens)
+};
+
+inline bool compressible(size_t L, int nsym, const TrainLimits &lim = TrainLimits()) { return L >= lim.zip_min_columns && nsym < kMaxAlphabet / 2; }
+
+struct TrainedDict {                               // what training gives: the dictionary and what the table build needs of it
+    PairDict dict;
+    std::vector<int> depth;                        // per token; raw symbols have depth 0
+    std::vector<tok_t> order;                      // merged tokens sorted by (depth, id)
+};
+
+// A pair becomes a 16-bit token when it occurs this often in the training sample: lim.wide_min_count in a full
+// sample, fewer in a short one - the dictionary of the FIRST chunk serves every later chunk of the alphabet, and a
+// workload of many 1e7-column chunks (BASELINE config[3]) trains on one of them: with the full-sample threshold it got
+// 1553 tokens (141 columns per token), with 3 occurrences 3473 (155) and a 3 % shorter evaluation; a token that turns
+// out to be rare costs one table entry.  (forced > 0 overrides - IMC_DICT_MIN_COUNT: experiments.)
+inline size_t wide_min_count(size_t sample_tokens, size_t forced, const TrainLimits &lim = TrainLimits())
+{
+    if (forced) return forced;
+    return sample_tokens >= 400000 ? lim.wide_min_count : sample_tokens >= 200000 ? 4 : 3;
+}
+
+// Train a pair dictionary on L symbols (exactly one of host / host16 is non-null).  forced_min_count: see
+// wide_min_count(); max_depth: see train_dict().
+inline TrainedDict train_dictionary(const uint8_t *host, const tok_t *host16, size_t L, int nsym, size_t forced_min_count, int max_depth,
+                                    const TrainLimits &lim = TrainLimits())
+{
+    TrainedDict t;
+    if (host16) {                                    // symbols are not bytes: straight to the 16-bit rounds on the raw stream
+        init_dict(t.dict, nsym);
+        const size_t nt = std::min(L - 1, lim.wide_train_tokens * 8);
+        train_dict_wide(t.dict, std::vector<tok_t>(host16 + 1, host16 + 1 + nt), lim.wide_min_count, max_depth);
+    } else {
+        const size_t n = std::min(L - 1, lim.train_max);
+        train_dict(t.dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), 64, max_depth);
+        // The 16-bit rounds only start from a FULL byte dictionary.  On a large sample the byte phase can stop a few entries
+        // short (the best remaining pair under the depth cap has 63 occurrences) - and the chunk then has no level beyond
+        // ~250 tokens at all (seen once in a bench run: 96 instead of 150 columns per token, every evaluation 25-40 %
+        // slower).  Retrain with a lower threshold rather than lose the wide levels.
+        for (size_t min_count : {(size_t)8, (size_t)2}) {
+            if (t.dict.alphabet >= kByteAlphabet || t.dict.alphabet < 3 * kByteAlphabet / 4 || n < lim.train_min) break;
+            train_dict(t.dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), min_count, max_depth);
+        }
+        if (t.dict.alphabet >= kByteAlphabet) {      // 16-bit tokens: rounds over the whole chunk's byte-level stream
+            const size_t cols = std::min(L, lim.wide_train_tokens * 96);   // a byte-level token covers ~60-100 columns
+            const std::vector<uint8_t> lvl256 = encode_bytes(t.dict, host, cols, nullptr);
+            const size_t nt = std::min(lvl256.size() - 1, lim.wide_train_tokens);
+            train_dict_wide(t.dict, std::vector<tok_t>(lvl256.begin() + 1, lvl256.begin() + 1 + nt), wide_min_count(nt, forced_min_count, lim), max_depth);
+        }
+    }
+    t.depth = dict_depths(t.dict);
+    t.order = dict_order(t.dict, t.depth);
+    return t;
+}
+
+// Columns of a chunk's head that train_dictionary() looks at: a dictionary trained on the head alone is the dictionary
+// trained on the whole chunk.
+inline size_t training_head(size_t L, bool wide_raw, const TrainLimits &lim = TrainLimits())
+{
+    return std::min(L, wide_raw ? lim.wide_train_tokens * 8 + 1 : std::max(lim.train_max + 1, lim.wide_train_tokens * 96));
+}
+
+// Joint re-compression trains on an equal share of every chunk (its head), up to the training budget: the symbols per chunk.
+inline size_t recompress_share(size_t n_chunks, bool wide_raw, const TrainLimits &lim = TrainLimits())
+{
+    const size_t budget = wide_raw ? lim.wide_train_tokens * 8 : std::max(lim.train_max, lim.wide_train_tokens * 96);
+    return std::max(lim.train_min, budget / n_chunks);
+}
+
+// ... and the sample itself: the first min(L_k, share) symbols of every chunk, in the order given.  raw[k] holds chunk k's
+// symbols (`unit` bytes each) from its first one - all of them, or any head of at least min(L_k, share).
+inline std::vector<uint8_t> recompress_sample(const std::vector<std::vector<uint8_t>> &raw, size_t share, size_t unit)
+{
+    std::vector<uint8_t> sample;
+    for (const std::vector<uint8_t> &r : raw) sample.insert(sample.end(), r.begin(), r.begin() + std::min(r.size() / unit, share) * unit);
+    return sample;
 }
 
 }  // namespace imc

@@ -23,15 +23,6 @@ struct TableSchedule {
     std::vector<std::pair<int, int>> launches;
 };
 
-// The dictionary's merged tokens (ids S .. alphabet-1) sorted by (depth, id); `depth` from dict_depths().
-inline std::vector<tok_t> dict_order(const PairDict &d, const std::vector<int> &depth)
-{
-    std::vector<tok_t> order;
-    for (int z = d.nsym; z < d.alphabet; ++z) order.push_back((tok_t)z);
-    std::stable_sort(order.begin(), order.end(), [&](tok_t x, tok_t y) { return depth[x] < depth[y]; });
-    return order;
-}
-
 // Merged tokens of a level's alphabet (ids S .. A-1) grouped by dictionary depth: the tokens of the k-th depth present
 // are order[lvl[k] .. lvl[k+1]).
 struct DepthOrder {

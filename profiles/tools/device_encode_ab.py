@@ -10,13 +10,15 @@ Workloads (3 symbols, bench.py's generator and seeds):
     one1e8   create 1 x 1e8 columns                         (bench.py's default workload)
     c32      create 32 x 1e7 columns, then recompress       (the per-GPU slice of BASELINE config[3])
     a100     create 100 x 1e6 columns, then recompress      (the reference authors' data scale)
-Legs: parent (the parent commit's package and library), switch0 (this tree, host encoder: the default), switch1 (this tree, device
-encoder).  Every measurement is one fresh child process under its own `timeout`; the legs are interleaved (parent,
+Legs: parent (the parent commit's package and library, its default encoder: the host's), parent1 (the same with its device
+encoder; --parent-device, for a parent that has one), switch0 (this tree, host encoder: the default), switch1 (this tree,
+device encoder).  Every measurement is one fresh child process under its own `timeout`; the legs are interleaved (parent,
 switch0, switch1, parent, ...); the data is generated once by this driver, which never touches the GPU, and handed over
 as .npy files.  A child creates the device context with an untimed imc_set_device(0) first, so the figures are the
 chunk work alone (bench.py's setup_s also holds the context creation).  Reported: median [min .. max] over the runs.
-The phase split is the library's own IMC_DEBUG_HOST=1 report and exists for this tree's legs only.  A child that fails
-ends the whole run."""
+The phase split is the library's own IMC_DEBUG_HOST=1 report.  With --parent-device the summary ends with this tree
+against the parent per workload and encoder: the difference of the medians beside the min .. max spread of the parent's
+own runs.  A child that fails ends the whole run."""
 import argparse
 import json
 import os
@@ -47,7 +49,7 @@ def child(workload, leg, data_dir, tree):
     lib = _capi.lib()
     _capi.check(lib.imc_set_device(0))                         # context creation, untimed
     if leg != "parent":
-        _capi.check(lib.imc_set_device_encoding(1 if leg == "switch1" else 0))
+        _capi.check(lib.imc_set_device_encoding(1 if leg.endswith("1") else 0))
     t0 = time.perf_counter()
     fw = [Forwarder.from_array(a, 3) for a in arrays]
     t1 = time.perf_counter()
@@ -81,6 +83,7 @@ def phases(stderr):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree")
+    ap.add_argument("--parent-device", action="store_true", help="also run the parent with its device encoder (leg parent1)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "device_encode_ab.txt"))
     ap.add_argument("--workloads", default="one1e8,c32,a100")
@@ -93,6 +96,7 @@ def main():
     sys.path.insert(0, REPO)
     import bench
     names = [w for w in args.workloads.split(",") if w]
+    legs = ("parent", "parent1", "switch0", "switch1") if args.parent_device else LEGS
     lines = []
 
     def say(text):
@@ -110,11 +114,11 @@ def main():
         say("# data generated in %.0f s (bench.py's generator and seeds)" % (time.time() - t0))
         for run in range(args.runs):
             for w in names:
-                for leg in LEGS:
+                for leg in legs:
                     env = dict(os.environ, IMC_DEBUG_HOST="1")
                     env.pop("IMC_DEVICE_ENCODE", None)
                     env.pop("IMCOAL_FWD_LIB", None)
-                    tree = os.path.abspath(args.parent_tree) if leg == "parent" else REPO
+                    tree = os.path.abspath(args.parent_tree) if leg.startswith("parent") else REPO
                     cmd = ["timeout", "-k", "10", str(WORKLOADS[w]["limit"]), sys.executable, os.path.abspath(__file__), "--child", w, leg, data_dir, tree]
                     out = subprocess.run(cmd, capture_output=True, text=True, env=env)
                     res = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -132,10 +136,10 @@ def main():
 
     say("#\n# summary (seconds)")
     for w in names:
-        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"]) for leg in LEGS for r in results[(w, leg)]}
+        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"]) for leg in legs for r in results[(w, leg)]}
         say("# %s: token streams of all legs and runs %s" % (w, "IDENTICAL (alphabet, token total, crc32 of the first and last chunk's deepest stream)"
                                                               if len(same) == 1 else "DIFFER: %r" % sorted(same)))
-        for leg in LEGS:
+        for leg in legs:
             rs = results[(w, leg)]
             say("%-7s %-8s create %s   recompress %s   total %s" % (
                 w, leg, stat([r["create_s"] for r in rs]), stat([r["recompress_s"] for r in rs]), stat([r["create_s"] + r["recompress_s"] for r in rs])))
@@ -143,6 +147,13 @@ def main():
             if keys:
                 say("#        %-8s phases, ms, median over runs (summed over the chunks of a run): %s" % (
                     leg, "; ".join("%s %.0f" % (k, float(np.median([r["phases"].get(k, 0.0) for r in rs]))) for k in keys)))
+    if args.parent_device:
+        say("#\n# this tree against the parent, total seconds: difference of medians | spread (max - min) of the parent's own runs")
+        for w in names:
+            for mine, theirs in (("switch0", "parent"), ("switch1", "parent1")):
+                tot = {leg: [r["create_s"] + r["recompress_s"] for r in results[(w, leg)]] for leg in (mine, theirs)}
+                diff, spread = float(np.median(tot[mine]) - np.median(tot[theirs])), max(tot[theirs]) - min(tot[theirs])
+                say("%-7s %-8s - %-8s %+8.3f | %7.3f   %s" % (w, mine, theirs, diff, spread, "inside" if abs(diff) <= spread else "OUTSIDE"))
     with open(args.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return 0
