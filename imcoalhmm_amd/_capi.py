@@ -70,6 +70,9 @@ SIGNATURES = [
     ("imc_set_compression", ctypes.c_int, [ctypes.c_int]),
     ("imc_dictionary_reset", ctypes.c_int, []),
     ("imc_set_device_encoding", ctypes.c_int, [ctypes.c_int]),
+    ("imc_set_device_ingest", ctypes.c_int, [ctypes.c_int]),
+    ("imc_obs_create_pairwise", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _vpp]),
+    ("imc_last_ingest", ctypes.c_int, [_u64p]),
     ("imc_profile_enable", ctypes.c_int, [ctypes.c_int]),
     ("imc_profile_read", ctypes.c_int, [_dp, _dp, _u64p, _u64p]),
     ("imc_last_rank1", ctypes.c_int, [_u64p, _u64p]),
@@ -184,6 +187,15 @@ def set_wide_blocked(mode):
     """25-32 states on the register-blocked fp64-MFMA scan (k_zpropagate4<7 | 8>): -1 = where the planner's estimate
     prefers it (default), 0 = never, 1 = wherever every dictionary of the call has a token level the scan can run."""
     check(lib().imc_set_wide_blocked(int(mode)))
+
+
+def last_ingest():
+    """Dict view of imc_last_ingest(): how the last chunk of this process was created.  ``path`` is "host", "text",
+    "cache" or "pairwise" (the last three: on the device)."""
+    arr = (ctypes.c_uint64 * 4)()
+    check(lib().imc_last_ingest(arr))
+    return {"path": ("host", "text", "cache", "pairwise")[int(arr[0])], "bytes": int(arr[1]), "slabs": int(arr[2]),
+            "columns": int(arr[3])}
 
 
 def last_plan():

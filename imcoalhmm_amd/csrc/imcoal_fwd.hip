@@ -18,8 +18,9 @@
 //
 // Host side, in the order of this file: context and device memory (dev_alloc, DevBuf); chunks and dictionaries (the
 // pieces a chunk is made of - padded buffers, obs_new, dictionary_for - then the one level loop install_levels with its
-// host and device sources, obs_upload / obs_from_device, recompress_alphabet; the training policy is pair_dict.hpp's and
-// the level rule encode_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
+// host and device sources, obs_upload / obs_from_device, the device ingestion of files and sequence pairs,
+// recompress_alphabet; the training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's and the parse
+// ingest_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
 // and its builder, one enqueue function per kernel family, the model layer, the C ABI.
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,7 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "../../include/imcoal_fwd.h"
@@ -55,6 +57,7 @@
 #include "kernels_zip4.hpp"
 #include "pair_dict.hpp"
 #include "kernels_encode.hpp"
+#include "kernels_ingest.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
 #include "model_host.hpp"
@@ -157,6 +160,10 @@ struct Ctx {
     std::vector<Ev3> events;
     std::map<int, std::shared_ptr<DictDev>> dicts;   // by raw alphabet size
     uint64_t last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t last_ingest[4] = {0, 0, 0, 0};      // imc_last_ingest: path, bytes sent to the device, slabs, columns
+    int device_ingest = -1;   // imc_obs_create_from_text: 0 = the host parser (obs_io.hpp), 1 = the file's bytes go to the device
+                              // in slabs and are parsed / unpacked there (kernels_ingest.hpp).  -1: not set yet - IMC_DEVICE_INGEST
+                              // at start-up, else 0 (imc_set_device_ingest)
     uint64_t r1_checked = 0, r1_collapsed = 0;   // last call: operator segments tested / certified rank one
     std::string last_kernels;   // propagate kernels of the last enqueue, e.g. "k_zpropagate2<5>[tokens]"
     std::vector<const void *> lds_opted;   // kernels of this device that may use LDS_BUDGET bytes of dynamic LDS (allow_lds_budget)
@@ -712,6 +719,8 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
     if (PhaseTimer::enabled())   // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
         std::fprintf(stderr, "[imc host] create %zu columns: train %.1f ms, encode %.1f ms, upload %.1f ms, install %.1f ms (%s encoder)\n", L,
                      tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
+    g.last_ingest[0] = g.last_ingest[1] = g.last_ingest[2] = 0;   // (imc_last_ingest: parsed and validated on the host)
+    g.last_ingest[3] = L;
     *out = o;
     return IMC_OK;
 }
@@ -735,9 +744,92 @@ int check_device_range(const void *p, size_t bytes)
     return IMC_OK;
 }
 
+// ---- chunks from symbols in device memory -------------------------------------------------------------------
+// The pieces every creation that has its symbols on the device is made of (imc_obs_create_device and the device
+// ingestion below); g_mu held, context ready, everything on g.stream.
+
+// First column of d[0..L) (sym_bytes per symbol) that is not below nsym: IMC_ERR_SYMBOL "symbol V at column T <tail>".
+int validate_device_symbols(const void *d, int sym_bytes, size_t L, int nsym, const char *tail)
+{
+    if (!L) return IMC_OK;
+    DevBuf<uint32_t> first_bad;
+    HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
+    const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
+    hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    if (bad == 0xffffffffu) return IMC_OK;
+    int32_t v = 0;
+    uint8_t raw[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(raw, (const char *)d + (size_t)bad * sym_bytes, sym_bytes, hipMemcpyDeviceToHost));
+    if (sym_bytes == 1) v = raw[0];
+    else if (sym_bytes == 2) { uint16_t u; std::memcpy(&u, raw, 2); v = u; }
+    else std::memcpy(&v, raw, 4);
+    return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(v) + " at column " + std::to_string(bad) + " " + tail);
+}
+
+// The chunk's own padded symbol buffer (all zeros; nothing has waited for the memset yet).
+int alloc_symbols(imc_obs *o)
+{
+    HIP_TRY(alloc_padded(o->L * (o->wide_raw ? sizeof(imc::tok_t) : 1), &o->d_sym));
+    return IMC_OK;
+}
+
+// d_src[0..o->L) validated against nsym and copied into the chunk's own buffer (narrowed to bytes, or to 16 bits).
+int adopt_device_symbols(imc_obs *o, const void *d_src, int sym_bytes, const char *tail)
+{
+    if (int rc = alloc_symbols(o)) return rc;
+    if (!o->L) return IMC_OK;
+    if (int rc = validate_device_symbols(d_src, sym_bytes, o->L, o->nsym, tail)) return rc;
+    const dim3 grid((uint32_t)((o->L + ENC_THREADS - 1) / ENC_THREADS));
+    hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)o->L, o->d_sym, o->wide_raw ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return IMC_OK;
+}
+
+// The chunk's symbols are in its buffer: its dictionary (only the head that training looks at comes back to the host,
+// and only when the alphabet has no dictionary yet) and its token streams, encoded on the device.
+int finish_device_chunk(std::unique_lock<std::mutex> &lk, imc_obs *o)
+{
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    if (!o->L) return IMC_OK;
+    const bool wide_raw = o->wide_raw;
+    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
+    std::shared_ptr<DictDev> dd;
+    std::vector<uint8_t> head;
+    auto copy_head = [&](HostSymbols *s) -> int {
+        head.resize(imc::training_head(o->L, wide_raw) * unit);
+        HIP_TRY(hipMemcpy(head.data(), o->d_sym, head.size(), hipMemcpyDeviceToHost));
+        *s = symbols_in(head, wide_raw);
+        return IMC_OK;
+    };
+    if (int rc = dictionary_for(lk, o->L, o->nsym, copy_head, &dd)) return rc;
+    std::vector<uint8_t>().swap(head);
+    HIP_TRY(hipSetDevice(g.device));
+    return dd && dd->dict.alphabet > o->nsym ? device_encode(dd, &o, 1) : IMC_OK;
+}
+
+// The switch of imc_set_device_ingest (g_mu held; no device needed): IMC_DEVICE_INGEST decides until it is set.
+int device_ingest_mode()
+{
+    if (g.device_ingest < 0) {
+        const char *di = std::getenv("IMC_DEVICE_INGEST");
+        g.device_ingest = di && std::atoi(di) == 1 ? 1 : 0;
+    }
+    return g.device_ingest;
+}
+
+void note_ingest(uint64_t path, uint64_t bytes, uint64_t slabs, uint64_t columns)
+{
+    g.last_ingest[0] = path; g.last_ingest[1] = bytes; g.last_ingest[2] = slabs; g.last_ingest[3] = columns;
+}
+
 // Build a chunk from symbols in device memory (imc_obs_create_device; arguments already checked).  The device work is on
-// the library's stream under g_mu; only the head that training looks at comes back to the host, and only when the
-// alphabet has no dictionary yet.
+// the library's stream under g_mu.
 int obs_from_device(const void *d_src, size_t L, int nsym, int sym_bytes, hipStream_t user_stream, imc_obs **out)
 {
     std::unique_lock<std::mutex> lk(g_mu);
@@ -748,50 +840,294 @@ int obs_from_device(const void *d_src, size_t L, int nsym, int sym_bytes, hipStr
     HIP_TRY(hipStreamSynchronize(user_stream));   // what the caller queued on its stream has produced the symbols
     imc_obs *o = obs_new(L, nsym);
     if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    const bool wide_raw = o->wide_raw;
-    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
-    auto work = [&]() -> int {
-        HIP_TRY(alloc_padded(L * unit, &o->d_sym));
-        if (!L) return hipStreamSynchronize(g.stream) == hipSuccess ? IMC_OK : fail(IMC_ERR_HIP, "stream synchronisation failed");
-        DevBuf<uint32_t> first_bad;
-        HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
-        const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
-        hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
-        hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)L, o->d_sym, wide_raw ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        uint32_t bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        if (bad != 0xffffffffu) {
-            int32_t v = 0;
-            uint8_t raw[4] = {0, 0, 0, 0};
-            HIP_TRY(hipMemcpy(raw, (const char *)d_src + (size_t)bad * sym_bytes, sym_bytes, hipMemcpyDeviceToHost));
-            if (sym_bytes == 1) v = raw[0];
-            else if (sym_bytes == 2) { uint16_t u; std::memcpy(&u, raw, 2); v = u; }
-            else std::memcpy(&v, raw, 4);
-            return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(v) + " at column " + std::to_string(bad) + " outside [0,nsym)");
-        }
-        std::shared_ptr<DictDev> dd;
-        std::vector<uint8_t> head;
-        auto copy_head = [&](HostSymbols *s) -> int {
-            head.resize(imc::training_head(L, wide_raw) * unit);
-            HIP_TRY(hipMemcpy(head.data(), o->d_sym, head.size(), hipMemcpyDeviceToHost));
-            *s = symbols_in(head, wide_raw);
-            return IMC_OK;
-        };
-        if (int rc = dictionary_for(lk, L, nsym, copy_head, &dd)) return rc;
-        std::vector<uint8_t>().swap(head);
-        return dd && dd->dict.alphabet > nsym ? device_encode(dd, &o, 1) : IMC_OK;
-    };
-    if (int rc = work()) {
+    int rc = adopt_device_symbols(o, d_src, sym_bytes, "outside [0,nsym)");
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc != IMC_OK) {
         const std::string msg = g_err;
+        obs_release(o);
+        delete o;
+        return fail(rc, msg);
+    }
+    note_ingest(0, 0, 0, L);
+    *out = o;
+    return IMC_OK;
+}
+
+// ---- device ingestion -------------------------------------------------------------------------------------
+// imc_obs_create_from_text with imc_set_device_ingest(1), and imc_obs_create_pairwise: the bytes of the file (of the two
+// sequences) go to the device in slabs of at most IMC_INGEST_SLAB_BYTES through two pinned staging buffers, so host memory
+// is bounded by the slab size, and the symbols are made there (kernels_ingest.hpp; the rules and the slab cut are
+// ingest_tiles.hpp's).  From the symbols on, the chunk is built by the pieces above.  The file is read WITHOUT g_mu, and
+// slab k + 1 is read while slab k is on the device; launches and copies are on g.stream with g_mu held.  Device memory
+// beyond the chunk itself: the two slabs, and for text one symbol buffer of the file's upper bound (max_tokens_in), both
+// released before the token streams are encoded.
+constexpr size_t INGEST_SLAB_DEFAULT = (size_t)4 << 20;    // (profiles/device_ingest_ab.txt: the sweep over 1 .. 256 MiB)
+
+size_t ingest_slab_bytes() { return imc::slab_bytes_setting(std::getenv("IMC_INGEST_SLAB_BYTES"), INGEST_SLAB_DEFAULT); }
+
+struct IngestStage {             // created, used for HIP calls and destroyed with g_mu held
+    size_t slab = 0;
+    uint8_t *host[2] = {nullptr, nullptr};
+    DevBuf<uint8_t> dev[2];
+    hipEvent_t done[2] = {nullptr, nullptr};
+    imc::IngestSummary *verdict = nullptr;     // pinned, one per buffer
+
+    IngestStage() = default;
+    IngestStage(const IngestStage &) = delete;
+    IngestStage &operator=(const IngestStage &) = delete;
+    int alloc(size_t slab_bytes, int buffers)
+    {
+        slab = slab_bytes;
+        HIP_TRY(hipHostMalloc((void **)&verdict, 2 * sizeof(imc::IngestSummary), hipHostMallocDefault));
+        for (int b = 0; b < buffers; ++b) {
+            HIP_TRY(hipHostMalloc((void **)&host[b], slab, hipHostMallocDefault));
+            HIP_TRY(dev[b].alloc(ing_slab_alloc(slab)));
+            HIP_TRY(hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+        }
+        return IMC_OK;
+    }
+    void release()
+    {
+        (void)hipStreamSynchronize(g.stream);
+        for (int b = 0; b < 2; ++b) {
+            if (host[b]) (void)hipHostFree(host[b]);
+            if (done[b]) (void)hipEventDestroy(done[b]);
+            dev[b].reset();
+            host[b] = nullptr;
+            done[b] = nullptr;
+        }
+        if (verdict) (void)hipHostFree(verdict);
+        verdict = nullptr;
+    }
+    ~IngestStage() { release(); }
+};
+
+// `total` units go to the device in pieces of at most `piece` units, alternating between the stage's two buffers:
+// fill(b, off, len) - called WITHOUT g_mu - puts the piece into st.host[b] (IMC_OK, or a fail()), consume(b, off, len)
+// queues its upload and its kernels on g.stream.  Piece k + 1 is filled while piece k is on the device.
+template <class Fill, class Consume>
+int ingest_pump(std::unique_lock<std::mutex> &lk, IngestStage &st, uint64_t total, uint64_t piece, uint64_t *pieces, Fill &&fill, Consume &&consume)
+{
+    bool used[2] = {false, false};
+    int b = 0;
+    for (uint64_t off = 0; off < total; off += piece, b ^= 1) {
+        const uint64_t len = std::min(piece, total - off);
+        lk.unlock();
+        int rc = IMC_OK;
+        if (used[b] && hipEventSynchronize(st.done[b]) != hipSuccess) rc = fail(IMC_ERR_HIP, "ingest: waiting for a staging buffer failed");
+        if (rc == IMC_OK) rc = fill(b, off, len);
+        lk.lock();
+        if (rc != IMC_OK) return rc;
+        HIP_TRY(hipSetDevice(g.device));
+        if (int rc2 = consume(b, off, len)) return rc2;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(st.done[b], g.stream));
+        used[b] = true;
+        ++*pieces;
+    }
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return IMC_OK;
+}
+
+// A new chunk whose creation failed, or the finished one (g_mu held).
+int ingest_result(int rc, imc_obs *o, imc_obs **out)
+{
+    if (rc != IMC_OK) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(g.stream);
         obs_release(o);
         delete o;
         return fail(rc, msg);
     }
     *out = o;
     return IMC_OK;
+}
+
+// Text file of file_bytes bytes, fp at its start.  *declined: the device parser does not take this file (a slab without
+// whitespace, a digit run beyond 16) - nothing was created, the host parser reads it from its start.  Errors are the host
+// parser's, in file order: slab k's verdict is looked at before slab k + 1 is queued.
+int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, const char *path, int nsym, imc_obs **out, bool *declined)
+{
+    const bool wide = nsym > imc::kByteAlphabet;
+    const size_t unit = wide ? sizeof(imc::tok_t) : 1;
+    const uint64_t room = imc::max_tokens_in(file_bytes);
+    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
+    const size_t tiles_max = (slab + ING_TILE - 1) / ING_TILE;
+    IngestStage st;
+    DevBuf<uint8_t> symbols;
+    DevBuf<uint16_t> flags;
+    DevBuf<imc::IngestSummary> sums, total;
+    DevBuf<uint32_t> tile_off;
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1)) return rc;
+    HIP_TRY(symbols.alloc(room * unit));
+    HIP_TRY(flags.alloc(tiles_max * ING_THREADS * sizeof(uint16_t)));
+    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::IngestSummary)));
+    HIP_TRY(total.alloc(sizeof(imc::IngestSummary)));
+    HIP_TRY(tile_off.alloc(tiles_max * sizeof(uint32_t)));
+    uint64_t cols = 0, sent = 0, slabs = 0, consumed = 0;
+    bool eof = false;
+    auto read_into = [&](uint8_t *dst, size_t want) -> size_t {       // WITHOUT g_mu
+        want = (size_t)std::min<uint64_t>(want, file_bytes - consumed);
+        const size_t got = want ? std::fread(dst, 1, want, fp) : 0;
+        consumed += got;
+        if (got < want || consumed == file_bytes) eof = true;
+        return got;
+    };
+    lk.unlock();
+    size_t fill = read_into(st.host[0], slab);
+    lk.lock();
+    for (int cur = 0;; cur ^= 1) {
+        const bool last = eof;
+        const size_t cut = imc::slab_cut(st.host[cur], fill, last);
+        if (cut == 0 && !last) { *declined = true; return IMC_OK; }
+        if (cut == 0) break;
+        HIP_TRY(hipSetDevice(g.device));
+        const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + ING_TILE - 1) / ING_TILE);
+        HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
+        hipLaunchKernelGGL(k_ing_text_summary, dim3(tiles), dim3(ING_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (uint32_t)nsym, flags.get(),
+                           sums.get());
+        hipLaunchKernelGGL(k_ing_scan, dim3(1), dim3(ING_SCAN_THREADS), 0, g.stream, (const imc::IngestSummary *)sums.get(), tiles, tile_off.get(), total.get());
+        hipLaunchKernelGGL(k_ing_text_scatter, dim3(tiles), dim3(ING_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (const uint16_t *)flags.get(),
+                           (const uint32_t *)tile_off.get(), symbols.get() + cols * unit, (uint32_t)std::min<uint64_t>(room - cols, 0xffffffffu), wide ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&st.verdict[cur], total.get(), sizeof(imc::IngestSummary), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipEventRecord(st.done[cur], g.stream));
+        sent += cut;
+        ++slabs;
+        // the next slab: what lies behind the cut, then more of the file - read while this one is on the device
+        const size_t carry = fill - cut;
+        lk.unlock();
+        size_t next_fill = carry;
+        if (carry) std::memcpy(st.host[cur ^ 1], st.host[cur] + cut, carry);
+        if (!last) next_fill += read_into(st.host[cur ^ 1] + carry, slab - carry);
+        const hipError_t waited = hipEventSynchronize(st.done[cur]);
+        lk.lock();
+        if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("ingest: ") + hipGetErrorString(waited));
+        const imc::IngestSummary all = st.verdict[cur];
+        const imc::IngestVerdict v = imc::ingest_verdict(all, n);
+        if (v.kind == imc::kIngestDeclined) { *declined = true; return IMC_OK; }
+        if (v.kind == imc::kIngestBadByte) return fail(IMC_ERR_IO, std::string("unexpected character in ") + path);
+        if (v.kind == imc::kIngestSymbol) return fail(IMC_ERR_SYMBOL, imc::symbol_error_text(v.value, cols + v.column, v.at_end));
+        cols += all.count;
+        if (cols > room) return fail(IMC_ERR_HIP, "ingest: more tokens than the file can hold");
+        fill = next_fill;
+        if (last) break;
+    }
+    if (cols >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    HIP_TRY(hipSetDevice(g.device));
+    imc_obs *o = obs_new((size_t)cols, nsym);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    int rc = adopt_device_symbols(o, symbols.get(), (int)unit, ">= nsym");
+    st.release();
+    symbols.reset();
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) note_ingest(1, sent, slabs, cols);
+    return ingest_result(rc, o, out);
+}
+
+// Cache file, fp behind its header h (checked).  The payload goes up packed: 2-bit files are unpacked by the device into the
+// chunk's buffer, 8- and 16-bit payloads are validated and copied as symbols in device memory are.
+int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHeader &h, const char *path, int nsym, imc_obs **out)
+{
+    const uint64_t L = h.L, payload = h.bits == 2 ? (L + 3) / 4 : L * (h.bits / 8);
+    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes() & ~(size_t)15, std::max<uint64_t>((payload + 15) & ~(uint64_t)15, imc::kMinSlabBytes));
+    IngestStage st;
+    DevBuf<uint8_t> raw;
+    if (int rc = st.alloc(slab, payload > slab ? 2 : 1)) return rc;
+    imc_obs *o = obs_new((size_t)L, nsym);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    const size_t unit = o->wide_raw ? sizeof(imc::tok_t) : 1;
+    uint64_t slabs = 0;
+    auto fill = [&](int b, uint64_t, uint64_t len) -> int {
+        return std::fread(st.host[b], 1, (size_t)len, fp) == (size_t)len ? IMC_OK : fail(IMC_ERR_IO, std::string("truncated cache ") + path);
+    };
+    auto work = [&]() -> int {
+        if (h.bits == 2) {
+            if (int rc = alloc_symbols(o)) return rc;
+            if (int rc = ingest_pump(lk, st, payload, slab, &slabs, fill, [&](int b, uint64_t off, uint64_t len) -> int {
+                    const uint32_t columns = (uint32_t)std::min<uint64_t>(4 * len, L - 4 * off);
+                    HIP_TRY(hipMemcpyAsync(st.dev[b].get(), st.host[b], (size_t)len, hipMemcpyHostToDevice, g.stream));
+                    hipLaunchKernelGGL(k_ing_unpack2, dim3((uint32_t)((len + ING_THREADS - 1) / ING_THREADS)), dim3(ING_THREADS), 0, g.stream,
+                                       (const uint8_t *)st.dev[b].get(), columns, o->d_sym + 4 * off * unit, o->wide_raw ? 1 : 0);
+                    return IMC_OK;
+                }))
+                return rc;
+            st.release();
+            return validate_device_symbols(o->d_sym, (int)unit, (size_t)L, nsym, ">= nsym");
+        }
+        HIP_TRY(raw.alloc((size_t)payload));
+        if (int rc = ingest_pump(lk, st, payload, slab, &slabs, fill, [&](int b, uint64_t off, uint64_t len) -> int {
+                HIP_TRY(hipMemcpyAsync(raw.get() + off, st.host[b], (size_t)len, hipMemcpyHostToDevice, g.stream));
+                return IMC_OK;
+            }))
+            return rc;
+        st.release();
+        const int rc = adopt_device_symbols(o, raw.get(), (int)(h.bits / 8), ">= nsym");
+        raw.reset();
+        return rc;
+    };
+    int rc = work();
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) note_ingest(2, payload, slabs, L);
+    return ingest_result(rc, o, out);
+}
+
+// imc_obs_create_from_text on the device path (arguments checked).  Opening the file, its size, the magic and the cache
+// header are the host's business and need no device.
+int obs_from_file_device(const char *path, int nsym, imc_obs **out, bool *declined)
+{
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+    struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{fp};
+    struct stat sb;
+    if (fstat(fileno(fp), &sb) != 0 || !S_ISREG(sb.st_mode)) { *declined = true; return IMC_OK; }   // (a pipe cannot be read twice)
+    char head[8];
+    const size_t nh = std::fread(head, 1, 8, fp);
+    const bool cache = nh == 8 && std::memcmp(head, imc::kCacheMagic, 8) == 0;
+    imc::CacheHeader h;
+    if (cache) {
+        const imc::IoResult hr = imc::read_cache_header(fp, path, nsym, h);
+        if (hr.code) return fail(hr.code, hr.msg);
+        if (h.bits == 16 && nsym <= imc::kByteAlphabet) { *declined = true; return IMC_OK; }   // (the host reader narrows before it validates)
+        if (h.L >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    } else
+        std::rewind(fp);
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    HIP_TRY(hipSetDevice(g.device));
+    return cache ? ingest_cache(lk, fp, h, path, nsym, out) : ingest_text(lk, fp, (uint64_t)sb.st_size, path, nsym, out, declined);
+}
+
+// imc_obs_create_pairwise (arguments checked): the rule of imc::encode_pairwise on the device, nsym = 3.
+int obs_from_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **out)
+{
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    HIP_TRY(hipSetDevice(g.device));
+    const size_t columns = std::min<size_t>(ingest_slab_bytes() / 2, std::max<size_t>(L, imc::kMinSlabBytes / 2)), half = (columns + 15) & ~(size_t)15;
+    IngestStage st;
+    if (int rc = st.alloc(2 * half, L > half ? 2 : 1)) return rc;
+    imc_obs *o = obs_new(L, 3);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    uint64_t slabs = 0;
+    int rc = alloc_symbols(o);
+    if (rc == IMC_OK)
+        rc = ingest_pump(lk, st, L, half, &slabs,
+                         [&](int b, uint64_t off, uint64_t len) -> int {
+                             std::memcpy(st.host[b], seq1 + off, (size_t)len);
+                             std::memcpy(st.host[b] + half, seq2 + off, (size_t)len);
+                             return IMC_OK;
+                         },
+                         [&](int b, uint64_t off, uint64_t len) -> int {
+                             HIP_TRY(hipMemcpyAsync(st.dev[b].get(), st.host[b], half + (size_t)len, hipMemcpyHostToDevice, g.stream));
+                             hipLaunchKernelGGL(k_ing_pairwise, dim3((uint32_t)((len + 4 * ING_THREADS - 1) / (4 * ING_THREADS))), dim3(ING_THREADS), 0, g.stream,
+                                                (const uint8_t *)st.dev[b].get(), (const uint8_t *)st.dev[b].get() + half, (uint32_t)len, o->d_sym + off);
+                             return IMC_OK;
+                         });
+    st.release();
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) note_ingest(3, 2 * (uint64_t)L, slabs, L);
+    return ingest_result(rc, o, out);
 }
 
 // The deepest level within alphabet_limit at which the chunk holds a token stream; -1: none, its raw symbols
@@ -2630,6 +2966,16 @@ int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out)
 {
     if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
     if (nsym < 1 || nsym > imc::kMaxRawAlphabet) return fail(IMC_ERR_ARG, "nsym must be in [1," + std::to_string(imc::kMaxRawAlphabet) + "]");
+    bool on_device;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        on_device = device_ingest_mode() == 1;
+    }
+    if (on_device) {                                    // parsed / unpacked on the device, unless the device parser declines the file
+        bool declined = false;
+        const int rc = obs_from_file_device(path, nsym, out, &declined);
+        if (!declined) return rc;
+    }
     if (nsym > imc::kByteAlphabet) {
         std::vector<imc::tok_t> wide;
         const imc::IoResult rw = imc::read_observation_file(path, nsym, wide);
@@ -2642,6 +2988,31 @@ int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out)
     if (r.code) return fail(r.code, r.msg);
     if (sym.size() >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
     return obs_upload(sym.data(), nullptr, sym.size(), nsym, out);
+}
+
+int imc_obs_create_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **out)
+{
+    // every argument check before any HIP call
+    if (!out) return fail(IMC_ERR_ARG, "out is null");
+    if (L && (!seq1 || !seq2)) return fail(IMC_ERR_ARG, "null sequence");
+    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    return obs_from_pairwise(seq1, seq2, L, out);
+}
+
+int imc_set_device_ingest(int mode)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device ingest mode must be 0 (host parser) or 1 (device parser)");
+    g.device_ingest = mode;
+    return IMC_OK;
+}
+
+int imc_last_ingest(uint64_t *out4)
+{
+    if (!out4) return fail(IMC_ERR_ARG, "out4 is null");
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (int i = 0; i < 4; ++i) out4[i] = g.last_ingest[i];
+    return IMC_OK;
 }
 
 int imc_read_observations(const char *path, int nsym, uint8_t *sym_out, size_t capacity, size_t *length)

@@ -8,6 +8,8 @@
 //  * encode_pairwise: the pairwise symbol rule of scripts/prepare-alignments.py:99-105
 //    (2 = either base not in ACGT, 0 = equal, 1 = different; case-insensitive);
 //  * write_cache.
+// The cache header (read_cache_header) and the text loop (TextParser) are pieces of their own: the device ingestion of
+// imcoal_fwd.hip checks headers with the first, and tests/ingest_tiles_check.cpp holds csrc/ingest_tiles.hpp to the second.
 #pragma once
 
 #include <cerrno>
@@ -34,6 +36,61 @@ inline IoResult io_fail(int code, const std::string &m)
     return r;
 }
 
+// What follows the magic of a cache file: alphabet size, bits per column (2, 8 or 16), columns; the payload comes next.
+struct CacheHeader {
+    uint32_t fs = 0, bits = 0;
+    uint64_t L = 0;
+};
+
+// fp stands behind the magic; the checks a cache header must pass, in the order their errors are reported.
+inline IoResult read_cache_header(FILE *fp, const char *path, int nsym, CacheHeader &h)
+{
+    if (std::fread(&h.fs, 4, 1, fp) != 1 || std::fread(&h.bits, 4, 1, fp) != 1 || std::fread(&h.L, 8, 1, fp) != 1)
+        return io_fail(-5, std::string("truncated cache header in ") + path);
+    if ((h.bits != 2 && h.bits != 8 && h.bits != 16) || h.fs < 1 || h.fs > 65536 || (h.bits == 2 && h.fs > 4) || (h.bits == 8 && h.fs > 256))
+        return io_fail(-5, std::string("bad cache header in ") + path);
+    if ((int)h.fs > nsym) return io_fail(-2, "cache holds an alphabet of " + std::to_string(h.fs) + " symbols, more than nsym");
+    return IoResult();
+}
+
+// The text loop of read_observation_file, fed buffer by buffer: a token is accumulated across feeds (values beyond
+// 1000000 read as 1000000), checked against nsym and appended at the whitespace that ends it - or by finish() at the end
+// of the file; any byte that is neither digit nor whitespace is an error where it stands.
+template <typename T>
+struct TextParser {
+    long cur = -1;   // token being accumulated, -1 = none
+
+    IoResult feed(const char *buf, size_t n, int nsym, const char *path, std::vector<T> &sym)
+    {
+        for (size_t i = 0; i < n; ++i) {
+            const unsigned char ch = (unsigned char)buf[i];
+            if (ch >= '0' && ch <= '9') {
+                cur = (cur < 0 ? 0 : cur) * 10 + (ch - '0');
+                if (cur > 1000000) cur = 1000000;
+            } else if (ch == ' ' || ch == '\n' || ch == '\t' || ch == '\r' || ch == '\f' || ch == '\v') {
+                if (cur >= 0) {
+                    if (cur >= nsym) return io_fail(-2, "symbol " + std::to_string(cur) + " at column " + std::to_string(sym.size()) + " >= nsym");
+                    sym.push_back((T)cur);
+                    cur = -1;
+                }
+            } else {
+                return io_fail(-5, std::string("unexpected character in ") + path);   // int() would raise ValueError (hmm.py:14)
+            }
+        }
+        return IoResult();
+    }
+
+    IoResult finish(int nsym, std::vector<T> &sym)
+    {
+        if (cur >= 0) {
+            if (cur >= nsym) return io_fail(-2, "symbol " + std::to_string(cur) + " >= nsym");
+            sym.push_back((T)cur);
+            cur = -1;
+        }
+        return IoResult();
+    }
+};
+
 template <typename T>
 inline IoResult read_observation_file(const char *path, int nsym, std::vector<T> &sym)
 {
@@ -45,20 +102,14 @@ inline IoResult read_observation_file(const char *path, int nsym, std::vector<T>
     const size_t nh = std::fread(head, 1, 8, fp);
     if (nh == 8 && std::memcmp(head, kCacheMagic, 8) == 0) {
         // ---- packed cache ----
-        uint32_t fs = 0, bits = 0;
-        uint64_t L = 0;
-        if (std::fread(&fs, 4, 1, fp) != 1 || std::fread(&bits, 4, 1, fp) != 1 || std::fread(&L, 8, 1, fp) != 1) {
+        CacheHeader h;
+        const IoResult hr = read_cache_header(fp, path, nsym, h);
+        if (hr.code) {
             std::fclose(fp);
-            return io_fail(-5, std::string("truncated cache header in ") + path);
+            return hr;
         }
-        if ((bits != 2 && bits != 8 && bits != 16) || fs < 1 || fs > 65536 || (bits == 2 && fs > 4) || (bits == 8 && fs > 256)) {
-            std::fclose(fp);
-            return io_fail(-5, std::string("bad cache header in ") + path);
-        }
-        if ((int)fs > nsym) {
-            std::fclose(fp);
-            return io_fail(-2, "cache holds an alphabet of " + std::to_string(fs) + " symbols, more than nsym");
-        }
+        const uint32_t bits = h.bits;
+        const uint64_t L = h.L;
         sym.resize(L);
         if (bits == 8 || bits == 16) {
             const size_t w = bits / 8;
@@ -77,38 +128,19 @@ inline IoResult read_observation_file(const char *path, int nsym, std::vector<T>
     }
     // ---- text ----
     std::vector<char> buf(1 << 22);
-    long cur = -1;   // token being accumulated, -1 = none
+    TextParser<T> text;
     size_t n = nh;
     std::memcpy(buf.data(), head, nh);
-    IoResult rc;
     while (n > 0) {
-        for (size_t i = 0; i < n; ++i) {
-            const unsigned char ch = (unsigned char)buf[i];
-            if (ch >= '0' && ch <= '9') {
-                cur = (cur < 0 ? 0 : cur) * 10 + (ch - '0');
-                if (cur > 1000000) cur = 1000000;
-            } else if (ch == ' ' || ch == '\n' || ch == '\t' || ch == '\r' || ch == '\f' || ch == '\v') {
-                if (cur >= 0) {
-                    if (cur >= nsym) {
-                        std::fclose(fp);
-                        return io_fail(-2, "symbol " + std::to_string(cur) + " at column " + std::to_string(sym.size()) + " >= nsym");
-                    }
-                    sym.push_back((T)cur);
-                    cur = -1;
-                }
-            } else {
-                std::fclose(fp);
-                return io_fail(-5, std::string("unexpected character in ") + path);   // int() would raise ValueError (hmm.py:14)
-            }
+        const IoResult rc = text.feed(buf.data(), n, nsym, path, sym);
+        if (rc.code) {
+            std::fclose(fp);
+            return rc;
         }
         n = std::fread(buf.data(), 1, buf.size(), fp);
     }
     std::fclose(fp);
-    if (cur >= 0) {
-        if (cur >= nsym) return io_fail(-2, "symbol " + std::to_string(cur) + " >= nsym");
-        sym.push_back((T)cur);
-    }
-    return IoResult();
+    return text.finish(nsym, sym);
 }
 
 template <typename T>

@@ -103,6 +103,13 @@ def set_device_encoding(mode):
     _capi.check(_capi.lib().imc_set_device_encoding(int(mode)))
 
 
+def set_device_ingest(mode):
+    """Where ``Forwarder(path, NSYM)`` turns the file into symbols (``imc_set_device_ingest``): 0 = the host parser
+    (default), 1 = on the device - the file's bytes go up in slabs and are parsed (text) or unpacked (cache) there; the
+    same symbols, streams, results and errors."""
+    _capi.check(_capi.lib().imc_set_device_ingest(int(mode)))
+
+
 _DEVICE_SYMBOL_BYTES = {"|u1": 1, "<i2": 2, "<u2": 2, "<i4": 4}
 
 
@@ -147,7 +154,8 @@ class Forwarder(object):
     """``Forwarder(input_filename, NSYM)`` - same surface as the reference class (hmm.py:10-21).
 
     ``input_filename`` is a text file of whitespace-separated symbols as written by
-    scripts/prepare-alignments.py.  Extra, additive constructors: ``Forwarder.from_array``, ``Forwarder.from_device``.
+    scripts/prepare-alignments.py.  Extra, additive constructors: ``Forwarder.from_array``, ``Forwarder.from_device``,
+    ``Forwarder.from_sequences``.
     """
 
     def __init__(self, input_filename, NSYM):
@@ -203,6 +211,24 @@ class Forwarder(object):
         self._h = None
         h = ctypes.c_void_p()
         _capi.check(_capi.lib().imc_obs_create_device(ptr, int(shape[0]), self.NSYM, size, stream or None, ctypes.byref(h)))
+        self._h = h.value
+        self._pid = os.getpid()
+        return self
+
+    @classmethod
+    def from_sequences(cls, seq1, seq2):
+        """Build from two aligned sequences (``str`` or ``bytes``) with the pairwise rule of
+        scripts/prepare-alignments.py:99-105 applied on the device (``imc_obs_create_pairwise``, NSYM = 3): the chunk
+        ``from_array(prepare.encode_pairwise(seq1, seq2), 3)`` builds, without the symbols existing on the host."""
+        a = seq1.encode("latin-1") if isinstance(seq1, str) else bytes(seq1)
+        b = seq2.encode("latin-1") if isinstance(seq2, str) else bytes(seq2)
+        if len(a) != len(b):
+            raise ValueError("sequences differ in length: %d vs %d" % (len(a), len(b)))
+        self = cls.__new__(cls)
+        self.NSYM = 3
+        self._h = None
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib().imc_obs_create_pairwise(a, b, len(a), ctypes.byref(h)))
         self._h = h.value
         self._pid = os.getpid()
         return self

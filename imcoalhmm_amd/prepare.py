@@ -67,6 +67,26 @@ def encode_pairwise(seq1, seq2):
     return out
 
 
+def pairwise_forwarders(path, pairs=None, in_format="fasta"):
+    """{(a, b): Forwarder} for the given pairs of sequence names of an alignment file - or for all pairs, in file order -
+    with the pairwise rule applied on the device (``Forwarder.from_sequences``): no intermediate observation file is
+    written and no symbol array is built on the host."""
+    from .hmm import Forwarder
+    if in_format not in ("fasta", "phylip"):
+        raise ValueError("in_format must be 'fasta' or 'phylip', got %r" % (in_format,))
+    seqs = read_fasta(path) if in_format == "fasta" else read_phylip(path)
+    names = list(seqs.keys())
+    if pairs is None:
+        pairs = [(a, b) for i, a in enumerate(names) for b in names[i + 1:]]
+    out = {}
+    for a, b in pairs:
+        for name in (a, b):
+            if name not in seqs:
+                raise KeyError("no sequence named %r in %s" % (name, path))
+        out[(a, b)] = Forwarder.from_sequences(seqs[a], seqs[b])
+    return out
+
+
 def write_text(path, obs):
     """The reference's own file format: one decimal token per column, each followed by a space."""
     obs = np.ascontiguousarray(obs, dtype=np.uint8)

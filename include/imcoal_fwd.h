@@ -31,7 +31,8 @@
  * (two synchronous calls on the SAME chunk list share a plan's result slots and run one after the other; a chunk is not
  * freed, and no plan released, while somebody waits on it).  The O(L) host work of imc_obs_create* (validation,
  * dictionary training, encoding) runs outside the mutex; the device encoder (imc_set_device_encoding(1),
- * imc_obs_create_device) runs on the library's stream with the mutex held.
+ * imc_obs_create_device) runs on the library's stream with the mutex held.  Device ingestion (imc_set_device_ingest(1),
+ * imc_obs_create_pairwise) reads its file outside the mutex and holds it for its launches.
  *
  * Environment (diagnostics only, read when a plan is built / the context is created):
  *   IMC_DEBUG=1        print the planner's cost estimates to stderr
@@ -97,6 +98,33 @@ int imc_obs_create_i32(const int32_t *sym, size_t L, int nsym, imc_obs **out);  
 /* File of whitespace-separated decimal tokens, the format written by
  * scripts/prepare-alignments.py:92-105 and read at hmm.py:13-14. */
 int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out);   /* also accepts imc_write_cache files */
+/* Where imc_obs_create_from_text turns the file into symbols.  0 (default): on the host, one thread, byte by byte
+ * (csrc/obs_io.hpp), then the symbols are uploaded.  1: on the device (csrc/kernels_ingest.hpp).  The file's bytes go up
+ * in slabs of at most IMC_INGEST_SLAB_BYTES (read at every call; default 4 MiB, at least 4096) through two pinned
+ * staging buffers - host memory is bounded by the slab size, the file is read without the library's mutex, and slab k + 1
+ * is read while slab k is on the device.  A text slab is cut after its last whitespace byte and parsed by three launches
+ * (token starts and error candidates per 4096-byte tile, one scan, a scatter that writes every token's value); a cache
+ * file's header is checked on the host as ever and its payload goes up packed - 2-bit payloads are unpacked by a kernel,
+ * 8- and 16-bit ones are taken as they are.  The symbols are validated against nsym on the device and the chunk is built
+ * from there as imc_obs_create_device builds one, so these chunks are always encoded on the device, whatever
+ * imc_set_device_encoding says; dictionary training stays on the host.  Symbols, dictionaries, token streams and results
+ * are those of mode 0, and so are the return code and the message of every error, in file order (an error in one slab is
+ * reported before the next slab is looked at).  The device parser DECLINES a file that has a slab without any whitespace
+ * or a digit run longer than 16: the host parser then reads it from its start (also what happens to anything that is
+ * not a regular file).  Device memory beyond the chunk: the two slabs and, for text, one symbol buffer of the file's
+ * upper bound, (bytes + 1) / 2 symbols; both are released before the token streams are encoded.
+ * IMC_DEVICE_INGEST=0|1 in the environment sets the mode at start-up; any other mode is IMC_ERR_ARG. */
+int imc_set_device_ingest(int mode);
+/* A chunk from two aligned sequences in host memory: the pairwise rule of imc_encode_pairwise (nsym = 3) is applied on
+ * the device to the bytes of the sequences, which go up through the same slabs; the chunk is the one imc_obs_create
+ * builds from imc_encode_pairwise's output, and no intermediate symbols exist on the host.  IMC_ERR_ARG - before any HIP
+ * call - for null pointers and L >= 2^31. */
+int imc_obs_create_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **out);
+/* The last chunk creation of this process: out4 = {path, bytes sent to the device as file or sequence bytes, slabs,
+ * columns}; path 0 = symbols made on the host (the host parser - also for a file the device parser declined - and the
+ * imc_obs_create* calls that take symbols), 1 = text parsed on the device, 2 = cache unpacked on the device,
+ * 3 = pairwise rule on the device.  For inspection and tests. */
+int imc_last_ingest(uint64_t *out4);
 /* A chunk from symbols that are already in device memory (a simulated replicate, the output of another stage): d_sym
  * points to L symbols of sym_bytes = 1 (uint8), 2 (16-bit) or 4 (int32) bytes each on the library's device.  The call
  * synchronises hip_stream (a hipStream_t; NULL is the default stream), copies the symbols into a buffer of its own on
