@@ -73,6 +73,8 @@ SIGNATURES = [
     ("imc_set_device_ingest", ctypes.c_int, [ctypes.c_int]),
     ("imc_obs_create_pairwise", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _vpp]),
     ("imc_last_ingest", ctypes.c_int, [_u64p]),
+    ("imc_set_device_training", ctypes.c_int, [ctypes.c_int]),
+    ("imc_last_training", ctypes.c_int, [_u64p]),
     ("imc_profile_enable", ctypes.c_int, [ctypes.c_int]),
     ("imc_profile_read", ctypes.c_int, [_dp, _dp, _u64p, _u64p]),
     ("imc_last_rank1", ctypes.c_int, [_u64p, _u64p]),
@@ -196,6 +198,15 @@ def last_ingest():
     check(lib().imc_last_ingest(arr))
     return {"path": ("host", "text", "cache", "pairwise")[int(arr[0])], "bytes": int(arr[1]), "slabs": int(arr[2]),
             "columns": int(arr[3])}
+
+
+def last_training():
+    """Dict view of imc_last_training(): the last dictionary training of this process.  ``path`` is 0 (host) or 1
+    (device), ``symbols`` the part of the sample training could look at, ``attempts`` the runs of the byte phase (0 for
+    raw alphabets beyond 256 symbols), ``rounds`` the 16-bit rounds."""
+    arr = (ctypes.c_uint64 * 4)()
+    check(lib().imc_last_training(arr))
+    return dict(zip(("path", "symbols", "attempts", "rounds"), [int(x) for x in arr]))
 
 
 def last_plan():

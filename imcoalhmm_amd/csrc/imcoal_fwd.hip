@@ -57,6 +57,7 @@
 #include "kernels_zip4.hpp"
 #include "pair_dict.hpp"
 #include "kernels_encode.hpp"
+#include "kernels_train.hpp"
 #include "kernels_ingest.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
@@ -164,6 +165,10 @@ struct Ctx {
     int device_ingest = -1;   // imc_obs_create_from_text: 0 = the host parser (obs_io.hpp), 1 = the file's bytes go to the device
                               // in slabs and are parsed / unpacked there (kernels_ingest.hpp).  -1: not set yet - IMC_DEVICE_INGEST
                               // at start-up, else 0 (imc_set_device_ingest)
+    int device_train = -1;    // dictionary training: 0 = imc::train_dictionary on the host, 1 = on the device wherever the sample is
+                              // there (kernels_train.hpp; the same dictionary).  -1: not set yet - IMC_DEVICE_TRAIN at start-up,
+                              // else 0 (imc_set_device_training)
+    uint64_t last_training[4] = {0, 0, 0, 0};    // imc_last_training: path, symbols in the sample, byte-phase attempts, 16-bit rounds
     uint64_t r1_checked = 0, r1_collapsed = 0;   // last call: operator segments tested / certified rank one
     std::string last_kernels;   // propagate kernels of the last enqueue, e.g. "k_zpropagate2<5>[tokens]"
     std::vector<const void *> lds_opted;   // kernels of this device that may use LDS_BUDGET bytes of dynamic LDS (allow_lds_budget)
@@ -432,13 +437,50 @@ void obs_release(imc_obs *o)
 
 // Train a pair dictionary on host symbols; host work only, called without g_mu.  The two experiment variables are read at
 // every training (imcoal_fwd.h).
-std::shared_ptr<DictDev> make_dictionary(const HostSymbols &sym, int nsym, uint64_t trained_on)
+struct TrainKnobs {
+    size_t forced_min_count;
+    int max_depth;
+};
+
+TrainKnobs train_knobs()
 {
     const char *min_count = std::getenv("IMC_DICT_MIN_COUNT"), *max_depth = std::getenv("IMC_DICT_MAX_DEPTH");
-    return std::make_shared<DictDev>(imc::train_dictionary(sym.bytes, sym.wide, sym.n, nsym, min_count ? (size_t)std::max(1, std::atoi(min_count)) : 0,
-                                                           max_depth ? std::atoi(max_depth) : imc::TrainLimits().max_depth),
+    return {min_count ? (size_t)std::max(1, std::atoi(min_count)) : 0, max_depth ? std::atoi(max_depth) : imc::TrainLimits().max_depth};
+}
+
+std::shared_ptr<DictDev> make_dictionary(const HostSymbols &sym, int nsym, uint64_t trained_on, imc::TrainStats *stats)
+{
+    const TrainKnobs kn = train_knobs();
+    return std::make_shared<DictDev>(imc::train_dictionary(sym.bytes, sym.wide, sym.n, nsym, kn.forced_min_count, kn.max_depth, imc::TrainLimits(), stats),
                                      trained_on);
 }
+
+// imc_last_training (g_mu held)
+void note_training(uint64_t path, const imc::TrainStats &st)
+{
+    g.last_training[0] = path; g.last_training[1] = st.sample; g.last_training[2] = st.attempts; g.last_training[3] = st.rounds;
+}
+
+// The switch of imc_set_device_training (g_mu held; no device needed): IMC_DEVICE_TRAIN decides until it is set.
+int device_train_mode()
+{
+    if (g.device_train < 0) {
+        const char *dt = std::getenv("IMC_DEVICE_TRAIN");
+        g.device_train = dt && std::atoi(dt) == 1 ? 1 : 0;
+    }
+    return g.device_train;
+}
+
+// n symbols (`unit` bytes each: 1, or 2 beyond 256 symbols) in device memory: a chunk's d_sym or its head.  A training
+// sample on the device is the concatenation of such pieces.
+struct TrainPiece {
+    const void *d;
+    int unit;
+    size_t n;
+};
+
+// The dictionary imc::train_dictionary gives for the concatenated pieces (L symbols), trained on the device (below).
+int device_train(const TrainPiece *pieces, size_t n_pieces, int nsym, size_t L, uint64_t trained_on, std::shared_ptr<DictDev> *out);
 
 // Device copy of a freshly trained dictionary (g_mu held, context ready).
 int upload_dictionary(const std::shared_ptr<DictDev> &nd)
@@ -470,19 +512,33 @@ int publish_dictionary(int nsym, const std::shared_ptr<DictDev> &nd)
 // one published for its alphabet; else, for the first chunk long enough, one trained now; else none (*dd stays null).
 // Called and left with lk (g_mu) held and the context ready; the lock is released while training runs.  head(&symbols)
 // supplies the training symbols - at least imc::training_head() of the chunk - and is called, under the lock, only when
-// a dictionary has to be trained.
+// a dictionary has to be trained.  With imc_set_device_training(1) and the chunk's symbols on the device (`dev`, all L
+// of them; else null) the dictionary is trained there instead, with the lock held, and nothing comes back to the host.
+// must_train(): whether a call now would train one.
+bool must_train(size_t L, int nsym)
+{
+    return g.compression && imc::compressible(L, nsym) && g.dicts.find(nsym) == g.dicts.end() && L >= imc::TrainLimits().train_min;
+}
+
 template <class Head>
-int dictionary_for(std::unique_lock<std::mutex> &lk, size_t L, int nsym, Head &&head, std::shared_ptr<DictDev> *dd)
+int dictionary_for(std::unique_lock<std::mutex> &lk, size_t L, int nsym, Head &&head, const TrainPiece *dev, std::shared_ptr<DictDev> *dd)
 {
     if (!g.compression || !imc::compressible(L, nsym)) return IMC_OK;
     auto it = g.dicts.find(nsym);
     if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }
     if (L < imc::TrainLimits().train_min) return IMC_OK;
-    HostSymbols sym{};
-    if (int rc = head(&sym)) return rc;
-    lk.unlock();
-    const std::shared_ptr<DictDev> nd = make_dictionary(sym, nsym, L);   // host only, unlocked
-    lk.lock();
+    std::shared_ptr<DictDev> nd;
+    if (dev && device_train_mode() == 1) {
+        if (int rc = device_train(dev, 1, nsym, L, L, &nd)) return rc;
+    } else {
+        HostSymbols sym{};
+        if (int rc = head(&sym)) return rc;
+        imc::TrainStats st;
+        lk.unlock();
+        nd = make_dictionary(sym, nsym, L, &st);                         // host only, unlocked
+        lk.lock();
+        note_training(0, st);
+    }
     it = g.dicts.find(nsym);
     if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }        // another thread published one meanwhile: use that
     if (int rc = publish_dictionary(nsym, nd)) return rc;
@@ -676,6 +732,215 @@ int device_encode(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_
     return IMC_OK;
 }
 
+// ---- dictionary training on the device ----------------------------------------------------------------------
+// imc::train_with (train_tiles.hpp) decides; this is its backend (kernels_train.hpp).  g_mu held, context ready, every
+// launch and copy on g.stream.  The stream is the encoder's pair of ping-pong scratch streams without chunk marks; the
+// device dictionary (left / right / depth) grows as training goes - k_trn_argmax appends a byte merge, a round's tokens
+// are uploaded - and the encoder's pass kernels read it.  One synchronisation per merge (winner and new length
+// together: the pass runs before the host has seen the winner, and is dropped if the host stops there), two per round
+// (candidates, new length).  Every buffer is released on return.
+struct DeviceTrainer {
+    const TrainPiece *pieces;
+    std::vector<size_t> piece_len;
+    size_t tiles0 = 0;
+    DevBuf<uint16_t> buf[2], flags, left, right, depth;
+    DevBuf<imc::TileSummary> sums;
+    DevBuf<uint2> tile_in, list;
+    DevBuf<uint32_t> scalars, counts, tkeys, tcounts;   // scalars: [0] new length, [1..3] winner {a, b, count}, [4] candidates, [5] table overflow
+    uint32_t table_capacity = 0, list_capacity = 0;
+    uint32_t n = 0, pending_n = 0;
+    int cur = 0;
+
+    int init(const TrainPiece *p, size_t n_pieces, size_t max_stream)
+    {
+        pieces = p;
+        for (size_t k = 0; k < n_pieces; ++k) piece_len.push_back(p[k].n);
+        if (max_stream == 0 || max_stream >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "device training: impossible sample size");
+        tiles0 = (max_stream + ENC_TILE - 1) / ENC_TILE;
+        HIP_TRY(hipSetDevice(g.device));
+        for (int b = 0; b < 2; ++b) HIP_TRY(buf[b].alloc((tiles0 * ENC_TILE + ENC_ITEMS) * sizeof(uint16_t)));
+        HIP_TRY(flags.alloc(tiles0 * ENC_THREADS * sizeof(uint16_t)));
+        HIP_TRY(sums.alloc(tiles0 * sizeof(imc::TileSummary)));
+        HIP_TRY(tile_in.alloc(tiles0 * sizeof(uint2)));
+        HIP_TRY(scalars.alloc(8 * sizeof(uint32_t)));
+        HIP_TRY(counts.alloc((size_t)imc::kByteAlphabet * imc::kByteAlphabet * sizeof(uint32_t)));
+        for (DevBuf<uint16_t> *d : {&left, &right, &depth}) {
+            HIP_TRY(d->alloc((size_t)imc::kMaxAlphabet * sizeof(uint16_t)));
+            HIP_TRY(hipMemsetAsync(d->get(), 0, (size_t)imc::kMaxAlphabet * sizeof(uint16_t), g.stream));
+        }
+        HIP_TRY(hipMemsetAsync(scalars.get(), 0, 8 * sizeof(uint32_t), g.stream));
+        return IMC_OK;
+    }
+    int load(size_t first, size_t count)
+    {
+        if (count > tiles0 * ENC_TILE) return fail(IMC_ERR_HIP, "device training: sample beyond the scratch stream");
+        for (const imc::SampleRange &r : imc::sample_ranges(piece_len, first, count))
+            hipLaunchKernelGGL(k_trn_load, dim3((uint32_t)((r.count + ENC_THREADS - 1) / ENC_THREADS)), dim3(ENC_THREADS), 0, g.stream,
+                               pieces[r.piece].d, pieces[r.piece].unit, (uint32_t)r.src_first, (uint32_t)r.count, buf[0].get() + r.dst_first);
+        HIP_TRY(hipGetLastError());
+        cur = 0;
+        n = (uint32_t)count;
+        return IMC_OK;
+    }
+    void launch_pass(int z0, int nz)                 // buf[cur] -> buf[cur ^ 1], scalars[0] = new length
+    {
+        const EncPass ps{left.get(), right.get(), z0, nz};
+        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
+        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), scalars.get());
+        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
+                           buf[cur ^ 1].get());
+    }
+    int byte_step(int A, int max_depth, imc::ByteStep *s)
+    {
+        if (n < 2 || A >= imc::kByteAlphabet) return fail(IMC_ERR_HIP, "device training: impossible byte step");
+        HIP_TRY(hipMemsetAsync(counts.get(), 0, (size_t)A * A * sizeof(uint32_t), g.stream));
+        const dim3 grid((n + TRN_HIST_TILE - 1) / TRN_HIST_TILE);
+        if (imc::pair_bins_in_lds((uint32_t)A))
+            hipLaunchKernelGGL(k_trn_pair_hist<true>, grid, dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, (uint32_t)A, counts.get());
+        else
+            hipLaunchKernelGGL(k_trn_pair_hist<false>, grid, dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, (uint32_t)A, counts.get());
+        hipLaunchKernelGGL(k_trn_argmax, dim3(1), dim3(TRN_ARGMAX_THREADS), 0, g.stream, counts.get(), (uint32_t)A, max_depth, left.get(), right.get(),
+                           depth.get(), scalars.get() + 1);
+        launch_pass(A, 1);                           // (with no winner token A is a stale pair: the output is dropped)
+        HIP_TRY(hipGetLastError());
+        uint32_t h[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(h, scalars.get(), sizeof h, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        *s = imc::ByteStep{h[1], h[2], h[3], h[0]};
+        if (s->count && (s->a >= (uint32_t)A || s->b >= (uint32_t)A || s->count >= n || s->new_n == 0 || s->new_n > n))
+            return fail(IMC_ERR_HIP, "device training: a merge returned an impossible winner or length");
+        pending_n = s->new_n;
+        return IMC_OK;
+    }
+    void accept()
+    {
+        cur ^= 1;
+        n = pending_n;
+    }
+    void truncate(size_t keep) { n = (uint32_t)std::min<size_t>(n, keep); }
+    int count_round(size_t threshold, std::vector<imc::RoundCandidate> &found)
+    {
+        if (n < 2) return fail(IMC_ERR_HIP, "device training: impossible round");
+        const uint32_t cap = imc::count_table_capacity(n);
+        if (!tkeys) {                                // the first round is the longest stream the rounds see
+            table_capacity = cap;
+            list_capacity = n;
+            HIP_TRY(tkeys.alloc((size_t)cap * sizeof(uint32_t)));
+            HIP_TRY(tcounts.alloc((size_t)cap * sizeof(uint32_t)));
+            HIP_TRY(list.alloc((size_t)list_capacity * sizeof(uint2)));
+        }
+        if (cap > table_capacity) return fail(IMC_ERR_HIP, "device training: the stream grew");
+        HIP_TRY(hipMemsetAsync(tkeys.get(), 0xff, (size_t)cap * sizeof(uint32_t), g.stream));
+        HIP_TRY(hipMemsetAsync(tcounts.get(), 0, (size_t)cap * sizeof(uint32_t), g.stream));
+        HIP_TRY(hipMemsetAsync(scalars.get() + 4, 0, 2 * sizeof(uint32_t), g.stream));
+        hipLaunchKernelGGL(k_trn_pair_count, dim3((n + ENC_TILE - 1) / ENC_TILE), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, cap, tkeys.get(),
+                           tcounts.get(), scalars.get() + 5);
+        hipLaunchKernelGGL(k_trn_candidates, dim3((cap + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, tkeys.get(), tcounts.get(), cap,
+                           (uint32_t)std::min<size_t>(threshold, 0xffffffffu), list.get(), list_capacity, scalars.get() + 4);
+        HIP_TRY(hipGetLastError());
+        uint32_t h[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h, scalars.get() + 4, sizeof h, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (h[1] || h[0] > list_capacity) return fail(IMC_ERR_HIP, "device training: impossible - the pair table overflowed");
+        std::vector<uint2> got(h[0]);
+        if (h[0]) HIP_TRY(hipMemcpy(got.data(), list.get(), (size_t)h[0] * sizeof(uint2), hipMemcpyDeviceToHost));
+        found.reserve(got.size());
+        for (const uint2 &c : got) found.push_back({(uint64_t)c.x, c.y});
+        return IMC_OK;
+    }
+    int apply(const imc::PairDict &d, int z0, int nz, size_t *new_n)
+    {
+        if (n < 1 || nz < 1 || nz > 256 || z0 + nz > imc::kMaxAlphabet || z0 + nz > d.alphabet) return fail(IMC_ERR_HIP, "device training: impossible pass");
+        HIP_TRY(hipMemcpyAsync(left.get() + z0, d.left.data() + z0, (size_t)nz * sizeof(uint16_t), hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipMemcpyAsync(right.get() + z0, d.right.data() + z0, (size_t)nz * sizeof(uint16_t), hipMemcpyHostToDevice, g.stream));
+        launch_pass(z0, nz);
+        HIP_TRY(hipGetLastError());
+        uint32_t hn = 0;
+        HIP_TRY(hipMemcpyAsync(&hn, scalars.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device training: a pass returned an impossible length");
+        n = hn;
+        cur ^= 1;
+        *new_n = hn;
+        return IMC_OK;
+    }
+};
+
+int device_train(const TrainPiece *pieces, size_t n_pieces, int nsym, size_t L, uint64_t trained_on, std::shared_ptr<DictDev> *out)
+{
+    const imc::TrainLimits lim;
+    const TrainKnobs kn = train_knobs();             // the two experiment variables are read at every training (imcoal_fwd.h)
+    if (L < 2) return fail(IMC_ERR_ARG, "device training: empty sample");
+    const size_t max_stream = nsym > imc::kByteAlphabet ? std::min(L - 1, lim.wide_train_tokens * 8)
+                                                        : std::max(std::min(L - 1, lim.train_max), std::min(L, lim.wide_train_tokens * 96) - 1);
+    imc::TrainedDict t;
+    imc::TrainStats st;
+    int rc;
+    {
+        DeviceTrainer be;
+        rc = be.init(pieces, n_pieces, max_stream);
+        if (rc == IMC_OK) rc = imc::train_with(be, L, nsym, kn.forced_min_count, kn.max_depth, lim, t, st);
+        if (rc != IMC_OK) {
+            const std::string msg = g_err;
+            (void)hipStreamSynchronize(g.stream);    // (the scratch streams are freed on return)
+            return fail(rc, msg);
+        }
+    }
+    note_training(1, st);
+    *out = std::make_shared<DictDev>(std::move(t), trained_on);
+    return IMC_OK;
+}
+
+// obs_upload for the creation that trains its alphabet's dictionary, with imc_set_device_training(1): the symbols go up
+// first and the dictionary is trained from the chunk's own buffer; the encoder is the one imc_set_device_encoding names.
+// lk (g_mu) held, context ready.
+int obs_upload_and_train(std::unique_lock<std::mutex> &lk, const HostSymbols &sym, int nsym, bool on_device, imc_obs **out)
+{
+    PhaseTimer tm;
+    HIP_TRY(hipSetDevice(g.device));
+    imc_obs *o = obs_new(sym.n, nsym);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    auto give_up = [&](int rc) {
+        const std::string msg = g_err;
+        obs_release(o);
+        delete o;
+        return fail(rc, msg);
+    };
+    const hipError_t e = o->wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(sym.wide), sym.n * sizeof(imc::tok_t), &o->d_sym)
+                                     : upload_padded(sym.bytes, sym.n, &o->d_sym);
+    if (e != hipSuccess) {
+        g_err = std::string("observation upload: ") + hipGetErrorString(e);
+        return give_up(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP);
+    }
+    tm.mark();
+    std::shared_ptr<DictDev> dd;
+    const TrainPiece piece{o->d_sym, o->wide_raw ? 2 : 1, sym.n};
+    if (int rc = dictionary_for(lk, sym.n, nsym, [](HostSymbols *) -> int { return IMC_OK; }, &piece, &dd)) return give_up(rc);
+    tm.mark();
+    if (dd && dd->dict.alphabet > nsym) {
+        int rc;
+        if (on_device) rc = device_encode(dd, &o, 1);
+        else {
+            imc::EncodedLevels enc;
+            lk.unlock();                             // host only, unlocked (a published dictionary is immutable; nobody else holds o)
+            imc::encode_levels(dd->dict, sym.bytes, sym.wide, sym.n, enc);
+            lk.lock();
+            (void)hipSetDevice(g.device);
+            rc = install_encoding(o, dd, enc);
+        }
+        if (rc != IMC_OK) return give_up(rc);
+    }
+    tm.mark();
+    if (PhaseTimer::enabled())
+        std::fprintf(stderr, "[imc host] create %zu columns: upload %.1f ms, train %.1f ms, encode + install %.1f ms (%s encoder, device trainer)\n", sym.n,
+                     tm.ms(0), tm.ms(1), tm.ms(2), on_device ? "device" : "host");
+    g.last_ingest[0] = g.last_ingest[1] = g.last_ingest[2] = 0;   // (imc_last_ingest: parsed and validated on the host)
+    g.last_ingest[3] = sym.n;
+    *out = o;
+    return IMC_OK;
+}
+
 // Build a chunk from validated host symbols (exactly one of host / host16 is non-null when L > 0).  Called WITHOUT g_mu.
 int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym, imc_obs **out)
 {
@@ -685,7 +950,8 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
     std::unique_lock<std::mutex> lk(g_mu);
     if (int rc = ensure_ctx()) return rc;
     const bool on_device = g.device_encode == 1;
-    if (int rc = dictionary_for(lk, L, nsym, [&](HostSymbols *s) -> int { *s = sym; return IMC_OK; }, &dd)) return rc;
+    if (device_train_mode() == 1 && must_train(L, nsym)) return obs_upload_and_train(lk, sym, nsym, on_device, out);
+    if (int rc = dictionary_for(lk, L, nsym, [&](HostSymbols *s) -> int { *s = sym; return IMC_OK; }, nullptr, &dd)) return rc;
     lk.unlock();
     tm.mark();
     imc::EncodedLevels enc;
@@ -717,7 +983,7 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
     }
     tm.mark();
     if (PhaseTimer::enabled())   // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
-        std::fprintf(stderr, "[imc host] create %zu columns: train %.1f ms, encode %.1f ms, upload %.1f ms, install %.1f ms (%s encoder)\n", L,
+        std::fprintf(stderr, "[imc host] create %zu columns: train %.1f ms, encode %.1f ms, upload %.1f ms, install %.1f ms (%s encoder, host trainer)\n", L,
                      tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
     g.last_ingest[0] = g.last_ingest[1] = g.last_ingest[2] = 0;   // (imc_last_ingest: parsed and validated on the host)
     g.last_ingest[3] = L;
@@ -807,7 +1073,8 @@ int finish_device_chunk(std::unique_lock<std::mutex> &lk, imc_obs *o)
         *s = symbols_in(head, wide_raw);
         return IMC_OK;
     };
-    if (int rc = dictionary_for(lk, o->L, o->nsym, copy_head, &dd)) return rc;
+    const TrainPiece piece{o->d_sym, (int)unit, o->L};   // (with imc_set_device_training(1) no head comes back)
+    if (int rc = dictionary_for(lk, o->L, o->nsym, copy_head, &piece, &dd)) return rc;
     std::vector<uint8_t>().swap(head);
     HIP_TRY(hipSetDevice(g.device));
     return dd && dd->dict.alphabet > o->nsym ? device_encode(dd, &o, 1) : IMC_OK;
@@ -1159,26 +1426,49 @@ int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
     if (total < imc::TrainLimits().train_min) return IMC_OK;
     // ---- sample: the raw symbols come back to the host (the chunks keep them on the device) - all of them for the host
     //      encoder, only the training heads when the device encodes ----
+    //      With imc_set_device_training(1) the sample stays where it is: the heads are the pieces of a device training,
+    //      and with the device encoder nothing comes back at all.
     const size_t share = imc::recompress_share(obs.size(), wide_raw);
     std::vector<std::vector<uint8_t>> raw(obs.size());
+    bool train_on_device = false;
+    size_t copied = 0;
     {
         std::lock_guard<std::mutex> lk(g_mu);
+        train_on_device = device_train_mode() == 1;
         // nothing to gain if these chunks already share a dictionary trained on at least this much data
         // (a second Likelihood over the same forwarders, a subset of a recompressed set)
         bool same = obs[0]->dict != nullptr;
         for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
         if (same && obs[0]->dict->trained_on >= total) return IMC_OK;
         HIP_TRY(hipSetDevice(g.device));
-        for (size_t k = 0; k < obs.size(); ++k) {
+        for (size_t k = 0; k < obs.size() && !(train_on_device && on_device); ++k) {
             raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
             HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
+            copied += raw[k].size();
         }
     }
-    std::vector<uint8_t> sample = imc::recompress_sample(raw, share, unit);
+    std::vector<uint8_t> sample;
+    if (!train_on_device) sample = imc::recompress_sample(raw, share, unit);
     tm.mark();
-    // ---- train (host, unlocked) ----
-    const std::shared_ptr<DictDev> nd = make_dictionary(symbols_in(sample, wide_raw), nsym, total);
-    std::vector<uint8_t>().swap(sample);
+    // ---- train (host, unlocked - or on the device, under the lock) ----
+    std::shared_ptr<DictDev> nd;
+    if (train_on_device) {
+        std::vector<TrainPiece> pieces;
+        size_t sample_len = 0;
+        for (imc_obs *o : obs) {
+            pieces.push_back({o->d_sym, (int)unit, std::min(o->L, share)});
+            sample_len += pieces.back().n;
+        }
+        std::lock_guard<std::mutex> lk(g_mu);
+        HIP_TRY(hipSetDevice(g.device));
+        if (int rc = device_train(pieces.data(), pieces.size(), nsym, sample_len, total, &nd)) return rc;
+    } else {
+        imc::TrainStats st;
+        nd = make_dictionary(symbols_in(sample, wide_raw), nsym, total, &st);
+        std::vector<uint8_t>().swap(sample);
+        std::lock_guard<std::mutex> lk(g_mu);
+        note_training(0, st);
+    }
     tm.mark();
     // ---- encode (host encoder only; unlocked) ----
     std::vector<imc::EncodedLevels> enc(obs.size());
@@ -1208,8 +1498,8 @@ int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
         }
     tm.mark();
     if (PhaseTimer::enabled())
-        std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder)\n",
-                     obs.size(), total, tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
+        std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder, %s trainer, %zu symbol bytes to the host)\n",
+                     obs.size(), total, tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host", train_on_device ? "device" : "host", copied);
     return IMC_OK;
 }
 
@@ -3012,6 +3302,22 @@ int imc_last_ingest(uint64_t *out4)
     if (!out4) return fail(IMC_ERR_ARG, "out4 is null");
     std::lock_guard<std::mutex> lk(g_mu);
     for (int i = 0; i < 4; ++i) out4[i] = g.last_ingest[i];
+    return IMC_OK;
+}
+
+int imc_set_device_training(int mode)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device training mode must be 0 (host trainer) or 1 (device trainer)");
+    g.device_train = mode;
+    return IMC_OK;
+}
+
+int imc_last_training(uint64_t *out4)
+{
+    if (!out4) return fail(IMC_ERR_ARG, "out4 is null");
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (int i = 0; i < 4; ++i) out4[i] = g.last_training[i];
     return IMC_OK;
 }
 

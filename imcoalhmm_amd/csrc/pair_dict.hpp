@@ -177,10 +177,29 @@ inline void init_dict(PairDict &d, int nsym)
     d.span.assign(nsym, 1);
 }
 
+// The order in which a round's candidates (count, key = a << 16 | b) become tokens: count descending, then key ascending -
+// a total order, so the dictionary does not depend on the order the candidates were found in.
+typedef std::pair<uint64_t, uint32_t> RoundCandidate;
+inline bool round_candidate_before(const RoundCandidate &x, const RoundCandidate &y)
+{
+    return x.first != y.first ? x.first > y.first : x.second < y.second;
+}
+
+// How many of `candidates` a round takes at this alphabet size; fewer than round_size(alphabet) makes it the last round.
+inline size_t round_take(size_t candidates, int alphabet)
+{
+    return std::min<size_t>({candidates, (size_t)round_size(alphabet), (size_t)(kMaxAlphabet - alphabet)});
+}
+
+// What a training did (imc_last_training): calls of train_dict (0 for raw alphabets beyond 256 symbols) and 16-bit rounds.
+struct TrainStats {
+    uint64_t sample = 0, attempts = 0, rounds = 0;
+};
+
 // Phase 2: extend a full byte dictionary (or the bare raw alphabet when that has more than 256 symbols) in rounds on
 // `seq`, the byte-level token stream (raw stream) of the training chunk, first column removed.  A pair needs
 // `min_count` occurrences to become a token.
-inline void train_dict_wide(PairDict &d, std::vector<tok_t> seq, size_t min_count, int max_depth = 0)
+inline void train_dict_wide(PairDict &d, std::vector<tok_t> seq, size_t min_count, int max_depth = 0, TrainStats *stats = nullptr)
 {
     if (d.alphabet < wide_base(d.nsym)) return;
     std::vector<int> depth = dict_depths(d);
@@ -191,7 +210,7 @@ inline void train_dict_wide(PairDict &d, std::vector<tok_t> seq, size_t min_coun
         keys.resize(n - 1);
         for (size_t t = 0; t + 1 < n; ++t) keys[t] = (uint32_t)seq[t] << 16 | seq[t + 1];
         radix_sort_u32(keys, scratch);
-        std::vector<std::pair<uint64_t, uint32_t>> cand;   // (count, key)
+        std::vector<RoundCandidate> cand;   // (count, key)
         for (size_t i = 0; i < keys.size();) {
             size_t j = i;
             while (j < keys.size() && keys[j] == keys[i]) ++j;
@@ -200,11 +219,9 @@ inline void train_dict_wide(PairDict &d, std::vector<tok_t> seq, size_t min_coun
             i = j;
         }
         if (cand.empty()) break;
-        std::sort(cand.begin(), cand.end(),
-                  [](const std::pair<uint64_t, uint32_t> &x, const std::pair<uint64_t, uint32_t> &y) {
-                      return x.first != y.first ? x.first > y.first : x.second < y.second;
-                  });
-        const size_t take = std::min<size_t>({cand.size(), round, (size_t)(kMaxAlphabet - d.alphabet)});
+        std::sort(cand.begin(), cand.end(), round_candidate_before);
+        const size_t take = round_take(cand.size(), d.alphabet);
+        if (stats) ++stats->rounds;
         std::vector<uint32_t> rk;
         std::vector<tok_t> ri;
         for (size_t q = 0; q < take; ++q) {
@@ -347,32 +364,45 @@ inline size_t wide_min_count(size_t sample_tokens, size_t forced, const TrainLim
     return sample_tokens >= 400000 ? lim.wide_min_count : sample_tokens >= 200000 ? 4 : 3;
 }
 
+inline size_t training_head(size_t L, bool wide_raw, const TrainLimits &lim = TrainLimits());
+
+// Whether a byte phase that stopped at `alphabet` tokens on a sample of n symbols is run again with the next lower
+// threshold (see train_dictionary): only a nearly full dictionary on a sample of training size.
+inline bool byte_phase_retry(int alphabet, size_t n, const TrainLimits &lim)
+{
+    return !(alphabet >= kByteAlphabet || alphabet < 3 * kByteAlphabet / 4 || n < lim.train_min);
+}
+constexpr size_t kByteThresholds[3] = {64, 8, 2};   // the byte phase's min_count, attempt by attempt
+
 // Train a pair dictionary on L symbols (exactly one of host / host16 is non-null).  forced_min_count: see
 // wide_min_count(); max_depth: see train_dict().
 inline TrainedDict train_dictionary(const uint8_t *host, const tok_t *host16, size_t L, int nsym, size_t forced_min_count, int max_depth,
-                                    const TrainLimits &lim = TrainLimits())
+                                    const TrainLimits &lim = TrainLimits(), TrainStats *stats = nullptr)
 {
     TrainedDict t;
+    if (stats) *stats = TrainStats{training_head(L, host16 != nullptr, lim), 0, 0};
     if (host16) {                                    // symbols are not bytes: straight to the 16-bit rounds on the raw stream
         init_dict(t.dict, nsym);
         const size_t nt = std::min(L - 1, lim.wide_train_tokens * 8);
-        train_dict_wide(t.dict, std::vector<tok_t>(host16 + 1, host16 + 1 + nt), lim.wide_min_count, max_depth);
+        train_dict_wide(t.dict, std::vector<tok_t>(host16 + 1, host16 + 1 + nt), lim.wide_min_count, max_depth, stats);
     } else {
         const size_t n = std::min(L - 1, lim.train_max);
-        train_dict(t.dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), 64, max_depth);
+        train_dict(t.dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), kByteThresholds[0], max_depth);
+        if (stats) stats->attempts = 1;
         // The 16-bit rounds only start from a FULL byte dictionary.  On a large sample the byte phase can stop a few entries
         // short (the best remaining pair under the depth cap has 63 occurrences) - and the chunk then has no level beyond
         // ~250 tokens at all (seen once in a bench run: 96 instead of 150 columns per token, every evaluation 25-40 %
         // slower).  Retrain with a lower threshold rather than lose the wide levels.
-        for (size_t min_count : {(size_t)8, (size_t)2}) {
-            if (t.dict.alphabet >= kByteAlphabet || t.dict.alphabet < 3 * kByteAlphabet / 4 || n < lim.train_min) break;
+        for (size_t min_count : {kByteThresholds[1], kByteThresholds[2]}) {
+            if (!byte_phase_retry(t.dict.alphabet, n, lim)) break;
             train_dict(t.dict, nsym, std::vector<uint8_t>(host + 1, host + 1 + n), min_count, max_depth);
+            if (stats) ++stats->attempts;
         }
         if (t.dict.alphabet >= kByteAlphabet) {      // 16-bit tokens: rounds over the whole chunk's byte-level stream
             const size_t cols = std::min(L, lim.wide_train_tokens * 96);   // a byte-level token covers ~60-100 columns
             const std::vector<uint8_t> lvl256 = encode_bytes(t.dict, host, cols, nullptr);
             const size_t nt = std::min(lvl256.size() - 1, lim.wide_train_tokens);
-            train_dict_wide(t.dict, std::vector<tok_t>(lvl256.begin() + 1, lvl256.begin() + 1 + nt), wide_min_count(nt, forced_min_count, lim), max_depth);
+            train_dict_wide(t.dict, std::vector<tok_t>(lvl256.begin() + 1, lvl256.begin() + 1 + nt), wide_min_count(nt, forced_min_count, lim), max_depth, stats);
         }
     }
     t.depth = dict_depths(t.dict);
@@ -382,7 +412,7 @@ inline TrainedDict train_dictionary(const uint8_t *host, const tok_t *host16, si
 
 // Columns of a chunk's head that train_dictionary() looks at: a dictionary trained on the head alone is the dictionary
 // trained on the whole chunk.
-inline size_t training_head(size_t L, bool wide_raw, const TrainLimits &lim = TrainLimits())
+inline size_t training_head(size_t L, bool wide_raw, const TrainLimits &lim)
 {
     return std::min(L, wide_raw ? lim.wide_train_tokens * 8 + 1 : std::max(lim.train_max + 1, lim.wide_train_tokens * 96));
 }

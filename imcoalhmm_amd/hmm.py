@@ -110,7 +110,14 @@ def set_device_ingest(mode):
     _capi.check(_capi.lib().imc_set_device_ingest(int(mode)))
 
 
-_DEVICE_SYMBOL_BYTES = {"|u1": 1, "<i2": 2, "<u2": 2, "<i4": 4}
+def set_device_training(mode):
+    """Where a pair dictionary is trained (``imc_set_device_training``): 0 = the host trainer (default), 1 = the device
+    trainer - the same dictionary, entry for entry, from the symbols already in HBM; no symbols are then copied back
+    for training.  ``_capi.last_training()`` says which path the last training took."""
+    _capi.check(_capi.lib().imc_set_device_training(int(mode)))
+
+
+_DEVICE_SYMBOL_BYTES ={"|u1": 1, "<i2": 2, "<u2": 2, "<i4": 4}
 
 
 def forward_states(handles, pis, Ts, Es, as_operator):

@@ -107,7 +107,7 @@ int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out);   /* al
  * file's header is checked on the host as ever and its payload goes up packed - 2-bit payloads are unpacked by a kernel,
  * 8- and 16-bit ones are taken as they are.  The symbols are validated against nsym on the device and the chunk is built
  * from there as imc_obs_create_device builds one, so these chunks are always encoded on the device, whatever
- * imc_set_device_encoding says; dictionary training stays on the host.  Symbols, dictionaries, token streams and results
+ * imc_set_device_encoding says; the dictionary is trained where imc_set_device_training says.  Symbols, dictionaries, token streams and results
  * are those of mode 0, and so are the return code and the message of every error, in file order (an error in one slab is
  * reported before the next slab is looked at).  The device parser DECLINES a file that has a slab without any whitespace
  * or a digit run longer than 16: the host parser then reads it from its start (also what happens to anything that is
@@ -130,7 +130,8 @@ int imc_last_ingest(uint64_t *out4);
  * synchronises hip_stream (a hipStream_t; NULL is the default stream), copies the symbols into a buffer of its own on
  * the device (narrowed to bytes, or to 16 bits beyond 256 symbols) and keeps no reference to d_sym.  Validation and the
  * token streams are computed on the device (csrc/kernels_encode.hpp; the tokens the host encoder would produce); only
- * when the alphabet has no dictionary yet does the head that dictionary training looks at travel to the host.
+ * when the alphabet has no dictionary yet and imc_set_device_training is 0 does the head that dictionary training looks
+ * at travel to the host.
  * IMC_ERR_ARG - checked before any HIP call - for null pointers, another sym_bytes, nsym outside [1,4096], byte symbols
  * with nsym > 256 and L >= 2^31; IMC_ERR_ARG as well for a pointer that is not device memory of the library's device
  * (hipPointerGetAttributes: an error, never a fault); IMC_ERR_SYMBOL names the first column whose symbol is outside
@@ -243,10 +244,28 @@ int imc_dictionary_reset(void);
  * whole chunk (imc::encode_levels) - imc_obs_recompress first copies every raw stream back for it.  1: on the device,
  * from the symbols that are there anyway (csrc/kernels_encode.hpp): imc_obs_create* still validate and train on the
  * host; imc_obs_recompress copies back only the training heads and encodes all chunks of an alphabet in one batched run.
- * Dictionary training is the host's in both modes, and the device encoder produces exactly the host encoder's tokens, so
+ * Dictionary training does not depend on this mode (imc_set_device_training), and the device encoder produces exactly the host encoder's tokens, so
  * dictionaries, streams and results are bit-identical; the mode changes set-up time only.  imc_obs_create_device always
  * encodes on the device.  IMC_DEVICE_ENCODE=0|1 in the environment sets the mode at start-up. */
 int imc_set_device_encoding(int mode);
+/* Where a pair dictionary is trained.  0 (default): on the host, one thread (imc::train_dictionary, csrc/pair_dict.hpp);
+ * a creation whose symbols are on the device copies the head that training looks at back for it, imc_obs_recompress
+ * every chunk's head.  1: on the device (csrc/kernels_train.hpp), from the symbols that are there: per byte merge one
+ * count of all adjacent pairs, the winner chosen by the host's rule (largest count, then smallest pair; the depth cap
+ * applies) and one replacement pass of the device encoder; per 16-bit round the counts of all distinct pairs in a table
+ * in device memory, ranked on the host with the host trainer's own comparator.  The host trainer is the specification:
+ * from the same symbols and the same IMC_DICT_MIN_COUNT / IMC_DICT_MAX_DEPTH the device trainer gives the same
+ * dictionary entry for entry, so token streams, operator tables and results are bit-identical and the mode changes
+ * set-up time only (tests/test_gpu_device_training.py; figures: profiles/README.md).  With mode 1 imc_obs_create* upload
+ * the symbols before they train, imc_obs_create_device, device ingestion and imc_obs_create_pairwise copy no symbols
+ * back, and neither does imc_obs_recompress while imc_set_device_encoding is 1 (the host encoder still gets the raw
+ * streams it needs).  The device trainer runs on the library's stream with the mutex held.  It needs no device to be
+ * set; IMC_DEVICE_TRAIN=0|1 in the environment sets the mode at start-up; any other mode is IMC_ERR_ARG. */
+int imc_set_device_training(int mode);
+/* The last dictionary training of this process: out4 = {path (0 host, 1 device), symbols of the sample that training
+ * could look at, runs of the byte phase (1 to 3: thresholds 64, 8, 2; 0 for raw alphabets beyond 256 symbols), 16-bit
+ * rounds}.  All zero before the first training.  For inspection and tests. */
+int imc_last_training(uint64_t *out4);
 /* Kernel timing with HIP events on the launch stream.  After imc_profile_enable(1) every
  * propagate/stitch launch is bracketed by events; imc_profile_read synchronises, returns the
  * accumulated device milliseconds and launch counts since the last reset, and resets.  ms_propagate is the
