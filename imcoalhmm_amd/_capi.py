@@ -73,6 +73,18 @@ SIGNATURES = [
     ("imc_set_device_ingest", ctypes.c_int, [ctypes.c_int]),
     ("imc_obs_create_pairwise", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _vpp]),
     ("imc_last_ingest", ctypes.c_int, [_u64p]),
+    ("imc_read_fasta", ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    ("imc_encode_triplet", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _u8p]),
+    ("imc_aln_open_fasta", ctypes.c_int, [ctypes.c_char_p, _vpp]),
+    ("imc_aln_count", ctypes.c_int, [ctypes.c_void_p]),
+    ("imc_aln_name", ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int]),
+    ("imc_aln_length", ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),
+    ("imc_aln_sequence", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]),
+    ("imc_aln_info", ctypes.c_int, [ctypes.c_void_p, _u64p]),
+    ("imc_aln_free", ctypes.c_int, [ctypes.c_void_p]),
+    ("imc_obs_create_from_alignment", ctypes.c_int, [ctypes.c_void_p, _i32p, ctypes.c_int, _vpp]),
     ("imc_set_device_training", ctypes.c_int, [ctypes.c_int]),
     ("imc_last_training", ctypes.c_int, [_u64p]),
     ("imc_profile_enable", ctypes.c_int, [ctypes.c_int]),
@@ -193,10 +205,10 @@ def set_wide_blocked(mode):
 
 def last_ingest():
     """Dict view of imc_last_ingest(): how the last chunk of this process was created.  ``path`` is "host", "text",
-    "cache" or "pairwise" (the last three: on the device)."""
+    "cache", "pairwise" or "alignment" (the last four: on the device; "alignment": columns of a resident alignment)."""
     arr = (ctypes.c_uint64 * 4)()
     check(lib().imc_last_ingest(arr))
-    return {"path": ("host", "text", "cache", "pairwise")[int(arr[0])], "bytes": int(arr[1]), "slabs": int(arr[2]),
+    return {"path": ("host", "text", "cache", "pairwise", "alignment")[int(arr[0])], "bytes": int(arr[1]), "slabs": int(arr[2]),
             "columns": int(arr[3])}
 
 

@@ -18,9 +18,9 @@
 //
 // Host side, in the order of this file: context and device memory (dev_alloc, DevBuf); chunks and dictionaries (the
 // pieces a chunk is made of - padded buffers, obs_new, dictionary_for - then the one level loop install_levels with its
-// host and device sources, obs_upload / obs_from_device, the device ingestion of files and sequence pairs,
-// recompress_alphabet; the training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's and the parse
-// ingest_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
+// host and device sources, obs_upload / obs_from_device, the device ingestion of files and sequence pairs, resident
+// alignments, recompress_alphabet; the training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's and the
+// parses ingest_tiles.hpp's and align_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
 // and its builder, one enqueue function per kernel family, the model layer, the C ABI.
 #include <hip/hip_runtime.h>
 
@@ -59,12 +59,14 @@
 #include "kernels_encode.hpp"
 #include "kernels_train.hpp"
 #include "kernels_ingest.hpp"
+#include "kernels_align.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
 #include "model_host.hpp"
 #include "kernels_model.hpp"
 #include "../../include/imcoal_model.h"
 #include "obs_io.hpp"
+#include "fasta_io.hpp"
 
 static_assert(sizeof(imc::Desc4) == sizeof(int4) && alignof(imc::Desc4) == alignof(int4), "descriptor entries are uploaded as int4");
 
@@ -322,6 +324,12 @@ public:
         p_ = nullptr;
     }
     T *get() const { return p_; }
+    T *release()                  // the caller owns the buffer from now on (dev_free)
+    {
+        T *p = p_;
+        p_ = nullptr;
+        return p;
+    }
     explicit operator bool() const { return p_ != nullptr; }
 };
 
@@ -342,6 +350,17 @@ struct imc_obs {
     size_t ntok[imc::kNumLevels] = {};
     int alphabet[imc::kNumLevels] = {};
     std::vector<uint32_t> tok_count[imc::kNumLevels];   // byte levels: occurrences of every token id (hot-set choice of the hybrid table)
+};
+
+// An alignment whose sequences are resident on the device: all records' bases back to back in one buffer (not word
+// aligned), names and the record table on the host.
+struct imc_aln {
+    pid_t pid = 0;
+    int device = 0;
+    std::vector<std::string> names;
+    std::vector<uint64_t> start, length;   // of every record, in bytes of d_bases
+    uint8_t *d_bases = nullptr;            // the file's size rounded up to 16 (device parser) / the bases' (host reader)
+    uint64_t info[4] = {0, 0, 0, 0};       // imc_aln_info
 };
 
 namespace {
@@ -1394,6 +1413,197 @@ int obs_from_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **ou
     st.release();
     if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
     if (rc == IMC_OK) note_ingest(3, 2 * (uint64_t)L, slabs, L);
+    return ingest_result(rc, o, out);
+}
+
+// ---- resident alignments ------------------------------------------------------------------------------------
+// imc_aln_open_fasta: the file's bytes go up through the same slabs and staging buffers as a text observation file and
+// are parsed there (kernels_align.hpp; the rules and the slab cut are align_tiles.hpp's): the kept bases of all slabs
+// land back to back in one buffer of the file's size, every header reports where it stands, and the host takes the names
+// from the pinned slab.  The state, the record count and the base count at the end of slab k are read from its total
+// before slab k + 1 is queued.  A file the device parser declines is read by imc::read_fasta and its sequences uploaded.
+void aln_release(imc_aln *a)
+{
+    if (a->pid == getpid()) dev_free(a->d_bases);
+    a->d_bases = nullptr;
+}
+
+struct PinnedBuf {               // created, used and destroyed with g_mu held
+    void *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
+
+// FASTA file of file_bytes bytes, fp at its start, into a (empty).  *declined: the device parser does not take this file;
+// a holds nothing then.
+int aln_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, imc_aln *a, bool *declined)
+{
+    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
+    const size_t tiles_max = (slab + ALN_TILE - 1) / ALN_TILE;
+    const uint64_t room = (file_bytes + 15) & ~(uint64_t)15;
+    IngestStage st;
+    DevBuf<uint8_t> bases;
+    DevBuf<imc::AlnSummary> sums;
+    DevBuf<AlnTileIn> tile_in;
+    DevBuf<imc::AlnTotal> total;
+    DevBuf<imc::AlnRecord> table;
+    PinnedBuf pinned;                                                   // two totals, then the record table
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1)) return rc;
+    HIP_TRY(bases.alloc((size_t)room));
+    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::AlnSummary)));
+    HIP_TRY(tile_in.alloc(tiles_max * sizeof(AlnTileIn)));
+    HIP_TRY(total.alloc(sizeof(imc::AlnTotal)));
+    HIP_TRY(table.alloc(imc::kMaxAlnRecords * sizeof(imc::AlnRecord)));
+    HIP_TRY(hipHostMalloc(&pinned.p, 2 * sizeof(imc::AlnTotal) + imc::kMaxAlnRecords * sizeof(imc::AlnRecord), hipHostMallocDefault));
+    imc::AlnTotal *verdict = static_cast<imc::AlnTotal *>(pinned.p);
+    imc::AlnRecord *recs = reinterpret_cast<imc::AlnRecord *>(verdict + 2);
+    uint64_t kept = 0, sent = 0, slabs = 0, consumed = 0;
+    uint32_t state = imc::kAlnStart0, prev = '\n';
+    bool eof = false;
+    auto read_into = [&](uint8_t *dst, size_t want) -> size_t {       // WITHOUT g_mu
+        want = (size_t)std::min<uint64_t>(want, file_bytes - consumed);
+        const size_t got = want ? std::fread(dst, 1, want, fp) : 0;
+        consumed += got;
+        if (got < want || consumed == file_bytes) eof = true;
+        return got;
+    };
+    lk.unlock();
+    size_t fill = read_into(st.host[0], slab);
+    lk.lock();
+    for (int cur = 0;; cur ^= 1) {
+        const bool last = eof;
+        const size_t cut = imc::aln_slab_cut(st.host[cur], fill, last, state);
+        if (cut == 0 && !last) { *declined = true; return IMC_OK; }
+        if (cut == 0) break;
+        HIP_TRY(hipSetDevice(g.device));
+        const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + ALN_TILE - 1) / ALN_TILE), have = (uint32_t)a->names.size();
+        HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
+        hipLaunchKernelGGL(k_aln_summary, dim3(tiles), dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, sums.get());
+        hipLaunchKernelGGL(k_aln_scan, dim3(1), dim3(ALN_SCAN_THREADS), 0, g.stream, (const imc::AlnSummary *)sums.get(), tiles, state, tile_in.get(), total.get());
+        hipLaunchKernelGGL(k_aln_scatter, dim3(tiles), dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, (const AlnTileIn *)tile_in.get(),
+                           bases.get(), kept, room, table.get(), have, imc::kMaxAlnRecords);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::AlnTotal), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipEventRecord(st.done[cur], g.stream));
+        sent += cut;
+        ++slabs;
+        // the next slab: what lies behind the cut, then more of the file - read while this one is on the device
+        const size_t carry = fill - cut;
+        lk.unlock();
+        size_t next_fill = carry;
+        if (carry) std::memcpy(st.host[cur ^ 1], st.host[cur] + cut, carry);
+        if (!last) next_fill += read_into(st.host[cur ^ 1] + carry, slab - carry);
+        const hipError_t waited = hipEventSynchronize(st.done[cur]);
+        lk.lock();
+        if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
+        const imc::AlnTotal t = verdict[cur];
+        if (t.decline || (uint64_t)have + t.hdr > imc::kMaxAlnRecords) { *declined = true; return IMC_OK; }
+        if (kept + t.seq > room) return fail(IMC_ERR_HIP, "alignment: more bases than the file can hold");
+        if (t.hdr) {                                                    // the names, from the slab's bytes in pinned memory
+            HIP_TRY(hipSetDevice(g.device));
+            HIP_TRY(hipMemcpyAsync(recs, table.get() + have, t.hdr * sizeof(imc::AlnRecord), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            for (uint32_t k = 0; k < t.hdr; ++k) {
+                const size_t at = (size_t)recs[k].slab_offset + 1;
+                if (at > cut || recs[k].start > kept + t.seq) return fail(IMC_ERR_HIP, "alignment: a header outside its slab");
+                std::string name = imc::aln_header_name(st.host[cur], cut, at - 1);
+                if (name.empty()) { *declined = true; return IMC_OK; }
+                a->names.push_back(std::move(name));
+                a->start.push_back(recs[k].start);
+            }
+        }
+        kept += t.seq;
+        state = t.exit;
+        prev = st.host[cur][cut - 1];
+        fill = next_fill;
+        if (last) break;
+    }
+    std::set<std::string> seen(a->names.begin(), a->names.end());
+    if (seen.size() != a->names.size()) { *declined = true; return IMC_OK; }
+    for (size_t k = 0; k < a->start.size(); ++k) a->length.push_back((k + 1 < a->start.size() ? a->start[k + 1] : kept) - a->start[k]);
+    a->d_bases = bases.release();                                       // the alignment owns the buffer now
+    a->info[0] = 1; a->info[1] = sent; a->info[2] = slabs; a->info[3] = a->names.size();
+    return IMC_OK;
+}
+
+// The records of the host reader into a: one buffer of the bases' size, uploaded record by record.
+int aln_upload_host(const imc::FastaRecords &r, imc_aln *a)
+{
+    uint64_t total = 0;
+    for (size_t k = 0; k < r.names.size(); ++k) {
+        a->names.push_back(r.names[k]);
+        a->start.push_back(total);
+        a->length.push_back(r.seqs[k].size());
+        total += r.seqs[k].size();
+    }
+    HIP_TRY(hipSetDevice(g.device));
+    HIP_TRY(dev_alloc((void **)&a->d_bases, (size_t)((total + 15) & ~(uint64_t)15)));
+    for (size_t k = 0; k < r.names.size(); ++k)
+        if (!r.seqs[k].empty()) HIP_TRY(hipMemcpy(a->d_bases + a->start[k], r.seqs[k].data(), r.seqs[k].size(), hipMemcpyHostToDevice));
+    a->info[0] = 0; a->info[1] = 0; a->info[2] = 0; a->info[3] = a->names.size();
+    return IMC_OK;
+}
+
+// imc_aln_open_fasta (arguments checked).  Opening the file needs no device.
+int aln_open(const char *path, imc_aln **out)
+{
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+    struct stat sb;
+    const bool regular = fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode);   // (a pipe cannot be read twice)
+    std::unique_ptr<imc_aln> a(new (std::nothrow) imc_aln());
+    if (!a) { std::fclose(fp); return fail(IMC_ERR_OOM, "host allocation failed"); }
+    bool declined = !regular;
+    {
+        struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{fp};
+        std::unique_lock<std::mutex> lk(g_mu);
+        if (int rc = ensure_ctx()) return rc;
+        HIP_TRY(hipSetDevice(g.device));
+        a->pid = g.pid;
+        a->device = g.device;
+        if (regular) {
+            const int rc = aln_parse_device(lk, fp, (uint64_t)sb.st_size, a.get(), &declined);
+            if (rc != IMC_OK) { (void)hipStreamSynchronize(g.stream); return rc; }
+        }
+    }
+    if (declined) {                                     // the host reader, from the start of the file, without g_mu
+        a->names.clear(); a->start.clear(); a->length.clear();
+        imc::FastaRecords records;
+        const imc::IoResult r = imc::read_fasta(path, records);
+        if (r.code) return fail(r.code, r.msg);
+        std::unique_lock<std::mutex> lk(g_mu);
+        if (int rc = aln_upload_host(records, a.get())) {
+            const std::string msg = g_err;
+            aln_release(a.get());
+            return fail(rc, msg);
+        }
+    }
+    *out = a.release();
+    return IMC_OK;
+}
+
+// imc_obs_create_from_alignment (arguments checked): K sequences of L bases each, resident at the given offsets.
+int obs_from_alignment(const imc_aln *a, const uint64_t *offsets, int k, size_t L, imc_obs **out)
+{
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    if (a->pid != g.pid) return fail(IMC_ERR_HIP, "alignment was opened in another process");
+    HIP_TRY(hipSetDevice(g.device));
+    imc_obs *o = obs_new(L, k == 2 ? 3 : 65);
+    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    int rc = alloc_symbols(o);
+    if (rc == IMC_OK && L) {
+        const dim3 grid((uint32_t)((L + (size_t)ALN_COLUMNS * ALN_THREADS - 1) / ((size_t)ALN_COLUMNS * ALN_THREADS)));
+        if (k == 2)
+            hipLaunchKernelGGL(k_aln_columns<2>, grid, dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], (uint64_t)0, (uint32_t)L, o->d_sym);
+        else
+            hipLaunchKernelGGL(k_aln_columns<3>, grid, dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], offsets[2], (uint32_t)L, o->d_sym);
+        if (hipGetLastError() != hipSuccess) rc = fail(IMC_ERR_HIP, "alignment: the column kernel could not be launched");
+    }
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) note_ingest(4, 0, 0, L);
     return ingest_result(rc, o, out);
 }
 
@@ -3346,6 +3556,103 @@ int imc_encode_pairwise(const char *seq1, const char *seq2, size_t L, uint8_t *s
     if (L && (!seq1 || !seq2 || !sym_out)) return fail(IMC_ERR_ARG, "null argument");
     imc::encode_pairwise(seq1, seq2, L, sym_out);
     return IMC_OK;
+}
+
+int imc_encode_triplet(const char *seq1, const char *seq2, const char *seq3, size_t L, uint8_t *sym_out)
+{
+    if (L && (!seq1 || !seq2 || !seq3 || !sym_out)) return fail(IMC_ERR_ARG, "null argument");
+    imc::encode_triplet(seq1, seq2, seq3, L, sym_out);
+    return IMC_OK;
+}
+
+int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
+{
+    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
+    imc::FastaRecords r;
+    const imc::IoResult io = imc::read_fasta(path, r);
+    if (io.code) return fail(io.code, io.msg);
+    *count = (int)r.names.size();
+    if (index < 0 || (size_t)index >= r.names.size()) {
+        if (length) *length = 0;
+        return name_out || seq_out ? fail(IMC_ERR_ARG, "record index out of range") : IMC_OK;
+    }
+    const std::string &name = r.names[(size_t)index], &seq = r.seqs[(size_t)index];
+    if (length) *length = seq.size();
+    if (name_out && name_capacity > name.size()) std::memcpy(name_out, name.c_str(), name.size() + 1);
+    if (seq_out && seq_capacity >= seq.size() && !seq.empty()) std::memcpy(seq_out, seq.data(), seq.size());
+    return IMC_OK;
+}
+
+int imc_aln_open_fasta(const char *path, imc_aln **out)
+{
+    if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
+    return aln_open(path, out);
+}
+
+int imc_aln_count(const imc_aln *aln) { return aln ? (int)aln->names.size() : 0; }
+
+const char *imc_aln_name(const imc_aln *aln, int index)
+{
+    return aln && index >= 0 && (size_t)index < aln->names.size() ? aln->names[(size_t)index].c_str() : nullptr;
+}
+
+size_t imc_aln_length(const imc_aln *aln, int index)
+{
+    return aln && index >= 0 && (size_t)index < aln->length.size() ? (size_t)aln->length[(size_t)index] : 0;
+}
+
+int imc_aln_sequence(const imc_aln *aln, int index, char *out, size_t capacity)
+{
+    if (!aln) return fail(IMC_ERR_ARG, "aln is null");
+    if (index < 0 || (size_t)index >= aln->names.size()) return fail(IMC_ERR_ARG, "record index out of range");
+    const size_t n = (size_t)aln->length[(size_t)index];
+    if (n && !out) return fail(IMC_ERR_ARG, "out is null");
+    if (capacity < n) return fail(IMC_ERR_ARG, "capacity smaller than the sequence");
+    if (!n) return IMC_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (int rc = ensure_ctx()) return rc;
+    if (aln->pid != g.pid) return fail(IMC_ERR_HIP, "alignment was opened in another process");
+    HIP_TRY(hipSetDevice(aln->device));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    HIP_TRY(hipMemcpy(out, aln->d_bases + aln->start[(size_t)index], n, hipMemcpyDeviceToHost));
+    return IMC_OK;
+}
+
+int imc_aln_info(const imc_aln *aln, uint64_t *out4)
+{
+    if (!aln || !out4) return fail(IMC_ERR_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) out4[i] = aln->info[i];
+    return IMC_OK;
+}
+
+int imc_aln_free(imc_aln *aln)
+{
+    if (!aln) return IMC_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    aln_release(aln);
+    delete aln;
+    return IMC_OK;
+}
+
+int imc_obs_create_from_alignment(const imc_aln *aln, const int *members, int k, imc_obs **out)
+{
+    // every argument check before any HIP call
+    if (!out) return fail(IMC_ERR_ARG, "out is null");
+    if (k != 2 && k != 3) return fail(IMC_ERR_ARG, "k must be 2 (pairwise rule) or 3 (triplet rule)");
+    if (!aln || !members) return fail(IMC_ERR_ARG, "null argument");
+    uint64_t offsets[3] = {0, 0, 0};
+    for (int j = 0; j < k; ++j) {
+        if (members[j] < 0 || (size_t)members[j] >= aln->names.size())
+            return fail(IMC_ERR_ARG, "member " + std::to_string(members[j]) + " is not a record of the alignment (" + std::to_string(aln->names.size()) + " records)");
+        offsets[j] = aln->start[(size_t)members[j]];
+    }
+    const uint64_t L = aln->length[(size_t)members[0]];
+    for (int j = 1; j < k; ++j)
+        if (aln->length[(size_t)members[j]] != L)
+            return fail(IMC_ERR_ARG, "sequences differ in length: " + aln->names[(size_t)members[0]] + " has " + std::to_string(L) + " bases, " +
+                                         aln->names[(size_t)members[j]] + " has " + std::to_string(aln->length[(size_t)members[j]]));
+    if (L >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    return obs_from_alignment(aln, offsets, k, (size_t)L, out);
 }
 
 size_t imc_obs_length(const imc_obs *obs) { return obs ? obs->L : 0; }

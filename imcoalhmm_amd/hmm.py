@@ -162,7 +162,7 @@ class Forwarder(object):
 
     ``input_filename`` is a text file of whitespace-separated symbols as written by
     scripts/prepare-alignments.py.  Extra, additive constructors: ``Forwarder.from_array``, ``Forwarder.from_device``,
-    ``Forwarder.from_sequences``.
+    ``Forwarder.from_sequences``, ``Forwarder.from_alignment``.
     """
 
     def __init__(self, input_filename, NSYM):
@@ -240,6 +240,24 @@ class Forwarder(object):
         self._pid = os.getpid()
         return self
 
+    @classmethod
+    def from_alignment(cls, aln, names):
+        """Build from two (pairwise rule, NSYM = 3) or three (triplet rule, NSYM = 65) records of an ``Alignment``, by
+        name: the symbols are made on the device from the resident sequences (``imc_obs_create_from_alignment``); the
+        chunk keeps no reference to the alignment."""
+        names = list(names)
+        if len(names) not in (2, 3):
+            raise ValueError("a chunk is built from two or three sequences, got %d names" % len(names))
+        members = (ctypes.c_int32 * len(names))(*[aln.index(name) for name in names])
+        self = cls.__new__(cls)
+        self.NSYM = 3 if len(names) == 2 else 65
+        self._h = None
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib().imc_obs_create_from_alignment(aln.handle, members, len(names), ctypes.byref(h)))
+        self._h = h.value
+        self._pid = os.getpid()
+        return self
+
     def __len__(self):
         return int(_capi.lib().imc_obs_length(self._h))
 
@@ -306,6 +324,85 @@ class Forwarder(object):
         if getattr(self, "_h", None) and self._pid == os.getpid():
             try:
                 _capi.lib().imc_obs_free(self._h)
+            except Exception:
+                pass
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class Alignment(object):
+    """A FASTA alignment opened ONCE, with its sequences resident in HBM (``imc_aln_open_fasta``): the counterpart of
+    ``SeqIO.to_dict`` at scripts/prepare-alignments.py:66.  The records are found on the device; a file the device parser
+    declines is read by the host reader (``parser`` says which, "device" or "host"), with the same result.  Any pair's or
+    triplet's chunk is then built from the resident sequences (``forwarder``, ``pairs``) without a sequence on the host or
+    an upload per pair.  Use as a context manager, or ``close()``; chunks built from it stay valid."""
+
+    def __init__(self, path):
+        self._h = None
+        h = ctypes.c_void_p()
+        L = _capi.lib()
+        _capi.check(L.imc_aln_open_fasta(os.fsencode(path), ctypes.byref(h)))
+        self._h = h.value
+        self._pid = os.getpid()
+        self.path = path
+        n = L.imc_aln_count(self._h)
+        self.names = [L.imc_aln_name(self._h, k).decode("ascii") for k in range(n)]
+        self.lengths = [int(L.imc_aln_length(self._h, k)) for k in range(n)]
+        self._index = {name: k for k, name in enumerate(self.names)}
+        info = (ctypes.c_uint64 * 4)()
+        _capi.check(L.imc_aln_info(self._h, info))
+        self.parser = "device" if info[0] else "host"
+        self.info = {"parser": self.parser, "bytes": int(info[1]), "slabs": int(info[2]), "records": int(info[3])}
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("the alignment is closed")
+        return self._h
+
+    def index(self, name):
+        try:
+            return self._index[name]
+        except KeyError:
+            raise KeyError("no sequence named %r in %s" % (name, self.path))
+
+    def sequence(self, name):
+        """The record's bases as bytes, copied back from the device (inspection, tests)."""
+        k = self.index(name)
+        buf = ctypes.create_string_buffer(max(self.lengths[k], 1))
+        _capi.check(_capi.lib().imc_aln_sequence(self.handle, k, buf, self.lengths[k]))
+        return buf.raw[:self.lengths[k]]
+
+    def forwarder(self, *names):
+        """``Forwarder`` of two (pairwise rule) or three (triplet rule) records."""
+        return Forwarder.from_alignment(self, names)
+
+    def pairs(self, pairs=None):
+        """{(a, b): Forwarder} for the given pairs of names - or for all pairs, in file order: the dictionary
+        ``prepare.pairwise_forwarders`` gives, from the resident sequences."""
+        if pairs is None:
+            pairs = [(a, b) for i, a in enumerate(self.names) for b in self.names[i + 1:]]
+        pairs = [tuple(p) for p in pairs]
+        for p in pairs:
+            for name in p:
+                self.index(name)
+        return {(a, b): self.forwarder(a, b) for a, b in pairs}
+
+    def __len__(self):
+        return len(self.names)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if getattr(self, "_h", None) and self._pid == os.getpid():
+            try:
+                _capi.lib().imc_aln_free(self._h)
             except Exception:
                 pass
         self._h = None

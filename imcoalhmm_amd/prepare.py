@@ -1,12 +1,15 @@
-"""Pairwise alignment -> observation file, the counterpart of the pairwise branch of the reference's
-scripts/prepare-alignments.py:77-111 (which needs BioPython; this does not).
+"""Pairwise or triplet alignment -> observation file, the counterpart of the pairwise and triplet branches of the
+reference's scripts/prepare-alignments.py:77-146 (which needs BioPython; this does not).
 
     python -m imcoalhmm_amd.prepare examples/example_data.fa out.ziphmm --names hg18,pantro2
     python -m imcoalhmm_amd.prepare in.fa out.imc --names a,b --cache     # packed 2-bit cache
+    python -m imcoalhmm_amd.prepare in.fa out.ziphmm --names a,b,c        # triplet: 65 symbols
 
-The text output is byte-compatible with the reference's ("%d " per column, prepare-alignments.py:99-105) and
-both outputs are accepted by ``Forwarder(input_filename, NSYM=3)``.  Triplet/quartet alignments (ILS model)
-are out of scope.
+The text output is byte-compatible with the reference's ("%d " per column, prepare-alignments.py:99-105 and 142-146)
+and the outputs are accepted by ``Forwarder(input_filename, NSYM=3)`` (pairs) and ``Forwarder(input_filename, NSYM=65)``
+(triplets).  To build chunks straight from an alignment, without a file in between, open it with
+``imcoalhmm_amd.Alignment``.  Quartet alignments are out of scope: the script's own formula (``... + 32*i4``, missing =
+128, lines 186-190) collides with valid codes and disagrees with ILS.py:414-433, which decodes base 4.
 """
 import argparse
 import ctypes
@@ -67,6 +70,37 @@ def encode_pairwise(seq1, seq2):
     return out
 
 
+def encode_triplet(seq1, seq2, seq3):
+    """uint8 symbols per column: i1 + 4*i2 + 16*i3 with A, C, G, T -> 0..3 (either case), 64 = any of the three bases not
+    in ACGT (scripts/prepare-alignments.py:134-146).  65 symbols."""
+    if not len(seq1) == len(seq2) == len(seq3):
+        raise ValueError("sequences differ in length: %d, %d and %d" % (len(seq1), len(seq2), len(seq3)))
+    a, b, c = seq1.encode("ascii"), seq2.encode("ascii"), seq3.encode("ascii")
+    out = np.empty(len(a), dtype=np.uint8)
+    _capi.check(_capi.lib().imc_encode_triplet(a, b, c, len(a), out.ctypes.data_as(_capi._u8p)))
+    return out
+
+
+def read_fasta_native(path):
+    """``read_fasta`` by the library's host reader (``imc_read_fasta``, csrc/fasta_io.hpp): {name: bytes} in file order
+    for ASCII files; IOError for a header without a name and for a byte >= 0x80."""
+    L = _capi.lib()
+    count, length = ctypes.c_int(0), ctypes.c_size_t(0)
+    _capi.check(L.imc_read_fasta(os.fsencode(path), -1, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
+    out = {}
+    for k in range(count.value):
+        _capi.check(L.imc_read_fasta(os.fsencode(path), k, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
+        room = 4096
+        while True:                                     # (a name is never empty: grow the buffer until it fits)
+            name, seq = ctypes.create_string_buffer(room), ctypes.create_string_buffer(max(length.value, 1))
+            _capi.check(L.imc_read_fasta(os.fsencode(path), k, name, len(name), seq, length.value, ctypes.byref(length), ctypes.byref(count)))
+            if name.value:
+                break
+            room *= 16
+        out[name.value.decode("ascii")] = seq.raw[:length.value]
+    return out
+
+
 def pairwise_forwarders(path, pairs=None, in_format="fasta"):
     """{(a, b): Forwarder} for the given pairs of sequence names of an alignment file - or for all pairs, in file order -
     with the pairwise rule applied on the device (``Forwarder.from_sequences``): no intermediate observation file is
@@ -112,25 +146,26 @@ def read_observations(path, nsym=3):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="pairwise alignment -> IMCoalHMM observation file")
+    ap = argparse.ArgumentParser(description="pairwise or triplet alignment -> IMCoalHMM observation file")
     ap.add_argument("in_filename")
     ap.add_argument("output_filename")
-    ap.add_argument("--names", default=None, help="comma-separated pair of sequence names (default: the first two)")
+    ap.add_argument("--names", default=None, help="comma-separated sequence names: two (pairwise) or three (triplet); default: the first two")
     ap.add_argument("--in-format", default="fasta", choices=["fasta", "phylip"])
-    ap.add_argument("--cache", action="store_true", help="write the packed 2-bit cache instead of text")
+    ap.add_argument("--cache", action="store_true", help="write the packed cache instead of text (2 bits per column for a pair, a byte for a triplet)")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
     seqs = read_fasta(args.in_filename) if args.in_format == "fasta" else read_phylip(args.in_filename)
     names = args.names.split(",") if args.names else list(seqs.keys())[:2]
-    if len(names) != 2:
-        ap.error("exactly two sequence names are needed for a pairwise alignment")
-    obs = encode_pairwise(seqs[names[0]], seqs[names[1]])
+    if len(names) not in (2, 3):
+        ap.error("two sequence names are needed for a pairwise alignment, three for a triplet")
+    nsym = 3 if len(names) == 2 else 65
+    obs = encode_pairwise(*(seqs[n] for n in names)) if len(names) == 2 else encode_triplet(*(seqs[n] for n in names))
     if args.cache:
-        write_cache(args.output_filename, obs, 3)
+        write_cache(args.output_filename, obs, nsym)
     else:
         write_text(args.output_filename, obs)
     if args.verbose:
-        print("%s vs %s: %d columns, symbol counts %s" % (names[0], names[1], obs.size, np.bincount(obs, minlength=3).tolist()))
+        print("%s: %d columns, symbol counts %s" % (" vs ".join(names), obs.size, np.bincount(obs, minlength=nsym).tolist()))
     return 0
 
 

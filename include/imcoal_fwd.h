@@ -32,7 +32,7 @@
  * freed, and no plan released, while somebody waits on it).  The O(L) host work of imc_obs_create* (validation,
  * dictionary training, encoding) runs outside the mutex; the device encoder (imc_set_device_encoding(1),
  * imc_obs_create_device) runs on the library's stream with the mutex held.  Device ingestion (imc_set_device_ingest(1),
- * imc_obs_create_pairwise) reads its file outside the mutex and holds it for its launches.
+ * imc_obs_create_pairwise, imc_aln_open_fasta) reads its file outside the mutex and holds it for its launches.
  *
  * Environment (diagnostics only, read when a plan is built / the context is created):
  *   IMC_DEBUG=1        print the planner's cost estimates to stderr
@@ -123,8 +123,43 @@ int imc_obs_create_pairwise(const char *seq1, const char *seq2, size_t L, imc_ob
 /* The last chunk creation of this process: out4 = {path, bytes sent to the device as file or sequence bytes, slabs,
  * columns}; path 0 = symbols made on the host (the host parser - also for a file the device parser declined - and the
  * imc_obs_create* calls that take symbols), 1 = text parsed on the device, 2 = cache unpacked on the device,
- * 3 = pairwise rule on the device.  For inspection and tests. */
+ * 3 = pairwise rule on the device, 4 = columns from a resident alignment (imc_obs_create_from_alignment: bytes 0,
+ * slabs 0).  For inspection and tests. */
 int imc_last_ingest(uint64_t *out4);
+
+/* Alignments resident on the device: the step in front of the symbols, scripts/prepare-alignments.py:66
+ * (SeqIO.to_dict) and its pairwise and triplet branches (lines 77-146). ------------------------------------- */
+typedef struct imc_aln imc_aln;   /* an alignment whose sequences are resident in HBM */
+/* Open a FASTA file ONCE: its bytes go up in slabs of at most IMC_INGEST_SLAB_BYTES through the two pinned staging
+ * buffers of device ingestion, the records are found and their line breaks squeezed out on the device
+ * (csrc/kernels_align.hpp), and every record's bases end up back to back in one device buffer; the names are taken on the
+ * host from the staged slab at the offsets the device reports.  No sequence exists on the host.  The result is what
+ * imc_read_fasta gives for the same file.  The device parser takes lines that end in "\n" or "\r\n", '>' at column 0
+ * followed by a name, sequence lines of the bytes 0x21-0x7e and empty lines anywhere; a slab may end in the middle of a
+ * sequence line but not of a header line.  It DECLINES anything else - other whitespace or control bytes in a sequence
+ * line, a lone '\r', whitespace in front of '>', a byte >= 0x80, an empty name, more than 4096 records, a repeated name,
+ * a header line longer than a slab - and so does anything that is not a regular file: the host reader then reads the
+ * file from its start and its sequences are uploaded, so every error is imc_read_fasta's.  A missing file is IMC_ERR_IO
+ * before the device is asked for; without a device the call is IMC_ERR_NODEVICE.  The file is read without the library's
+ * mutex; launches run on the library's stream with the mutex held.  Device memory: one buffer of the file's size (the
+ * bases' size for the host reader), kept as it is - it is NOT trimmed to the bases after the parse (headers and line
+ * breaks are under 2 % of a wrapped file) - plus, during the call, the two slabs and the tile tables. */
+int imc_aln_open_fasta(const char *path, imc_aln **out);
+int imc_aln_count(const imc_aln *aln);
+const char *imc_aln_name(const imc_aln *aln, int index);          /* owned by the alignment */
+size_t imc_aln_length(const imc_aln *aln, int index);
+int imc_aln_sequence(const imc_aln *aln, int index, char *out, size_t capacity);   /* copy back: inspection, tests */
+/* out4 = {parser: 0 host reader (declined or not a regular file), 1 device; file bytes sent; slabs; records} */
+int imc_aln_info(const imc_aln *aln, uint64_t *out4);
+int imc_aln_free(imc_aln *aln);                                    /* NULL is fine */
+/* k = 2: pairwise rule, nsym 3; k = 3: triplet rule, nsym 65.  members[] index the alignment's records (a record may
+ * occur twice).  The chunk is the one imc_obs_create builds from imc_encode_pairwise / imc_encode_triplet on the same
+ * sequences: same symbols, dictionary, token streams and results, bit for bit; it keeps no reference to the alignment.
+ * The symbols are made by a column kernel from the resident bases - no upload - and the chunk is built from them as
+ * imc_obs_create_device builds one: encoded on the device, trained where imc_set_device_training says.  IMC_ERR_ARG -
+ * before any HIP call - for null pointers, k outside {2, 3}, a member out of range, members of different lengths (the
+ * message names both records and their lengths) and L >= 2^31. */
+int imc_obs_create_from_alignment(const imc_aln *aln, const int *members, int k, imc_obs **out);
 /* A chunk from symbols that are already in device memory (a simulated replicate, the output of another stage): d_sym
  * points to L symbols of sym_bytes = 1 (uint8), 2 (16-bit) or 4 (int32) bytes each on the library's device.  The call
  * synchronises hip_stream (a hipStream_t; NULL is the default stream), copies the symbols into a buffer of its own on
@@ -179,6 +214,15 @@ int imc_write_cache(const char *path, const uint8_t *sym, size_t L, int nsym);
 /* The pairwise symbol rule of scripts/prepare-alignments.py:99-105 on two aligned sequences:
  * 2 = either base not in ACGT (case-insensitive), 0 = equal, 1 = different. */
 int imc_encode_pairwise(const char *seq1, const char *seq2, size_t L, uint8_t *sym_out);
+/* Record `index` of a FASTA file read on the host (csrc/fasta_io.hpp, the C++ statement of prepare.read_fasta for ASCII
+ * files): *count = records; name and sequence are copied when the pointers are non-null and the capacities suffice (name
+ * NUL-terminated); *length = its bases.  Call with null buffers to size them.  IMC_ERR_IO for a file that cannot be
+ * opened, a header without a name and a byte >= 0x80. */
+int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity,
+                   char *seq_out, size_t seq_capacity, size_t *length, int *count);
+/* The triplet rule of scripts/prepare-alignments.py:134-146: i1 + 4*i2 + 16*i3 with A,C,G,T -> 0..3 (either case),
+ * 64 when any of the three bases is not in ACGT.  nsym = 65. */
+int imc_encode_triplet(const char *seq1, const char *seq2, const char *seq3, size_t L, uint8_t *sym_out);
 
 /* Forward log-likelihood: replaces Forwarder.forward -> ziphmm.zip_forward,
  * src/IMCoalHMM/hmm.py:19-21, and the sum over forwarders at likelihood.py:33.
