@@ -152,6 +152,7 @@ struct Ctx {
     int fuse_tail = 1;        // the chunk's last workgroup finishes the chunk (zip3_tail) instead of k_chain launches: 1 = where a chunk is
                               // at most four workgroups (one in-wavefront fold; measured: 100 x 1e6 columns -1.5 us, and +6 us at 13
                               // workgroups of 20 states, where the chain's twenty parallel wavefronts win), 2 = wherever possible, 0 = never (IMC_FUSE_TAIL)
+    bool chain_lds = false;   // IMC_CHAIN_LDS=1: k_chain's step hands its vector round through LDS, not lane to lane (A/B measurements)
     bool fuse_head = true;    // IMC_FUSE_HEAD=0: k_stage_params + k_z4_raw as launches of their own (A/B measurements)
     bool pack_table = true;   // IMC_PACK_TABLE=0: the mat-vec chain reads the padded table (A/B measurements)
     int device_encode = -1;   // token streams of new / recompressed chunks: 0 = encoded on the host (imc::encode_levels), 1 = on the
@@ -220,6 +221,7 @@ int ensure_ctx()
     if (const char *tt = std::getenv("IMC_TABLE_TRIPLES")) g.table_triples = std::atoi(tt) != 0 ? 1 : 0;
     if (const char *ft = std::getenv("IMC_FUSE_TAIL")) g.fuse_tail = std::max(0, std::min(2, std::atoi(ft)));
     if (const char *xa = std::getenv("IMC_XCD_AFFINE")) g.xcd_affine = std::atoi(xa) != 0;
+    if (const char *cl = std::getenv("IMC_CHAIN_LDS")) g.chain_lds = std::atoi(cl) != 0;
     if (const char *wb = std::getenv("IMC_WIDE_BLOCKED")) { const int v = std::atoi(wb); if (v >= -1 && v <= 1) g.wide_blocked = v; }
     if (g.device_encode < 0) {
         const char *de = std::getenv("IMC_DEVICE_ENCODE");
@@ -1715,13 +1717,14 @@ int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
 
 // ---- kernel table ---------------------------------------------------------------------------------
 
-using ChainFn = void (*)(const ChainDesc *, int, const uint32_t *, uint32_t, uint32_t, const double *, const int *,
+using ChainFn = void (*)(const ChainDesc *, int, uint32_t, uint32_t, const double *, const int *,
                          const int *, uint32_t, double *, int *, double *, int);
 
 struct KernelChoice : imc::KernelFacts {   // the planner's facts of the entry (planner_host.hpp) + the kernels themselves
     void (*plain)(PropArgs) = nullptr;
     void (*zip)(PropArgs) = nullptr;
     ChainFn chain = nullptr;
+    ChainFn chain_lds = nullptr;       // the same kernel with the step's vector handed round through LDS (IMC_CHAIN_LDS=1)
     void (*big_table_raw)(BigArgs) = nullptr;
     void (*big_table_level)(BigArgs, const uint16_t *, int) = nullptr;
     void (*big_prop)(BigArgs, const BigBlock *) = nullptr;
@@ -1763,7 +1766,9 @@ KernelChoice make_kc()
     k.plain = k_propagate<R, G, MW>;
     k.zip = k_zpropagate<R, G>;
     k.zip_lds = &ZipGeom<R, G>::lds_bytes;
-    k.chain = k_chain<NP, (NP <= 12 ? 6 : NP <= 24 ? 4 : NP <= 32 ? 3 : NP <= 64 ? 2 : 1)>;
+    constexpr int CHAIN_D = NP <= 12 ? 6 : NP <= 24 ? 4 : NP <= 32 ? 3 : NP <= 64 ? 2 : 1;
+    k.chain = k_chain<NP, CHAIN_D, CHAIN_STEP>;
+    k.chain_lds = k_chain<NP, CHAIN_D, CHAIN_LDS>;
     k.chain_self_emax = true;          // (k_chain<NP, D > 0>: one wavefront, prefetch ring)
     if constexpr (NP % 4 == 0 && NP <= 24) {
         k.zip2 = k_zpropagate2<NP / 4>;
@@ -1811,7 +1816,7 @@ KernelChoice make_big()
     KernelChoice k;
     k.G = NT; k.NP = 16 * NT;          // NT wavefronts per workgroup
     k.z4_waves = Z2WAVES;
-    k.chain = k_chain<16 * NT, 0>;
+    k.chain = k.chain_lds = k_chain<16 * NT, 0>;
     k.big_table_raw = k_big_table_raw<NT>;
     k.big_table_level = k_big_table_level<NT>;
     k.big_prop = k_big_propagate<NT, NSLAB>;
@@ -2184,7 +2189,8 @@ struct PlanBuilder {
             // a level whose chunks all hold one first-vector is final; level 0 operators always need one pass
             if (kmax <= 1 && hl.size() > 1) break;
             if (kmax == 0) break;
-            // ~3 levels: per level a chain costs g serial steps (~0.3 us each) plus two launches (~6 us)
+            // ~3 levels: per level a chain costs g serial steps (0.38 us each at 20 states, profiles/mb_chain_step.txt) plus
+            // one launch (~3 us up to its second step)
             const uint32_t gsz = kmax <= 16 ? kmax : std::max<uint32_t>(12, (uint32_t)std::ceil(std::cbrt((double)kmax)));
             p->chain_steps += gsz;
             HostLevel nx;
@@ -2199,7 +2205,11 @@ struct PlanBuilder {
                     nx.vec0.push_back(nx.n_vecs);
                     nx.first.push_back(fst);
                     const int nvv = fst ? 1 : N;
-                    for (int c = 0; c < nvv; ++c) nx.chains.push_back(ChainDesc{rb, re, (uint32_t)c, nx.n_vecs + c, fst ? 1u : 0u, 0u});
+                    // the start vector and the first operator's vectors: known here, so no chain looks them up on the device
+                    const uint32_t op0 = rb + (fst ? 1u : 0u);
+                    const uint32_t vec_first = fst ? cur.vec0[rb] : 0u, vbase = op0 < re ? cur.vec0[op0] : 0u;
+                    for (int c = 0; c < nvv; ++c)
+                        nx.chains.push_back(ChainDesc{rb, re, (uint32_t)c, nx.n_vecs + c, fst ? 1u : 0u, 0u, vec_first, vbase});
                     nx.n_vecs += nvv;
                 }
             }
@@ -2823,8 +2833,8 @@ int Launch::stitch() const
         }
         const int threads = (int)round_up((size_t)NP, 64);
         const bool last_level = l + 2 == p->levels.size();
-        hipLaunchKernelGGL(kc->chain, dim3(ot.n_chains, (unsigned)B), dim3(threads), 0, stream,
-                           ot.d_chains.get(), N, in.d_vec0.get(), in.n_segs, in.n_vecs, in.d_P.get(), in.d_EX.get(), in.d_EMAX.get(),
+        hipLaunchKernelGGL(g.chain_lds ? kc->chain_lds : kc->chain, dim3(ot.n_chains, (unsigned)B), dim3(threads), 0, stream,
+                           ot.d_chains.get(), N, in.n_segs, in.n_vecs, in.d_P.get(), in.d_EX.get(), in.d_EMAX.get(),
                            ot.n_vecs, ot.d_P.get(), ot.d_EX.get(), (last_level && p->finish_fused) ? out : (double *)nullptr, p->n_chunks);
         HIP_TRY(hipGetLastError());
     }

@@ -9,6 +9,7 @@
 // serial depth drops from K steps to ~2 sqrt(K).  k_finish turns the last vectors into log-likelihoods.
 #pragma once
 #include "kernels_plain.hpp"
+#include <utility>
 
 struct ChainDesc {
     uint32_t seg_begin, seg_end;   // input segments [begin, end) of the previous level
@@ -16,7 +17,54 @@ struct ChainDesc {
     uint32_t out_vec;              // output vector index in the next level
     uint32_t first;                // 1: the run starts with its chunk's first segment (a vector)
     uint32_t chunk1;               // last level only: 1 + the chunk whose final vector this chain produces (0: none)
+    uint32_t vec_first;            // first == 1: that vector's index in the previous level
+    uint32_t vbase;                // first vector of the run's first operator (operator t starts at vbase + t*N); 0: no operator
 };
+
+// How a step of k_chain<NP, D > 0> hands the rescaled vector (entry m in lane m) to every lane.
+//   CHAIN_LDS   through LDS: one write, a fence, NP/2 broadcast 16-byte reads
+//   CHAIN_LANE  two v_readlane_b32 per entry into a scalar pair
+//   CHAIN_DPP   rows made whole-wave copies by the gfx950 lane swaps, then one v_mov_b64_dpp row_newbcast per entry
+// All three apply the same operations to the same operands in the same order: the results are the same bits.
+enum ChainForm { CHAIN_LDS = 0, CHAIN_LANE = 1, CHAIN_DPP = 2 };
+// the library's form: the fastest in profiles/mb_chain_step.txt (CHAIN_LDS stays behind IMC_CHAIN_LDS=1)
+static constexpr int CHAIN_STEP = CHAIN_DPP;
+
+template <int... M, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, M...>, F &&f) { (f(std::integral_constant<int, M>()), ...); }
+
+// x of lane M in every lane
+template <int M>
+__device__ __forceinline__ double lane_bcast_f64(double x)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), M), hi = __builtin_amdgcn_readlane(__double2hiint(x), M);
+    return __hiloint2double(hi, lo);
+}
+
+// rows[r] = the 16-lane row r of x in all four rows (NP <= 16 * NR; rows beyond NR are not produced).  v_permlane32_swap
+// exchanges the upper half of its first operand with the lower half of its second, v_permlane16_swap the odd rows of the
+// first with the even rows of the second; applied to two copies of x they leave one copy of each half / row in both.
+template <int NR>
+__device__ __forceinline__ void rows_to_all(double x, double (&rows)[NR])
+{
+    static_assert(NR >= 1 && NR <= 4, "a wavefront has four rows");
+    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+    if constexpr (NR == 1) {
+        rows[0] = x;
+    } else if constexpr (NR == 2) {
+        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        rows[0] = __hiloint2double((int)h[0], (int)l[0]);
+        rows[1] = __hiloint2double((int)h[1], (int)l[1]);
+    } else {
+        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        const auto l0 = __builtin_amdgcn_permlane16_swap(l[0], l[0], false, false), h0 = __builtin_amdgcn_permlane16_swap(h[0], h[0], false, false);
+        const auto l1 = __builtin_amdgcn_permlane16_swap(l[1], l[1], false, false), h1 = __builtin_amdgcn_permlane16_swap(h[1], h[1], false, false);
+        rows[0] = __hiloint2double((int)h0[0], (int)l0[0]);
+        rows[1] = __hiloint2double((int)h0[1], (int)l0[1]);
+        rows[2] = __hiloint2double((int)h1[0], (int)l1[0]);
+        if constexpr (NR == 4) rows[3] = __hiloint2double((int)h1[1], (int)l1[1]);
+    }
+}
 
 // EMAX[b][seg] = max_c EX[b][vec0(seg)+c]
 __global__ void k_emax(const uint32_t *seg_vec0, const uint8_t *seg_first, uint32_t n_segs, uint32_t n_vecs, int N,
@@ -37,13 +85,17 @@ __global__ void k_emax(const uint32_t *seg_vec0, const uint8_t *seg_first, uint3
 // The operators of a run are consecutive N-vector blocks, so their addresses are known up front: the
 // rows and exponents of the next D operators are kept in flight in a register ring (D-deep prefetch),
 // which takes the L2/HBM latency (~0.7 us) off the serial chain.  With D > 0 (one wavefront, NP <= 64) the
-// kernel also finds each unit's largest exponent itself and EMin is not read.
-template <int NP, int D>
+// kernel also finds each unit's largest exponent itself and EMin is not read; FORM says how a step's rescaled vector
+// reaches every lane (D == 0 always goes through LDS).  Everything a chain needs before its first operand fetch is in
+// its descriptor: one load, then the ring's first D fetches.
+template <int NP, int D, int FORM = CHAIN_LDS>
 __global__ __launch_bounds__(((NP + 63) / 64) * 64) void k_chain(
     const ChainDesc *chains, int N,
-    const uint32_t *in_vec0, uint32_t in_n_segs, uint32_t in_n_vecs, const double *Pin, const int *EXin, const int *EMin,
+    uint32_t in_n_segs, uint32_t in_n_vecs, const double *Pin, const int *EXin, const int *EMin,
     uint32_t out_n_vecs, double *Pout, int *EXout, double *fin_out, int n_chunks)
 {
+    static_assert(FORM == CHAIN_LDS || (D > 0 && NP <= 64), "the register forms are for one wavefront");
+    constexpr int NR = (NP + 15) / 16;   // 16-lane rows that hold entries of the vector
     __shared__ __attribute__((aligned(16))) double w[2][NP];
     // a single-wavefront workgroup needs no s_barrier (LDS is in-order within a wavefront), and a
     // __syncthreads() would drain the prefetch loads with its vmcnt(0)
@@ -61,7 +113,7 @@ __global__ __launch_bounds__(((NP + 63) / 64) * 64) void k_chain(
     int etot;
     uint32_t k0 = cd.seg_begin;
     if (cd.first) {
-        const uint32_t v = in_vec0[k0];
+        const uint32_t v = cd.vec_first;
         a = mine ? Pb[(size_t)v * NP + i] : 0.0;
         etot = EXb[v];
         ++k0;
@@ -71,7 +123,7 @@ __global__ __launch_bounds__(((NP + 63) / 64) * 64) void k_chain(
     }
     const int nsteps = (int)cd.seg_end - (int)k0;
     // operator k0+t starts at vector vbase + t*N (every segment after a chunk's first is an operator)
-    const uint32_t vbase = nsteps > 0 ? in_vec0[k0] : 0u;
+    const uint32_t vbase = cd.vbase;
 
     if constexpr (D == 0) {
         // large NP: no register ring (it would not fit); stream the operator row straight from L2
@@ -103,7 +155,7 @@ __global__ __launch_bounds__(((NP + 63) / 64) * 64) void k_chain(
         }
     } else {
     double2 pk[D > 0 ? D : 1][NP / 2];
-    int exr[D > 0 ? D : 1];
+    int exr[D > 0 ? D : 1] = {};
     auto fetch = [&](int t, int slot) {   // slot is a compile-time constant at every call site
         const size_t v0 = (size_t)vbase + (size_t)t * N;
         // Loads only, D steps ahead of their use.  (Round 2 reduced the exponents to their maximum right here: that
@@ -117,48 +169,97 @@ __global__ __launch_bounds__(((NP + 63) / 64) * 64) void k_chain(
 #pragma unroll
     for (int s = 0; s < D; ++s)
         if (s < nsteps) fetch(s, s);   // (D > 0 here)
+    // The unit's largest column exponent is found here instead of by a k_emax launch per level (seven DPP moves).  It
+    // and the shift exr - em depend on prefetched integers only, so those of step t + 1 are taken while the FMAs of
+    // step t run, not between two steps of the dependent chain.
+    int em = 0, sh = 0;
+    if (nsteps > 0) {
+        em = wave_max_i32_dpp(exr[0]);
+        sh = exr[0] - em;
+    }
     int buf = 0;
     for (int t0 = 0; t0 < nsteps; t0 += D) {
 #pragma unroll
         for (int s = 0; s < D; ++s) {
             const int t = t0 + s;
             if (t < nsteps) {   // wave-uniform
-                // the unit's largest column exponent, found here instead of by a k_emax launch per level: seven DPP moves
-                const int em = wave_max_i32_dpp(exr[s]);
-                if (mine) w[buf][i] = ldexp(a, exr[s] - em);
-                else if (i < NP) w[buf][i] = 0.0;
+                const double wi = mine ? ldexp(a, sh) : 0.0;   // entry i of the rescaled vector
+                const int em_t = em;
                 double2 cur[NP / 2];
 #pragma unroll
                 for (int m = 0; m < NP / 2; ++m) cur[m] = pk[s][m];
                 if (t + D < nsteps) fetch(t + D, s);
-                sync();
+                // (slot s + 1 was fetched D - 1 steps ago; at s = D - 1 slot 0 holds step t0 + D by now.  No branch, so that
+                // the scheduler may put this among the FMAs: beyond the last step the slot is stale and the result unused.)
+                em = wave_max_i32_dpp(exr[(s + 1) % D]);
+                sh = exr[(s + 1) % D] - em;
+                // acc0 / s0 take the even columns in order, acc1 / s1 the odd ones, whatever the form
                 double acc0 = 0.0, acc1 = 0.0, s0 = 0.0, s1 = 0.0;
-                const double2 *wv = reinterpret_cast<const double2 *>(&w[buf][0]);
+                auto column = [&](auto M, double wm) {
+                    constexpr int m = decltype(M)::value;
+                    if constexpr (m & 1) {
+                        acc1 = fma(cur[m / 2].y, wm, acc1);
+                        s1 += wm;
+                    } else {
+                        acc0 = fma(cur[m / 2].x, wm, acc0);
+                        s0 += wm;
+                    }
+                };
+                if constexpr (FORM == CHAIN_LDS) {
+                    if (i < NP) w[buf][i] = wi;
+                    sync();
+                    const double2 *wv = reinterpret_cast<const double2 *>(&w[buf][0]);
 #pragma unroll
-                for (int m = 0; m < NP / 2; ++m) {
-                    const double2 wc = wv[m];
-                    acc0 = fma(cur[m].x, wc.x, acc0);
-                    acc1 = fma(cur[m].y, wc.y, acc1);
-                    s0 += wc.x;
-                    s1 += wc.y;
+                    for (int m = 0; m < NP / 2; ++m) {
+                        const double2 wc = wv[m];
+                        acc0 = fma(cur[m].x, wc.x, acc0);
+                        acc1 = fma(cur[m].y, wc.y, acc1);
+                        s0 += wc.x;
+                        s1 += wc.y;
+                    }
+                    buf ^= 1;   // the next step writes the other buffer: one fence per step suffices
+                } else if constexpr (FORM == CHAIN_LANE) {
+                    static_for(std::make_integer_sequence<int, NP>(), [&](auto M) { column(M, lane_bcast_f64<decltype(M)::value>(wi)); });
+                } else {
+                    double rows[NR];
+                    rows_to_all<NR>(wi, rows);
+                    static_for(std::make_integer_sequence<int, NP>(), [&](auto M) {
+                        constexpr int m = decltype(M)::value;
+                        column(M, __builtin_amdgcn_update_dpp(0.0, rows[m / 16], 0x150 + m % 16, 0xf, 0xf, true));   // row_newbcast:m%16
+                    });
                 }
                 const double sm = s0 + s1;
                 int e = 0;
                 (void)frexp(sm, &e);
                 e = (sm > 0.0 && sm < INFINITY) ? e : 0;
-                a = mine ? ldexp(acc0 + acc1, -e) : 0.0;
-                etot += em + e;
-                buf ^= 1;   // the next step writes the other buffer: one fence per step suffices
+                // (lanes beyond N carry what row 0 gives them: every use of a below selects or stores by `mine`)
+                a = ldexp(acc0 + acc1, -e);
+                etot += em_t + e;
             }
         }
     }
     }
     // normalise the result by its total and store it as a segment of the next level
-    sync();
-    if (i < NP) w[0][i] = mine ? a : 0.0;
-    sync();
-    double tot = 0.0;
-    for (int c = 0; c < N; ++c) tot += w[0][c];
+    double tot = 0.0;   // entries 0 .. N-1, left to right
+    if constexpr (FORM == CHAIN_LDS) {
+        sync();
+        if (i < NP) w[0][i] = mine ? a : 0.0;
+        sync();
+        for (int c = 0; c < N; ++c) tot += w[0][c];
+    } else if constexpr (FORM == CHAIN_LANE) {
+        static_for(std::make_integer_sequence<int, NP>(), [&](auto M) {
+            const double am = lane_bcast_f64<decltype(M)::value>(a);
+            tot = decltype(M)::value < N ? tot + am : tot;
+        });
+    } else {
+        double rows[NR];
+        rows_to_all<NR>(a, rows);
+        static_for(std::make_integer_sequence<int, NP>(), [&](auto M) {
+            constexpr int m = decltype(M)::value;
+            const double am = __builtin_amdgcn_update_dpp(0.0, rows[m / 16], 0x150 + m % 16, 0xf, 0xf, true);
+            tot = m < N ? tot + am : tot;
+        });
+    }
     int e = 0;
     (void)frexp(tot, &e);
     e = (tot > 0.0 && tot < INFINITY) ? e : 0;
