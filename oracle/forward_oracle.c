@@ -135,6 +135,199 @@ double orc_forward_scaled_ld(int N, int S, const double *pi, const double *T, co
     return (double)(sum + comp);
 }
 
+/* ------------------------------------------------------------------------------------------
+ * (1b) States instead of scalars: what imc_forward_state exports (include/imcoal_fwd.h), by the definition.
+ *
+ * Operator: for every basis index c, x = e_c, then x <- diag(E[:,o_t]) T' x over ALL L columns (the first column acts
+ * as an operator too); x is rescaled to sum 1 after every column and the logs of the rescales are accumulated
+ * (Neumaier).  shape[i*N + c] = x_i / sum_i x_i and logmass[c] = log sum_i x_i of the unscaled column, both rounded
+ * once to double.  A column whose mass becomes 0 gets shape 0 and logmass -inf; NaN in -> NaN out.
+ * Vector: the same recursion from x = pi .* E[:,o_0], columns 1 .. L-1 applied.
+ *
+ * Written twice, statement for statement: in long double (the reference) and in double (the "fp64 flag", which
+ * measures what rounding in fp64 alone does to a state).  Observations are 8-bit, or 16-bit for alphabets beyond 256
+ * symbols (as orc_forward_scaled_u16): the bodies take both pointers and read the one that is not NULL.  The
+ * operator is parallel over c.
+ * ------------------------------------------------------------------------------------------ */
+static int orc_obs_at(const uint8_t *obs8, const uint16_t *obs16, size_t t) { return obs16 ? obs16[t] : obs8[t]; }
+
+/* One column: b = diag(E[:,o]) T' a and its mass c = sum b, which is returned.  When c > 0, a = b / c and log c is
+ * added to the compensated accumulator (sum, comp); otherwise a and the accumulator are left as they were. */
+static long double orc_state_step_ld(int N, int S, const double *T, const double *E, int o, long double *a,
+                                     long double *b, long double *sum, long double *comp)
+{
+    for (int j = 0; j < N; ++j) b[j] = 0.0L;
+    for (int i = 0; i < N; ++i) {
+        const long double ai = a[i];
+        const double *Ti = T + (size_t)i * N;
+        for (int j = 0; j < N; ++j) b[j] += (long double)Ti[j] * ai;
+    }
+    long double c = 0.0L;
+    for (int j = 0; j < N; ++j) { b[j] *= E[(size_t)j * S + o]; c += b[j]; }
+    if (!(c > 0.0L)) return c;
+    for (int j = 0; j < N; ++j) a[j] = b[j] / c;
+    const long double x = logl(c);
+    const long double t2 = *sum + x;
+    if (fabsl(*sum) >= fabsl(x)) *comp += (*sum - t2) + x; else *comp += (x - t2) + *sum;
+    *sum = t2;
+    return c;
+}
+
+static void orc_operator_body_ld(int N, int S, const double *T, const double *E, const uint8_t *obs8,
+                                 const uint16_t *obs16, size_t L, double *shape, double *logmass)
+{
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+    for (int col = 0; col < N; ++col) {
+        long double *a = (long double *)malloc(sizeof(long double) * 2 * (size_t)N);
+        long double *b = a + N;
+        long double sum = 0.0L, comp = 0.0L, c = 1.0L;
+        for (int j = 0; j < N; ++j) a[j] = j == col ? 1.0L : 0.0L;
+        for (size_t t = 0; t < L; ++t) {
+            c = orc_state_step_ld(N, S, T, E, orc_obs_at(obs8, obs16, t), a, b, &sum, &comp);
+            if (!(c > 0.0L)) break;
+        }
+        const int dead = !(c > 0.0L);
+        for (int i = 0; i < N; ++i) shape[(size_t)i * N + col] = dead ? (c == 0.0L ? 0.0 : NAN) : (double)a[i];
+        logmass[col] = dead ? (c == 0.0L ? -INFINITY : NAN) : (double)(sum + comp);
+        free(a);
+    }
+}
+
+static void orc_vector_body_ld(int N, int S, const double *pi, const double *T, const double *E, const uint8_t *obs8,
+                               const uint16_t *obs16, size_t L, double *shape, double *logmass)
+{
+    long double *a = (long double *)malloc(sizeof(long double) * 2 * (size_t)N);
+    long double *b = a + N;
+    long double sum = 0.0L, comp = 0.0L, c = 0.0L;
+    if (L > 0) {
+        const int o0 = orc_obs_at(obs8, obs16, 0);
+        for (int j = 0; j < N; ++j) { a[j] = (long double)pi[j] * E[(size_t)j * S + o0]; c += a[j]; }
+    }
+    if (c > 0.0L) {
+        for (int j = 0; j < N; ++j) a[j] /= c;
+        sum = logl(c);
+        for (size_t t = 1; t < L; ++t) {
+            c = orc_state_step_ld(N, S, T, E, orc_obs_at(obs8, obs16, t), a, b, &sum, &comp);
+            if (!(c > 0.0L)) break;
+        }
+    }
+    const int dead = !(c > 0.0L);
+    for (int i = 0; i < N; ++i) shape[i] = dead ? (c == 0.0L ? 0.0 : NAN) : (double)a[i];
+    *logmass = dead ? (c == 0.0L ? -INFINITY : NAN) : (double)(sum + comp);
+    free(a);
+}
+
+/* The fp64 variant: the three functions above with `double` for `long double`, log for logl, fabs for fabsl. */
+static double orc_state_step_f64(int N, int S, const double *T, const double *E, int o, double *a, double *b,
+                                 double *sum, double *comp)
+{
+    for (int j = 0; j < N; ++j) b[j] = 0.0;
+    for (int i = 0; i < N; ++i) {
+        const double ai = a[i];
+        const double *Ti = T + (size_t)i * N;
+        for (int j = 0; j < N; ++j) b[j] += Ti[j] * ai;
+    }
+    double c = 0.0;
+    for (int j = 0; j < N; ++j) { b[j] *= E[(size_t)j * S + o]; c += b[j]; }
+    if (!(c > 0.0)) return c;
+    for (int j = 0; j < N; ++j) a[j] = b[j] / c;
+    const double x = log(c);
+    const double t2 = *sum + x;
+    if (fabs(*sum) >= fabs(x)) *comp += (*sum - t2) + x; else *comp += (x - t2) + *sum;
+    *sum = t2;
+    return c;
+}
+
+static void orc_operator_body_f64(int N, int S, const double *T, const double *E, const uint8_t *obs8,
+                                  const uint16_t *obs16, size_t L, double *shape, double *logmass)
+{
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 1)
+#endif
+    for (int col = 0; col < N; ++col) {
+        double *a = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+        double *b = a + N;
+        double sum = 0.0, comp = 0.0, c = 1.0;
+        for (int j = 0; j < N; ++j) a[j] = j == col ? 1.0 : 0.0;
+        for (size_t t = 0; t < L; ++t) {
+            c = orc_state_step_f64(N, S, T, E, orc_obs_at(obs8, obs16, t), a, b, &sum, &comp);
+            if (!(c > 0.0)) break;
+        }
+        const int dead = !(c > 0.0);
+        for (int i = 0; i < N; ++i) shape[(size_t)i * N + col] = dead ? (c == 0.0 ? 0.0 : NAN) : a[i];
+        logmass[col] = dead ? (c == 0.0 ? -INFINITY : NAN) : sum + comp;
+        free(a);
+    }
+}
+
+static void orc_vector_body_f64(int N, int S, const double *pi, const double *T, const double *E, const uint8_t *obs8,
+                                const uint16_t *obs16, size_t L, double *shape, double *logmass)
+{
+    double *a = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    double *b = a + N;
+    double sum = 0.0, comp = 0.0, c = 0.0;
+    if (L > 0) {
+        const int o0 = orc_obs_at(obs8, obs16, 0);
+        for (int j = 0; j < N; ++j) { a[j] = pi[j] * E[(size_t)j * S + o0]; c += a[j]; }
+    }
+    if (c > 0.0) {
+        for (int j = 0; j < N; ++j) a[j] /= c;
+        sum = log(c);
+        for (size_t t = 1; t < L; ++t) {
+            c = orc_state_step_f64(N, S, T, E, orc_obs_at(obs8, obs16, t), a, b, &sum, &comp);
+            if (!(c > 0.0)) break;
+        }
+    }
+    const int dead = !(c > 0.0);
+    for (int i = 0; i < N; ++i) shape[i] = dead ? (c == 0.0 ? 0.0 : NAN) : a[i];
+    *logmass = dead ? (c == 0.0 ? -INFINITY : NAN) : sum + comp;
+    free(a);
+}
+
+/* The entry points: long double or fp64, 8- or 16-bit observations. */
+void orc_operator_ld(int N, int S, const double *T, const double *E, const uint8_t *obs, size_t L, double *shape,
+                     double *logmass)
+{
+    orc_operator_body_ld(N, S, T, E, obs, NULL, L, shape, logmass);
+}
+void orc_operator_ld_u16(int N, int S, const double *T, const double *E, const uint16_t *obs, size_t L, double *shape,
+                         double *logmass)
+{
+    orc_operator_body_ld(N, S, T, E, NULL, obs, L, shape, logmass);
+}
+void orc_operator_f64(int N, int S, const double *T, const double *E, const uint8_t *obs, size_t L, double *shape,
+                      double *logmass)
+{
+    orc_operator_body_f64(N, S, T, E, obs, NULL, L, shape, logmass);
+}
+void orc_operator_f64_u16(int N, int S, const double *T, const double *E, const uint16_t *obs, size_t L, double *shape,
+                          double *logmass)
+{
+    orc_operator_body_f64(N, S, T, E, NULL, obs, L, shape, logmass);
+}
+void orc_vector_ld(int N, int S, const double *pi, const double *T, const double *E, const uint8_t *obs, size_t L,
+                   double *shape, double *logmass)
+{
+    orc_vector_body_ld(N, S, pi, T, E, obs, NULL, L, shape, logmass);
+}
+void orc_vector_ld_u16(int N, int S, const double *pi, const double *T, const double *E, const uint16_t *obs, size_t L,
+                       double *shape, double *logmass)
+{
+    orc_vector_body_ld(N, S, pi, T, E, NULL, obs, L, shape, logmass);
+}
+void orc_vector_f64(int N, int S, const double *pi, const double *T, const double *E, const uint8_t *obs, size_t L,
+                    double *shape, double *logmass)
+{
+    orc_vector_body_f64(N, S, pi, T, E, obs, NULL, L, shape, logmass);
+}
+void orc_vector_f64_u16(int N, int S, const double *pi, const double *T, const double *E, const uint16_t *obs, size_t L,
+                        double *shape, double *logmass)
+{
+    orc_vector_body_f64(N, S, pi, T, E, NULL, obs, L, shape, logmass);
+}
+
 /* Sum over independent chunks, each restarted from pi (likelihood.py:33), left-to-right. */
 double orc_forward_chunks(int N, int S, const double *pi, const double *T, const double *E,
                           const uint8_t *const *obs, const size_t *L, int n_chunks)

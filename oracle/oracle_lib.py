@@ -33,6 +33,14 @@ def lib():
         L.orc_forward_scaled_u16.restype = ctypes.c_double
         L.orc_forward_scaled_u16.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint16),
                                              ctypes.c_size_t]
+        for kind in ("ld", "f64"):
+            for suffix, obs_p in (("", _u8p), ("_u16", ctypes.POINTER(ctypes.c_uint16))):
+                f = getattr(L, "orc_operator_%s%s" % (kind, suffix))
+                f.restype = None
+                f.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, obs_p, ctypes.c_size_t, _dp, _dp]
+                f = getattr(L, "orc_vector_%s%s" % (kind, suffix))
+                f.restype = None
+                f.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, obs_p, ctypes.c_size_t, _dp, _dp]
         L.orc_zip_preprocess.restype = ctypes.c_void_p
         L.orc_zip_preprocess.argtypes = [_u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_long, ctypes.c_int]
         L.orc_zip_length.restype = ctypes.c_size_t
@@ -84,6 +92,48 @@ def forward_scaled(pi, T, E, obs):
 def forward_scaled_ld(pi, T, E, obs):
     pi, T, E, obs, N, S = _prep(pi, T, E, obs)
     return lib().orc_forward_scaled_ld(N, S, _p(pi), _p(T), _p(E), obs.ctypes.data_as(_u8p), obs.size)
+
+
+def _state_args(T, E, obs):
+    """(T, E, obs, obs pointer, name suffix): 8-bit observations, 16-bit ones for alphabets beyond 256 symbols."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    N, S = E.shape
+    assert T.shape == (N, N)
+    obs = np.asarray(obs)
+    assert obs.size == 0 or (int(obs.min()) >= 0 and int(obs.max()) < S)
+    if S > 256:
+        obs = np.ascontiguousarray(obs, dtype=np.uint16)
+        return T, E, obs, obs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), "_u16"
+    obs = np.ascontiguousarray(obs, dtype=np.uint8)
+    return T, E, obs, obs.ctypes.data_as(_u8p), ""
+
+
+def operator_ld(T, E, obs, fp64=False):
+    """Transfer operator of all columns of `obs`, by the definition in long double: ``(shape[N, N], logmass[N])`` with
+    column c of the operator = ``shape[:, c] * exp(logmass[c])`` and every column of ``shape`` summing to 1.
+    ``fp64=True``: the same statements in double."""
+    T, E, obs, optr, suffix = _state_args(T, E, obs)
+    N, S = E.shape
+    shape = np.zeros((N, N), dtype=np.float64)
+    logmass = np.zeros(N, dtype=np.float64)
+    getattr(lib(), "orc_operator_%s%s" % ("f64" if fp64 else "ld", suffix))(N, S, _p(T), _p(E), optr, obs.size, _p(shape),
+                                                                           _p(logmass))
+    return shape, logmass
+
+
+def vector_ld(pi, T, E, obs, fp64=False):
+    """Forward vector after `obs`, started from pi, in long double: ``(shape[N], logmass)`` with the vector =
+    ``shape * exp(logmass)`` and ``shape`` summing to 1.  ``fp64=True``: the same statements in double."""
+    T, E, obs, optr, suffix = _state_args(T, E, obs)
+    N, S = E.shape
+    pi = np.ascontiguousarray(pi, dtype=np.float64).reshape(-1)
+    assert pi.shape == (N,)
+    shape = np.zeros(N, dtype=np.float64)
+    logmass = np.zeros(1, dtype=np.float64)
+    getattr(lib(), "orc_vector_%s%s" % ("f64" if fp64 else "ld", suffix))(N, S, _p(pi), _p(T), _p(E), optr, obs.size,
+                                                                         _p(shape), _p(logmass))
+    return shape, float(logmass[0])
 
 
 class Zip:
