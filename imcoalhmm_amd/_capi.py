@@ -107,6 +107,14 @@ SIGNATURES = [
      [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _dp, _dp, _dp, _dp,
       _dp, _dp]),
     ("imc_model_expm_batch_device", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    # include/imcoal_sample.h (alignments drawn from an HMM: csrc/sample_tiles.hpp, csrc/kernels_sample.hpp)
+    ("imc_sample_host", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    ("imc_sample_device", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    ("imc_last_sampling", ctypes.c_int, [_u64p]),
 ]
 
 _lib = None

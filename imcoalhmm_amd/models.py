@@ -601,6 +601,20 @@ class Model(object):
         Es = np.stack([emission_matrix(self.emission_points(*t)) for t in thetas])
         return pis, Ts, Es
 
+    def simulate(self, parameters, length, seed, replicates=1, missing=None):
+        """``replicates`` alignments of ``length`` columns drawn from the model's HMM at ``parameters``, as one
+        ``Forwarder`` each (``simulate.forwarders``; the symbols are made on the device and stay there).  Columns are 0 / 1
+        from the first two emission columns; ``missing=(fraction, mean_run)`` - or ``(2, fraction, mean_run)`` - overlays
+        runs of the missing-data symbol 2."""
+        from . import simulate as _simulate
+        if missing is not None:
+            missing = tuple(missing)
+            if len(missing) == 3 and int(missing[0]) != 2:
+                raise ValueError("the missing-data symbol of these models is 2, got %r" % (missing[0],))
+            missing = (2,) + missing[-2:]
+        pi, T, E = self.build_hidden_markov_model(np.asarray(parameters, dtype=np.float64))
+        return _simulate.forwarders(pi, T, E, length, seed, replicates=replicates, emit_symbols=2, missing=missing)
+
 
 def _repeat_per_epoch(values, intervals):
     if len(values) != len(intervals):
