@@ -11,7 +11,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG, "csrc", "imcoal_fwd.hip")
 HDR = os.path.join(os.path.dirname(PKG), "include", "imcoal_fwd.h")
 DEPS = [SRC, HDR, os.path.join(os.path.dirname(PKG), "include", "imcoal_model.h"), os.path.join(os.path.dirname(PKG), "include", "imcoal_sample.h")] + [os.path.join(PKG, "csrc", f) for f in
-                     ("kernels_plain.hpp", "kernels_zip.hpp", "kernels_stitch.hpp", "kernels_big.hpp", "kernels_zip2.hpp", "kernels_zip3.hpp", "kernels_zip4.hpp", "pair_dict.hpp", "encode_tiles.hpp", "kernels_encode.hpp", "train_tiles.hpp", "kernels_train.hpp", "ingest_tiles.hpp", "kernels_ingest.hpp", "align_tiles.hpp", "kernels_align.hpp", "fasta_io.hpp","plan_host.hpp", "planner_host.hpp", "obs_io.hpp",
+                     ("kernels_plain.hpp", "kernels_zip.hpp", "kernels_stitch.hpp", "kernels_big.hpp", "kernels_zip2.hpp", "kernels_zip3.hpp", "kernels_zip4.hpp", "pair_dict.hpp", "encode_tiles.hpp", "kernels_encode.hpp", "train_tiles.hpp", "kernels_train.hpp", "ingest_tiles.hpp", "kernels_ingest.hpp", "align_tiles.hpp", "kernels_align.hpp", "tile_scan.hpp", "slab_stream.hpp", "fasta_io.hpp", "plan_host.hpp", "planner_host.hpp", "obs_io.hpp",
                       "model_host.hpp", "kernels_model.hpp", "sample_tiles.hpp", "kernels_sample.hpp")]
 LIB = os.path.join(PKG, "libimcoal_fwd.so")
 

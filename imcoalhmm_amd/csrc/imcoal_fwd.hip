@@ -60,6 +60,7 @@
 #include "kernels_train.hpp"
 #include "kernels_ingest.hpp"
 #include "kernels_align.hpp"
+#include "slab_stream.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
 #include "model_host.hpp"
@@ -630,6 +631,44 @@ constexpr size_t ENC_RUN_MAX_ELEMENTS = (size_t)1 << 30;   // per run of passes;
 constexpr size_t ENC_RUN_MAX_CHUNKS = 4096;                // (the histogram's grid and count buffer are per chunk)
 static_assert(ENC_HIST_BINS >= HYBRID_MAX_ALPHABET, "every counted level must fit the histogram's LDS bins");
 
+// The encoder's stream and what a pass over it needs: two 16-bit ping-pong scratch streams of whole tiles, the flag words
+// and the tile tables.  stream() holds n elements.  Used by the encoder and by training, g_mu held.
+struct EncWorkspace {
+    size_t capacity = 0;                             // elements a stream holds (whole tiles)
+    DevBuf<uint16_t> buf[2], flags;
+    DevBuf<imc::TileSummary> sums;
+    DevBuf<uint2> tile_in;
+    uint32_t n = 0;
+    int cur = 0;
+
+    hipError_t alloc(size_t max_elements)
+    {
+        const size_t tiles = (max_elements + TILE_SIZE - 1) / TILE_SIZE;
+        capacity = tiles * TILE_SIZE;
+        hipError_t e = hipSuccess;
+        for (int b = 0; b < 2 && e == hipSuccess; ++b) e = buf[b].alloc((capacity + TILE_ITEMS) * sizeof(uint16_t));
+        if (e == hipSuccess) e = flags.alloc(tiles * TILE_THREADS * sizeof(uint16_t));
+        if (e == hipSuccess) e = sums.alloc(tiles * sizeof(imc::TileSummary));
+        if (e == hipSuccess) e = tile_in.alloc(tiles * sizeof(uint2));
+        return e;
+    }
+    uint16_t *stream() { return buf[cur].get(); }
+    uint32_t tiles() const { return (n + TILE_SIZE - 1) / TILE_SIZE; }
+    // One pass, queued on g.stream: stream() -> the other buffer, the new length lands at d_new_n.  The owner reads it
+    // back by its own protocol and then calls flip().
+    void launch_pass(const EncPass &ps, uint32_t *d_new_n)
+    {
+        hipLaunchKernelGGL(k_enc_summary, dim3(tiles()), dim3(TILE_THREADS), 0, g.stream, stream(), n, ps, flags.get(), sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, sums.get(), tiles(), tile_in.get(), d_new_n);
+        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles()), dim3(TILE_THREADS), 0, g.stream, stream(), n, ps, flags.get(), tile_in.get(), buf[cur ^ 1].get());
+    }
+    void flip(uint32_t new_n)
+    {
+        cur ^= 1;
+        n = new_n;
+    }
+};
+
 int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_t K)
 {
     const imc::EncodeSchedule sch = imc::encode_schedule(dd->dict);
@@ -641,24 +680,17 @@ int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, s
         if (r.counted) max_counted = std::max(max_counted, r.alphabet);
     if (K == 0 || total == 0) return IMC_OK;
     if (total >= (size_t)1 << 31 || K > ENC_RUN_MAX_CHUNKS) return fail(IMC_ERR_ARG, "device encoder: too many elements or chunks in one run");
-    const size_t tiles0 = (total + ENC_TILE - 1) / ENC_TILE;
-    DevBuf<uint16_t> buf[2], flags;
-    DevBuf<imc::TileSummary> sums;
-    DevBuf<uint2> tile_in;
+    EncWorkspace ws;
     DevBuf<uint32_t> new_n, pos, counts;
     DevBuf<uint8_t *> dptr;
     std::vector<uint32_t> hpos(K + 1), hcounts;
     std::vector<uint8_t *> hptr(K);
-    uint32_t n = (uint32_t)total;
-    int cur = 0;
     size_t applied = 0;
 
     auto setup = [&]() -> int {
         HIP_TRY(hipSetDevice(g.device));
-        for (int b = 0; b < 2; ++b) HIP_TRY(buf[b].alloc((tiles0 * ENC_TILE + ENC_ITEMS) * sizeof(uint16_t)));
-        HIP_TRY(flags.alloc(tiles0 * ENC_THREADS * sizeof(uint16_t)));
-        HIP_TRY(sums.alloc(tiles0 * sizeof(imc::TileSummary)));
-        HIP_TRY(tile_in.alloc(tiles0 * sizeof(uint2)));
+        HIP_TRY(ws.alloc(total));
+        ws.n = (uint32_t)total;
         HIP_TRY(new_n.alloc(sizeof(uint32_t)));
         HIP_TRY(pos.alloc((K + 1) * sizeof(uint32_t)));
         HIP_TRY(dptr.alloc(K * sizeof(uint8_t *)));
@@ -667,34 +699,28 @@ int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, s
         for (size_t k = 0; k < K; ++k) {
             const uint32_t L = (uint32_t)obs[k]->L;
             if (!L) return fail(IMC_ERR_ARG, "device encoder: empty chunk");
-            hipLaunchKernelGGL(k_enc_load, dim3((L + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, (const void *)obs[k]->d_sym,
-                               obs[k]->wide_raw ? 2 : 1, L, buf[0].get() + off);
+            hipLaunchKernelGGL(k_enc_load, dim3((L + TILE_THREADS - 1) / TILE_THREADS), dim3(TILE_THREADS), 0, g.stream, (const void *)obs[k]->d_sym,
+                               obs[k]->wide_raw ? 2 : 1, L, ws.stream() + off);
             off += L;
         }
         HIP_TRY(hipGetLastError());
         return IMC_OK;
     };
     auto run_pass = [&](const imc::EncodeSchedule::Pass &p) -> int {
-        const EncPass ps{dd->d_left, dd->d_right, p.z0, p.nz};
-        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
-        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
-        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
-        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
-                           buf[cur ^ 1].get());
+        ws.launch_pass(EncPass{dd->d_left, dd->d_right, p.z0, p.nz}, new_n.get());
         HIP_TRY(hipGetLastError());
         uint32_t hn = 0;
         HIP_TRY(hipMemcpyAsync(&hn, new_n.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device encoder: a pass returned an impossible length");
-        n = hn;
-        cur ^= 1;
+        if (hn == 0 || hn > ws.n) return fail(IMC_ERR_HIP, "device encoder: a pass returned an impossible length");
+        ws.flip(hn);
         return IMC_OK;
     };
     auto snapshot = [&](int l, const imc::LevelRule &r) -> int {
-        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
-        hipLaunchKernelGGL(k_enc_mark_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, sums.get());
-        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), new_n.get());
-        hipLaunchKernelGGL(k_enc_mark_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, tile_in.get(), pos.get(), (uint32_t)K);
+        const uint32_t n = ws.n, tiles = ws.tiles();
+        hipLaunchKernelGGL(k_enc_mark_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, ws.stream(), n, ws.sums.get());
+        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, ws.sums.get(), tiles, ws.tile_in.get(), new_n.get());
+        hipLaunchKernelGGL(k_enc_mark_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, ws.stream(), n, ws.tile_in.get(), pos.get(), (uint32_t)K);
         HIP_TRY(hipGetLastError());
         uint32_t marks = 0;
         HIP_TRY(hipMemcpyAsync(&marks, new_n.get(), sizeof marks, hipMemcpyDeviceToHost, g.stream));
@@ -710,15 +736,15 @@ int device_encode_run(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, s
             hptr[k] = obs[k]->d_tok[l];
         }
         HIP_TRY(hipMemcpyAsync(dptr.get(), hptr.data(), K * sizeof(uint8_t *), hipMemcpyHostToDevice, g.stream));
-        hipLaunchKernelGGL(k_enc_snapshot, dim3((n + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, pos.get(),
+        hipLaunchKernelGGL(k_enc_snapshot, dim3((n + TILE_THREADS - 1) / TILE_THREADS), dim3(TILE_THREADS), 0, g.stream, ws.stream(), n, pos.get(),
                            (uint32_t)K, dptr.get(), r.is_wide ? 0 : 1);
         HIP_TRY(hipGetLastError());
         if (r.counted) {
             uint32_t longest = 1;
             for (size_t k = 0; k < K; ++k) longest = std::max(longest, hpos[k + 1] - hpos[k]);
-            const uint32_t bx = std::max<uint32_t>(1, std::min<uint32_t>(128, (longest + 8 * ENC_THREADS - 1) / (8 * ENC_THREADS)));
+            const uint32_t bx = std::max<uint32_t>(1, std::min<uint32_t>(128, (longest + 8 * TILE_THREADS - 1) / (8 * TILE_THREADS)));
             HIP_TRY(hipMemsetAsync(counts.get(), 0, K * (size_t)r.alphabet * sizeof(uint32_t), g.stream));
-            hipLaunchKernelGGL(k_enc_histogram, dim3(bx, (uint32_t)K), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), pos.get(), r.alphabet, counts.get());
+            hipLaunchKernelGGL(k_enc_histogram, dim3(bx, (uint32_t)K), dim3(TILE_THREADS), 0, g.stream, ws.stream(), pos.get(), r.alphabet, counts.get());
             HIP_TRY(hipGetLastError());
             hcounts.resize(K * (size_t)r.alphabet);
             HIP_TRY(hipMemcpyAsync(hcounts.data(), counts.get(), hcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
@@ -765,26 +791,20 @@ int device_encode(const std::shared_ptr<DictDev> &dd, imc_obs *const *obs, size_
 struct DeviceTrainer {
     const TrainPiece *pieces;
     std::vector<size_t> piece_len;
-    size_t tiles0 = 0;
-    DevBuf<uint16_t> buf[2], flags, left, right, depth;
-    DevBuf<imc::TileSummary> sums;
-    DevBuf<uint2> tile_in, list;
+    EncWorkspace ws;
+    DevBuf<uint16_t> left, right, depth;
+    DevBuf<uint2> list;
     DevBuf<uint32_t> scalars, counts, tkeys, tcounts;   // scalars: [0] new length, [1..3] winner {a, b, count}, [4] candidates, [5] table overflow
     uint32_t table_capacity = 0, list_capacity = 0;
-    uint32_t n = 0, pending_n = 0;
-    int cur = 0;
+    uint32_t pending_n = 0;
 
     int init(const TrainPiece *p, size_t n_pieces, size_t max_stream)
     {
         pieces = p;
         for (size_t k = 0; k < n_pieces; ++k) piece_len.push_back(p[k].n);
         if (max_stream == 0 || max_stream >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "device training: impossible sample size");
-        tiles0 = (max_stream + ENC_TILE - 1) / ENC_TILE;
         HIP_TRY(hipSetDevice(g.device));
-        for (int b = 0; b < 2; ++b) HIP_TRY(buf[b].alloc((tiles0 * ENC_TILE + ENC_ITEMS) * sizeof(uint16_t)));
-        HIP_TRY(flags.alloc(tiles0 * ENC_THREADS * sizeof(uint16_t)));
-        HIP_TRY(sums.alloc(tiles0 * sizeof(imc::TileSummary)));
-        HIP_TRY(tile_in.alloc(tiles0 * sizeof(uint2)));
+        HIP_TRY(ws.alloc(max_stream));
         HIP_TRY(scalars.alloc(8 * sizeof(uint32_t)));
         HIP_TRY(counts.alloc((size_t)imc::kByteAlphabet * imc::kByteAlphabet * sizeof(uint32_t)));
         for (DevBuf<uint16_t> *d : {&left, &right, &depth}) {
@@ -796,33 +816,25 @@ struct DeviceTrainer {
     }
     int load(size_t first, size_t count)
     {
-        if (count > tiles0 * ENC_TILE) return fail(IMC_ERR_HIP, "device training: sample beyond the scratch stream");
+        if (count > ws.capacity) return fail(IMC_ERR_HIP, "device training: sample beyond the scratch stream");
         for (const imc::SampleRange &r : imc::sample_ranges(piece_len, first, count))
-            hipLaunchKernelGGL(k_trn_load, dim3((uint32_t)((r.count + ENC_THREADS - 1) / ENC_THREADS)), dim3(ENC_THREADS), 0, g.stream,
-                               pieces[r.piece].d, pieces[r.piece].unit, (uint32_t)r.src_first, (uint32_t)r.count, buf[0].get() + r.dst_first);
+            hipLaunchKernelGGL(k_trn_load, dim3((uint32_t)((r.count + TILE_THREADS - 1) / TILE_THREADS)), dim3(TILE_THREADS), 0, g.stream,
+                               pieces[r.piece].d, pieces[r.piece].unit, (uint32_t)r.src_first, (uint32_t)r.count, ws.buf[0].get() + r.dst_first);
         HIP_TRY(hipGetLastError());
-        cur = 0;
-        n = (uint32_t)count;
+        ws.cur = 0;
+        ws.n = (uint32_t)count;
         return IMC_OK;
     }
-    void launch_pass(int z0, int nz)                 // buf[cur] -> buf[cur ^ 1], scalars[0] = new length
-    {
-        const EncPass ps{left.get(), right.get(), z0, nz};
-        const uint32_t tiles = (n + ENC_TILE - 1) / ENC_TILE;
-        hipLaunchKernelGGL(k_enc_summary, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), sums.get());
-        hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(ENC_SCAN_THREADS), 0, g.stream, sums.get(), tiles, tile_in.get(), scalars.get());
-        hipLaunchKernelGGL(k_enc_scatter, dim3(tiles), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, ps, flags.get(), tile_in.get(),
-                           buf[cur ^ 1].get());
-    }
+    void launch_pass(int z0, int nz) { ws.launch_pass(EncPass{left.get(), right.get(), z0, nz}, scalars.get()); }   // scalars[0] = new length
     int byte_step(int A, int max_depth, imc::ByteStep *s)
     {
-        if (n < 2 || A >= imc::kByteAlphabet) return fail(IMC_ERR_HIP, "device training: impossible byte step");
+        if (ws.n < 2 || A >= imc::kByteAlphabet) return fail(IMC_ERR_HIP, "device training: impossible byte step");
         HIP_TRY(hipMemsetAsync(counts.get(), 0, (size_t)A * A * sizeof(uint32_t), g.stream));
-        const dim3 grid((n + TRN_HIST_TILE - 1) / TRN_HIST_TILE);
+        const dim3 grid((ws.n + TRN_HIST_TILE - 1) / TRN_HIST_TILE);
         if (imc::pair_bins_in_lds((uint32_t)A))
-            hipLaunchKernelGGL(k_trn_pair_hist<true>, grid, dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, (uint32_t)A, counts.get());
+            hipLaunchKernelGGL(k_trn_pair_hist<true>, grid, dim3(TILE_THREADS), 0, g.stream, ws.stream(), ws.n, (uint32_t)A, counts.get());
         else
-            hipLaunchKernelGGL(k_trn_pair_hist<false>, grid, dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, (uint32_t)A, counts.get());
+            hipLaunchKernelGGL(k_trn_pair_hist<false>, grid, dim3(TILE_THREADS), 0, g.stream, ws.stream(), ws.n, (uint32_t)A, counts.get());
         hipLaunchKernelGGL(k_trn_argmax, dim3(1), dim3(TRN_ARGMAX_THREADS), 0, g.stream, counts.get(), (uint32_t)A, max_depth, left.get(), right.get(),
                            depth.get(), scalars.get() + 1);
         launch_pass(A, 1);                           // (with no winner token A is a stale pair: the output is dropped)
@@ -831,24 +843,20 @@ struct DeviceTrainer {
         HIP_TRY(hipMemcpyAsync(h, scalars.get(), sizeof h, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
         *s = imc::ByteStep{h[1], h[2], h[3], h[0]};
-        if (s->count && (s->a >= (uint32_t)A || s->b >= (uint32_t)A || s->count >= n || s->new_n == 0 || s->new_n > n))
+        if (s->count && (s->a >= (uint32_t)A || s->b >= (uint32_t)A || s->count >= ws.n || s->new_n == 0 || s->new_n > ws.n))
             return fail(IMC_ERR_HIP, "device training: a merge returned an impossible winner or length");
         pending_n = s->new_n;
         return IMC_OK;
     }
-    void accept()
-    {
-        cur ^= 1;
-        n = pending_n;
-    }
-    void truncate(size_t keep) { n = (uint32_t)std::min<size_t>(n, keep); }
+    void accept() { ws.flip(pending_n); }
+    void truncate(size_t keep) { ws.n = (uint32_t)std::min<size_t>(ws.n, keep); }
     int count_round(size_t threshold, std::vector<imc::RoundCandidate> &found)
     {
-        if (n < 2) return fail(IMC_ERR_HIP, "device training: impossible round");
-        const uint32_t cap = imc::count_table_capacity(n);
+        if (ws.n < 2) return fail(IMC_ERR_HIP, "device training: impossible round");
+        const uint32_t cap = imc::count_table_capacity(ws.n);
         if (!tkeys) {                                // the first round is the longest stream the rounds see
             table_capacity = cap;
-            list_capacity = n;
+            list_capacity = ws.n;
             HIP_TRY(tkeys.alloc((size_t)cap * sizeof(uint32_t)));
             HIP_TRY(tcounts.alloc((size_t)cap * sizeof(uint32_t)));
             HIP_TRY(list.alloc((size_t)list_capacity * sizeof(uint2)));
@@ -857,9 +865,9 @@ struct DeviceTrainer {
         HIP_TRY(hipMemsetAsync(tkeys.get(), 0xff, (size_t)cap * sizeof(uint32_t), g.stream));
         HIP_TRY(hipMemsetAsync(tcounts.get(), 0, (size_t)cap * sizeof(uint32_t), g.stream));
         HIP_TRY(hipMemsetAsync(scalars.get() + 4, 0, 2 * sizeof(uint32_t), g.stream));
-        hipLaunchKernelGGL(k_trn_pair_count, dim3((n + ENC_TILE - 1) / ENC_TILE), dim3(ENC_THREADS), 0, g.stream, buf[cur].get(), n, cap, tkeys.get(),
+        hipLaunchKernelGGL(k_trn_pair_count, dim3((ws.n + TILE_SIZE - 1) / TILE_SIZE), dim3(TILE_THREADS), 0, g.stream, ws.stream(), ws.n, cap, tkeys.get(),
                            tcounts.get(), scalars.get() + 5);
-        hipLaunchKernelGGL(k_trn_candidates, dim3((cap + ENC_THREADS - 1) / ENC_THREADS), dim3(ENC_THREADS), 0, g.stream, tkeys.get(), tcounts.get(), cap,
+        hipLaunchKernelGGL(k_trn_candidates, dim3((cap + TILE_THREADS - 1) / TILE_THREADS), dim3(TILE_THREADS), 0, g.stream, tkeys.get(), tcounts.get(), cap,
                            (uint32_t)std::min<size_t>(threshold, 0xffffffffu), list.get(), list_capacity, scalars.get() + 4);
         HIP_TRY(hipGetLastError());
         uint32_t h[2] = {0, 0};
@@ -874,7 +882,7 @@ struct DeviceTrainer {
     }
     int apply(const imc::PairDict &d, int z0, int nz, size_t *new_n)
     {
-        if (n < 1 || nz < 1 || nz > 256 || z0 + nz > imc::kMaxAlphabet || z0 + nz > d.alphabet) return fail(IMC_ERR_HIP, "device training: impossible pass");
+        if (ws.n < 1 || nz < 1 || nz > 256 || z0 + nz > imc::kMaxAlphabet || z0 + nz > d.alphabet) return fail(IMC_ERR_HIP, "device training: impossible pass");
         HIP_TRY(hipMemcpyAsync(left.get() + z0, d.left.data() + z0, (size_t)nz * sizeof(uint16_t), hipMemcpyHostToDevice, g.stream));
         HIP_TRY(hipMemcpyAsync(right.get() + z0, d.right.data() + z0, (size_t)nz * sizeof(uint16_t), hipMemcpyHostToDevice, g.stream));
         launch_pass(z0, nz);
@@ -882,9 +890,8 @@ struct DeviceTrainer {
         uint32_t hn = 0;
         HIP_TRY(hipMemcpyAsync(&hn, scalars.get(), sizeof hn, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (hn == 0 || hn > n) return fail(IMC_ERR_HIP, "device training: a pass returned an impossible length");
-        n = hn;
-        cur ^= 1;
+        if (hn == 0 || hn > ws.n) return fail(IMC_ERR_HIP, "device training: a pass returned an impossible length");
+        ws.flip(hn);
         *new_n = hn;
         return IMC_OK;
     }
@@ -1044,8 +1051,8 @@ int validate_device_symbols(const void *d, int sym_bytes, size_t L, int nsym, co
     DevBuf<uint32_t> first_bad;
     HIP_TRY(first_bad.alloc(sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(first_bad.get(), 0xff, sizeof(uint32_t), g.stream));
-    const dim3 grid((uint32_t)((L + ENC_THREADS - 1) / ENC_THREADS));
-    hipLaunchKernelGGL(k_enc_validate, grid, dim3(ENC_THREADS), 0, g.stream, d, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
+    const dim3 grid((uint32_t)((L + TILE_THREADS - 1) / TILE_THREADS));
+    hipLaunchKernelGGL(k_enc_validate, grid, dim3(TILE_THREADS), 0, g.stream, d, sym_bytes, (uint32_t)L, (uint32_t)nsym, first_bad.get());
     HIP_TRY(hipGetLastError());
     uint32_t bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, first_bad.get(), sizeof bad, hipMemcpyDeviceToHost, g.stream));
@@ -1073,8 +1080,8 @@ int adopt_device_symbols(imc_obs *o, const void *d_src, int sym_bytes, const cha
     if (int rc = alloc_symbols(o)) return rc;
     if (!o->L) return IMC_OK;
     if (int rc = validate_device_symbols(d_src, sym_bytes, o->L, o->nsym, tail)) return rc;
-    const dim3 grid((uint32_t)((o->L + ENC_THREADS - 1) / ENC_THREADS));
-    hipLaunchKernelGGL(k_enc_narrow, grid, dim3(ENC_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)o->L, o->d_sym, o->wide_raw ? 1 : 0);
+    const dim3 grid((uint32_t)((o->L + TILE_THREADS - 1) / TILE_THREADS));
+    hipLaunchKernelGGL(k_enc_narrow, grid, dim3(TILE_THREADS), 0, g.stream, d_src, sym_bytes, (uint32_t)o->L, o->d_sym, o->wide_raw ? 1 : 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g.stream));
     return IMC_OK;
@@ -1160,15 +1167,15 @@ struct IngestStage {             // created, used for HIP calls and destroyed wi
     uint8_t *host[2] = {nullptr, nullptr};
     DevBuf<uint8_t> dev[2];
     hipEvent_t done[2] = {nullptr, nullptr};
-    imc::IngestSummary *verdict = nullptr;     // pinned, one per buffer
+    void *pinned = nullptr;          // pinned, as many bytes as the caller asked for: one verdict per buffer, and what it keeps behind them
 
     IngestStage() = default;
     IngestStage(const IngestStage &) = delete;
     IngestStage &operator=(const IngestStage &) = delete;
-    int alloc(size_t slab_bytes, int buffers)
+    int alloc(size_t slab_bytes, int buffers, size_t pinned_bytes = 0)
     {
         slab = slab_bytes;
-        HIP_TRY(hipHostMalloc((void **)&verdict, 2 * sizeof(imc::IngestSummary), hipHostMallocDefault));
+        if (pinned_bytes) HIP_TRY(hipHostMalloc(&pinned, pinned_bytes, hipHostMallocDefault));
         for (int b = 0; b < buffers; ++b) {
             HIP_TRY(hipHostMalloc((void **)&host[b], slab, hipHostMallocDefault));
             HIP_TRY(dev[b].alloc(ing_slab_alloc(slab)));
@@ -1186,10 +1193,17 @@ struct IngestStage {             // created, used for HIP calls and destroyed wi
             host[b] = nullptr;
             done[b] = nullptr;
         }
-        if (verdict) (void)hipHostFree(verdict);
-        verdict = nullptr;
+        if (pinned) (void)hipHostFree(pinned);
+        pinned = nullptr;
     }
     ~IngestStage() { release(); }
+};
+
+// g_mu for the length of a callback of imc::slab_stream, which runs without it.
+struct Relock {
+    std::unique_lock<std::mutex> &lk;
+    explicit Relock(std::unique_lock<std::mutex> &l) : lk(l) { lk.lock(); }
+    ~Relock() { lk.unlock(); }
 };
 
 // `total` units go to the device in pieces of at most `piece` units, alternating between the stage's two buffers:
@@ -1242,67 +1256,56 @@ int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes,
     const size_t unit = wide ? sizeof(imc::tok_t) : 1;
     const uint64_t room = imc::max_tokens_in(file_bytes);
     const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
-    const size_t tiles_max = (slab + ING_TILE - 1) / ING_TILE;
+    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
     IngestStage st;
     DevBuf<uint8_t> symbols;
     DevBuf<uint16_t> flags;
     DevBuf<imc::IngestSummary> sums, total;
     DevBuf<uint32_t> tile_off;
-    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1)) return rc;
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::IngestSummary))) return rc;
     HIP_TRY(symbols.alloc(room * unit));
-    HIP_TRY(flags.alloc(tiles_max * ING_THREADS * sizeof(uint16_t)));
+    HIP_TRY(flags.alloc(tiles_max * TILE_THREADS * sizeof(uint16_t)));
     HIP_TRY(sums.alloc(tiles_max * sizeof(imc::IngestSummary)));
     HIP_TRY(total.alloc(sizeof(imc::IngestSummary)));
     HIP_TRY(tile_off.alloc(tiles_max * sizeof(uint32_t)));
-    uint64_t cols = 0, sent = 0, slabs = 0, consumed = 0;
-    bool eof = false;
-    auto read_into = [&](uint8_t *dst, size_t want) -> size_t {       // WITHOUT g_mu
-        want = (size_t)std::min<uint64_t>(want, file_bytes - consumed);
-        const size_t got = want ? std::fread(dst, 1, want, fp) : 0;
-        consumed += got;
-        if (got < want || consumed == file_bytes) eof = true;
-        return got;
-    };
-    lk.unlock();
-    size_t fill = read_into(st.host[0], slab);
+    imc::IngestSummary *verdict = static_cast<imc::IngestSummary *>(st.pinned);
+    uint64_t cols = 0, sent = 0, slabs = 0;
+    lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
+    const int end = imc::slab_stream(
+        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [](const uint8_t *buf, size_t fill, bool last) { return imc::slab_cut(buf, fill, last); },
+        [&](int cur, size_t cut) -> int {
+            Relock held(lk);
+            HIP_TRY(hipSetDevice(g.device));
+            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE);
+            HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
+            hipLaunchKernelGGL(k_ing_text_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (uint32_t)nsym, flags.get(),
+                               sums.get());
+            hipLaunchKernelGGL(k_ing_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::IngestSummary *)sums.get(), tiles, tile_off.get(), total.get());
+            hipLaunchKernelGGL(k_ing_text_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (const uint16_t *)flags.get(),
+                               (const uint32_t *)tile_off.get(), symbols.get() + cols * unit, (uint32_t)std::min<uint64_t>(room - cols, 0xffffffffu), wide ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::IngestSummary), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipEventRecord(st.done[cur], g.stream));
+            sent += cut;
+            ++slabs;
+            return IMC_OK;
+        },
+        [&](int cur, size_t cut) -> int {
+            const hipError_t waited = hipEventSynchronize(st.done[cur]);
+            Relock held(lk);
+            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("ingest: ") + hipGetErrorString(waited));
+            const imc::IngestSummary all = verdict[cur];
+            const imc::IngestVerdict v = imc::ingest_verdict(all, (uint32_t)cut);
+            if (v.kind == imc::kIngestDeclined) return imc::kSlabDeclined;
+            if (v.kind == imc::kIngestBadByte) return fail(IMC_ERR_IO, std::string("unexpected character in ") + path);
+            if (v.kind == imc::kIngestSymbol) return fail(IMC_ERR_SYMBOL, imc::symbol_error_text(v.value, cols + v.column, v.at_end));
+            cols += all.count;
+            if (cols > room) return fail(IMC_ERR_HIP, "ingest: more tokens than the file can hold");
+            return IMC_OK;
+        });
     lk.lock();
-    for (int cur = 0;; cur ^= 1) {
-        const bool last = eof;
-        const size_t cut = imc::slab_cut(st.host[cur], fill, last);
-        if (cut == 0 && !last) { *declined = true; return IMC_OK; }
-        if (cut == 0) break;
-        HIP_TRY(hipSetDevice(g.device));
-        const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + ING_TILE - 1) / ING_TILE);
-        HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
-        hipLaunchKernelGGL(k_ing_text_summary, dim3(tiles), dim3(ING_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (uint32_t)nsym, flags.get(),
-                           sums.get());
-        hipLaunchKernelGGL(k_ing_scan, dim3(1), dim3(ING_SCAN_THREADS), 0, g.stream, (const imc::IngestSummary *)sums.get(), tiles, tile_off.get(), total.get());
-        hipLaunchKernelGGL(k_ing_text_scatter, dim3(tiles), dim3(ING_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (const uint16_t *)flags.get(),
-                           (const uint32_t *)tile_off.get(), symbols.get() + cols * unit, (uint32_t)std::min<uint64_t>(room - cols, 0xffffffffu), wide ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&st.verdict[cur], total.get(), sizeof(imc::IngestSummary), hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipEventRecord(st.done[cur], g.stream));
-        sent += cut;
-        ++slabs;
-        // the next slab: what lies behind the cut, then more of the file - read while this one is on the device
-        const size_t carry = fill - cut;
-        lk.unlock();
-        size_t next_fill = carry;
-        if (carry) std::memcpy(st.host[cur ^ 1], st.host[cur] + cut, carry);
-        if (!last) next_fill += read_into(st.host[cur ^ 1] + carry, slab - carry);
-        const hipError_t waited = hipEventSynchronize(st.done[cur]);
-        lk.lock();
-        if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("ingest: ") + hipGetErrorString(waited));
-        const imc::IngestSummary all = st.verdict[cur];
-        const imc::IngestVerdict v = imc::ingest_verdict(all, n);
-        if (v.kind == imc::kIngestDeclined) { *declined = true; return IMC_OK; }
-        if (v.kind == imc::kIngestBadByte) return fail(IMC_ERR_IO, std::string("unexpected character in ") + path);
-        if (v.kind == imc::kIngestSymbol) return fail(IMC_ERR_SYMBOL, imc::symbol_error_text(v.value, cols + v.column, v.at_end));
-        cols += all.count;
-        if (cols > room) return fail(IMC_ERR_HIP, "ingest: more tokens than the file can hold");
-        fill = next_fill;
-        if (last) break;
-    }
+    if (end == imc::kSlabDeclined) { *declined = true; return IMC_OK; }
+    if (end != imc::kSlabDone) return end;
     if (cols >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
     HIP_TRY(hipSetDevice(g.device));
     imc_obs *o = obs_new((size_t)cols, nsym);
@@ -1337,7 +1340,7 @@ int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHea
             if (int rc = ingest_pump(lk, st, payload, slab, &slabs, fill, [&](int b, uint64_t off, uint64_t len) -> int {
                     const uint32_t columns = (uint32_t)std::min<uint64_t>(4 * len, L - 4 * off);
                     HIP_TRY(hipMemcpyAsync(st.dev[b].get(), st.host[b], (size_t)len, hipMemcpyHostToDevice, g.stream));
-                    hipLaunchKernelGGL(k_ing_unpack2, dim3((uint32_t)((len + ING_THREADS - 1) / ING_THREADS)), dim3(ING_THREADS), 0, g.stream,
+                    hipLaunchKernelGGL(k_ing_unpack2, dim3((uint32_t)((len + TILE_THREADS - 1) / TILE_THREADS)), dim3(TILE_THREADS), 0, g.stream,
                                        (const uint8_t *)st.dev[b].get(), columns, o->d_sym + 4 * off * unit, o->wide_raw ? 1 : 0);
                     return IMC_OK;
                 }))
@@ -1410,7 +1413,7 @@ int obs_from_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **ou
                          },
                          [&](int b, uint64_t off, uint64_t len) -> int {
                              HIP_TRY(hipMemcpyAsync(st.dev[b].get(), st.host[b], half + (size_t)len, hipMemcpyHostToDevice, g.stream));
-                             hipLaunchKernelGGL(k_ing_pairwise, dim3((uint32_t)((len + 4 * ING_THREADS - 1) / (4 * ING_THREADS))), dim3(ING_THREADS), 0, g.stream,
+                             hipLaunchKernelGGL(k_ing_pairwise, dim3((uint32_t)((len + 4 * TILE_THREADS - 1) / (4 * TILE_THREADS))), dim3(TILE_THREADS), 0, g.stream,
                                                 (const uint8_t *)st.dev[b].get(), (const uint8_t *)st.dev[b].get() + half, (uint32_t)len, o->d_sym + off);
                              return IMC_OK;
                          });
@@ -1432,20 +1435,12 @@ void aln_release(imc_aln *a)
     a->d_bases = nullptr;
 }
 
-struct PinnedBuf {               // created, used and destroyed with g_mu held
-    void *p = nullptr;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-};
-
 // FASTA file of file_bytes bytes, fp at its start, into a (empty).  *declined: the device parser does not take this file;
 // a holds nothing then.
 int aln_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, imc_aln *a, bool *declined)
 {
     const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
-    const size_t tiles_max = (slab + ALN_TILE - 1) / ALN_TILE;
+    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
     const uint64_t room = (file_bytes + 15) & ~(uint64_t)15;
     IngestStage st;
     DevBuf<uint8_t> bases;
@@ -1453,77 +1448,64 @@ int aln_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_b
     DevBuf<AlnTileIn> tile_in;
     DevBuf<imc::AlnTotal> total;
     DevBuf<imc::AlnRecord> table;
-    PinnedBuf pinned;                                                   // two totals, then the record table
-    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1)) return rc;
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::AlnTotal) + imc::kMaxAlnRecords * sizeof(imc::AlnRecord))) return rc;
     HIP_TRY(bases.alloc((size_t)room));
     HIP_TRY(sums.alloc(tiles_max * sizeof(imc::AlnSummary)));
     HIP_TRY(tile_in.alloc(tiles_max * sizeof(AlnTileIn)));
     HIP_TRY(total.alloc(sizeof(imc::AlnTotal)));
     HIP_TRY(table.alloc(imc::kMaxAlnRecords * sizeof(imc::AlnRecord)));
-    HIP_TRY(hipHostMalloc(&pinned.p, 2 * sizeof(imc::AlnTotal) + imc::kMaxAlnRecords * sizeof(imc::AlnRecord), hipHostMallocDefault));
-    imc::AlnTotal *verdict = static_cast<imc::AlnTotal *>(pinned.p);
+    imc::AlnTotal *verdict = static_cast<imc::AlnTotal *>(st.pinned);   // two totals, then the record table
     imc::AlnRecord *recs = reinterpret_cast<imc::AlnRecord *>(verdict + 2);
-    uint64_t kept = 0, sent = 0, slabs = 0, consumed = 0;
+    uint64_t kept = 0, sent = 0, slabs = 0;
     uint32_t state = imc::kAlnStart0, prev = '\n';
-    bool eof = false;
-    auto read_into = [&](uint8_t *dst, size_t want) -> size_t {       // WITHOUT g_mu
-        want = (size_t)std::min<uint64_t>(want, file_bytes - consumed);
-        const size_t got = want ? std::fread(dst, 1, want, fp) : 0;
-        consumed += got;
-        if (got < want || consumed == file_bytes) eof = true;
-        return got;
-    };
-    lk.unlock();
-    size_t fill = read_into(st.host[0], slab);
-    lk.lock();
-    for (int cur = 0;; cur ^= 1) {
-        const bool last = eof;
-        const size_t cut = imc::aln_slab_cut(st.host[cur], fill, last, state);
-        if (cut == 0 && !last) { *declined = true; return IMC_OK; }
-        if (cut == 0) break;
-        HIP_TRY(hipSetDevice(g.device));
-        const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + ALN_TILE - 1) / ALN_TILE), have = (uint32_t)a->names.size();
-        HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
-        hipLaunchKernelGGL(k_aln_summary, dim3(tiles), dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, sums.get());
-        hipLaunchKernelGGL(k_aln_scan, dim3(1), dim3(ALN_SCAN_THREADS), 0, g.stream, (const imc::AlnSummary *)sums.get(), tiles, state, tile_in.get(), total.get());
-        hipLaunchKernelGGL(k_aln_scatter, dim3(tiles), dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, (const AlnTileIn *)tile_in.get(),
-                           bases.get(), kept, room, table.get(), have, imc::kMaxAlnRecords);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::AlnTotal), hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipEventRecord(st.done[cur], g.stream));
-        sent += cut;
-        ++slabs;
-        // the next slab: what lies behind the cut, then more of the file - read while this one is on the device
-        const size_t carry = fill - cut;
-        lk.unlock();
-        size_t next_fill = carry;
-        if (carry) std::memcpy(st.host[cur ^ 1], st.host[cur] + cut, carry);
-        if (!last) next_fill += read_into(st.host[cur ^ 1] + carry, slab - carry);
-        const hipError_t waited = hipEventSynchronize(st.done[cur]);
-        lk.lock();
-        if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
-        const imc::AlnTotal t = verdict[cur];
-        if (t.decline || (uint64_t)have + t.hdr > imc::kMaxAlnRecords) { *declined = true; return IMC_OK; }
-        if (kept + t.seq > room) return fail(IMC_ERR_HIP, "alignment: more bases than the file can hold");
-        if (t.hdr) {                                                    // the names, from the slab's bytes in pinned memory
+    lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
+    const int end = imc::slab_stream(
+        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [&](const uint8_t *buf, size_t fill, bool last) { return imc::aln_slab_cut(buf, fill, last, state); },
+        [&](int cur, size_t cut) -> int {
+            Relock held(lk);
             HIP_TRY(hipSetDevice(g.device));
-            HIP_TRY(hipMemcpyAsync(recs, table.get() + have, t.hdr * sizeof(imc::AlnRecord), hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            for (uint32_t k = 0; k < t.hdr; ++k) {
-                const size_t at = (size_t)recs[k].slab_offset + 1;
-                if (at > cut || recs[k].start > kept + t.seq) return fail(IMC_ERR_HIP, "alignment: a header outside its slab");
-                std::string name = imc::aln_header_name(st.host[cur], cut, at - 1);
-                if (name.empty()) { *declined = true; return IMC_OK; }
-                a->names.push_back(std::move(name));
-                a->start.push_back(recs[k].start);
+            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE), have = (uint32_t)a->names.size();
+            HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
+            hipLaunchKernelGGL(k_aln_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, sums.get());
+            hipLaunchKernelGGL(k_aln_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::AlnSummary *)sums.get(), tiles, state, tile_in.get(), total.get());
+            hipLaunchKernelGGL(k_aln_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, (const AlnTileIn *)tile_in.get(),
+                               bases.get(), kept, room, table.get(), have, imc::kMaxAlnRecords);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::AlnTotal), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipEventRecord(st.done[cur], g.stream));
+            sent += cut;
+            ++slabs;
+            return IMC_OK;
+        },
+        [&](int cur, size_t cut) -> int {
+            const hipError_t waited = hipEventSynchronize(st.done[cur]);
+            Relock held(lk);
+            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
+            const imc::AlnTotal t = verdict[cur];
+            const uint32_t have = (uint32_t)a->names.size();
+            if (t.decline || (uint64_t)have + t.hdr > imc::kMaxAlnRecords) return imc::kSlabDeclined;
+            if (kept + t.seq > room) return fail(IMC_ERR_HIP, "alignment: more bases than the file can hold");
+            if (t.hdr) {                                                // the names, from the slab's bytes in pinned memory
+                HIP_TRY(hipSetDevice(g.device));
+                HIP_TRY(hipMemcpyAsync(recs, table.get() + have, t.hdr * sizeof(imc::AlnRecord), hipMemcpyDeviceToHost, g.stream));
+                HIP_TRY(hipStreamSynchronize(g.stream));
+                for (uint32_t k = 0; k < t.hdr; ++k) {
+                    const size_t at = (size_t)recs[k].slab_offset + 1;
+                    if (at > cut || recs[k].start > kept + t.seq) return fail(IMC_ERR_HIP, "alignment: a header outside its slab");
+                    std::string name = imc::aln_header_name(st.host[cur], cut, at - 1);
+                    if (name.empty()) return imc::kSlabDeclined;
+                    a->names.push_back(std::move(name));
+                    a->start.push_back(recs[k].start);
+                }
             }
-        }
-        kept += t.seq;
-        state = t.exit;
-        prev = st.host[cur][cut - 1];
-        fill = next_fill;
-        if (last) break;
-    }
+            kept += t.seq;
+            state = t.exit;
+            prev = st.host[cur][cut - 1];
+            return IMC_OK;
+        });
+    lk.lock();
+    if (end == imc::kSlabDeclined) { *declined = true; return IMC_OK; }
+    if (end != imc::kSlabDone) return end;
     std::set<std::string> seen(a->names.begin(), a->names.end());
     if (seen.size() != a->names.size()) { *declined = true; return IMC_OK; }
     for (size_t k = 0; k < a->start.size(); ++k) a->length.push_back((k + 1 < a->start.size() ? a->start[k + 1] : kept) - a->start[k]);
@@ -1599,11 +1581,11 @@ int obs_from_alignment(const imc_aln *a, const uint64_t *offsets, int k, size_t 
     if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
     int rc = alloc_symbols(o);
     if (rc == IMC_OK && L) {
-        const dim3 grid((uint32_t)((L + (size_t)ALN_COLUMNS * ALN_THREADS - 1) / ((size_t)ALN_COLUMNS * ALN_THREADS)));
+        const dim3 grid((uint32_t)((L + (size_t)ALN_COLUMNS * TILE_THREADS - 1) / ((size_t)ALN_COLUMNS * TILE_THREADS)));
         if (k == 2)
-            hipLaunchKernelGGL(k_aln_columns<2>, grid, dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], (uint64_t)0, (uint32_t)L, o->d_sym);
+            hipLaunchKernelGGL(k_aln_columns<2>, grid, dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], (uint64_t)0, (uint32_t)L, o->d_sym);
         else
-            hipLaunchKernelGGL(k_aln_columns<3>, grid, dim3(ALN_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], offsets[2], (uint32_t)L, o->d_sym);
+            hipLaunchKernelGGL(k_aln_columns<3>, grid, dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], offsets[2], (uint32_t)L, o->d_sym);
         if (hipGetLastError() != hipSuccess) rc = fail(IMC_ERR_HIP, "alignment: the column kernel could not be launched");
     }
     if (rc == IMC_OK) rc = finish_device_chunk(lk, o);

@@ -4,7 +4,7 @@
 //
 // The stream lives in two 16-bit ping-pong scratch buffers; bit 15 marks a chunk's first element (imc::kChunkMark), so
 // K concatenated chunks go through one run of passes.  A PASS is three launches, ordered by kernel boundaries only:
-//   k_enc_summary   one workgroup per tile of ENC_TILE elements: the pair flag of every position (16 bits per thread,
+//   k_enc_summary   one workgroup per tile of TILE_SIZE elements: the pair flag of every position (16 bits per thread,
 //                   kept for the scatter) and the tile's summary (emitted count and outgoing carry per incoming carry)
 //   k_enc_scan      ONE workgroup: every tile's incoming carry and output offset, and the new length
 //   k_enc_scatter   one workgroup per tile: emits into LDS in order, then writes its part of the output coalesced
@@ -26,22 +26,19 @@
 #include <hip/hip_runtime.h>
 
 #include "encode_tiles.hpp"
+#include "tile_scan.hpp"
 
-constexpr int ENC_THREADS = 256;
-constexpr int ENC_ITEMS = 16;                          // consecutive elements per thread: one 16-bit flag word
-constexpr int ENC_TILE = ENC_THREADS * ENC_ITEMS;      // 4096 elements per workgroup
-constexpr int ENC_SCAN_THREADS = 1024;
 constexpr int ENC_HIST_BINS = 4096;                    // largest alphabet whose tokens are counted (HYBRID_MAX_ALPHABET)
-static_assert(ENC_TILE < (int)imc::kPackedCountLimit, "a tile's counts must fit the packed summary");
+static_assert(TILE_SIZE < (int)imc::kPackedCountLimit, "a tile's counts must fit the packed summary");
 
 struct EncPass {
     const uint16_t *left, *right;   // the dictionary's device copy: token z = left[z] followed by right[z]
     int z0, nz;                     // the pass replaces the pairs of tokens z0 .. z0 + nz - 1 (nz <= 256)
 };
 
-// Scratch buffers hold ENC_TILE * tiles + ENC_ITEMS elements, so the vector loads of a tile's last thread and the
+// Scratch buffers hold TILE_SIZE * tiles + TILE_ITEMS elements, so the vector loads of a tile's last thread and the
 // look-ahead element stay inside the allocation; what lies beyond n is never used (every use checks the index).
-__device__ inline void enc_load_items(const uint16_t *seq, uint32_t base, uint16_t (&x)[ENC_ITEMS + 1])
+__device__ inline void enc_load_items(const uint16_t *seq, uint32_t base, uint16_t (&x)[TILE_ITEMS + 1])
 {
     const uint4 *p = reinterpret_cast<const uint4 *>(seq + base);
     const uint4 a = p[0], b = p[1];
@@ -51,16 +48,16 @@ __device__ inline void enc_load_items(const uint16_t *seq, uint32_t base, uint16
         x[2 * j] = (uint16_t)(w[j] & 0xffffu);
         x[2 * j + 1] = (uint16_t)(w[j] >> 16);
     }
-    x[ENC_ITEMS] = seq[base + ENC_ITEMS];
+    x[TILE_ITEMS] = seq[base + TILE_ITEMS];
 }
 
 // The round's keys into the workgroup's LDS set (hk: kKeySlots words, hv: kKeySlots ids); nothing to do for one pair.
 __device__ inline void enc_build_keys(const EncPass &ps, uint32_t *hk, uint16_t *hv)
 {
     if (ps.nz <= 1) return;
-    for (uint32_t s = threadIdx.x; s < imc::kKeySlots; s += ENC_THREADS) hk[s] = imc::kNoKey;
+    for (uint32_t s = threadIdx.x; s < imc::kKeySlots; s += TILE_THREADS) hk[s] = imc::kNoKey;
     __syncthreads();
-    for (int q = threadIdx.x; q < ps.nz; q += ENC_THREADS) {
+    for (int q = threadIdx.x; q < ps.nz; q += TILE_THREADS) {
         const int z = ps.z0 + q;
         const uint32_t k = imc::key_of(ps.left[z], ps.right[z]);
         uint32_t s = imc::key_slot(k);
@@ -80,156 +77,123 @@ __device__ inline uint16_t enc_pair_token(const EncPass &ps, uint16_t one_a, uin
     return imc::key_lookup(hk, hv, imc::key_of(a, b));
 }
 
-// Exclusive scan of one packed summary per thread over the workgroup's ENC_THREADS threads, in thread order; `total`
+// Exclusive scan of one packed summary per thread over the workgroup's TILE_THREADS threads, in thread order; `total`
 // gets the whole tile's summary.  wave_tot: 4 words of LDS.  Two barriers; all threads must call it.
 __device__ inline uint32_t enc_wg_scan(uint32_t mine, uint32_t *wave_tot, uint32_t &total)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t v = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d);
-        if (lane >= d) v = imc::tile_pack(imc::tile_combine(imc::tile_unpack(u), imc::tile_unpack(v)));
-    }
-    if (lane == 63) wave_tot[wave] = v;
-    uint32_t before = __shfl_up(v, 1);
-    const uint32_t ident = imc::tile_pack(imc::tile_identity());
-    if (lane == 0) before = ident;
+    const uint32_t before = tile_wg_scan(
+        mine, imc::tile_pack(imc::tile_identity()),
+        [](uint32_t a, uint32_t b) { return imc::tile_pack(imc::tile_combine(imc::tile_unpack(a), imc::tile_unpack(b))); }, wave_tot, total);
     __syncthreads();
-    imc::TileSummary prefix = imc::tile_identity(), all = imc::tile_identity();
-#pragma unroll
-    for (int j = 0; j < ENC_THREADS / 64; ++j) {
-        const imc::TileSummary t = imc::tile_unpack(wave_tot[j]);
-        if (j < wave) prefix = imc::tile_combine(prefix, t);
-        all = imc::tile_combine(all, t);
-    }
-    __syncthreads();
-    total = imc::tile_pack(all);
-    return imc::tile_pack(imc::tile_combine(prefix, imc::tile_unpack(before)));
+    return before;
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_summary(const uint16_t *seq, uint32_t n, EncPass ps, uint16_t *flags,
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_summary(const uint16_t *seq, uint32_t n, EncPass ps, uint16_t *flags,
                                                             imc::TileSummary *sums)
 {
     __shared__ uint32_t hk[imc::kKeySlots];
     __shared__ uint16_t hv[imc::kKeySlots];
-    __shared__ uint32_t wave_tot[ENC_THREADS / 64];
+    __shared__ uint32_t wave_tot[TILE_THREADS / 64];
     enc_build_keys(ps, hk, hv);
     const uint16_t one_a = ps.left[ps.z0], one_b = ps.right[ps.z0];
-    const uint32_t base = blockIdx.x * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
-    uint16_t x[ENC_ITEMS + 1];
+    const uint32_t base = blockIdx.x * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
+    uint16_t x[TILE_ITEMS + 1];
     enc_load_items(seq, base, x);
     uint32_t mask = 0;
     imc::TileSummary s = imc::tile_identity();
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i) {
+    for (int i = 0; i < TILE_ITEMS; ++i) {
         const uint32_t t = base + i;
         const bool m = t + 1 < n && enc_pair_token(ps, one_a, one_b, hk, hv, x[i], x[i + 1]) != imc::kNoToken;
         mask |= (m ? 1u : 0u) << i;
         if (t < n) s = imc::tile_step(s, m);
     }
-    flags[blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x] = (uint16_t)mask;
+    flags[blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x] = (uint16_t)mask;
     uint32_t total;
     (void)enc_wg_scan(imc::tile_pack(s), wave_tot, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = imc::tile_unpack(total);
 }
 
 // One workgroup.  tile_in[i] = (output offset, incoming carry) of tile i; *new_n = elements emitted in all.
-// Every thread folds ceil(ntiles / ENC_SCAN_THREADS) consecutive summaries, the folds are scanned in LDS, and the
-// thread walks its summaries again from its own prefix.
-__global__ __launch_bounds__(ENC_SCAN_THREADS) void k_enc_scan(const imc::TileSummary *sums, uint32_t ntiles, uint2 *tile_in, uint32_t *new_n)
+__global__ __launch_bounds__(TILE_SCAN_THREADS) void k_enc_scan(const imc::TileSummary *sums, uint32_t ntiles, uint2 *tile_in, uint32_t *new_n)
 {
-    __shared__ imc::TileSummary sc[ENC_SCAN_THREADS];
-    const uint32_t per = (ntiles + ENC_SCAN_THREADS - 1) / ENC_SCAN_THREADS;
-    const uint32_t lo = min(threadIdx.x * per, ntiles), hi = min(lo + per, ntiles);
-    imc::TileSummary acc = imc::tile_identity();
-    for (uint32_t i = lo; i < hi; ++i) acc = imc::tile_combine(acc, sums[i]);
-    sc[threadIdx.x] = acc;
-    __syncthreads();
-    for (int d = 1; d < ENC_SCAN_THREADS; d <<= 1) {          // inclusive scan in thread order
-        imc::TileSummary v = sc[threadIdx.x];
-        if ((int)threadIdx.x >= d) v = imc::tile_combine(sc[threadIdx.x - d], v);
-        __syncthreads();
-        sc[threadIdx.x] = v;
-        __syncthreads();
-    }
-    imc::TileSummary run = threadIdx.x ? sc[threadIdx.x - 1] : imc::tile_identity();
-    for (uint32_t i = lo; i < hi; ++i) {
-        tile_in[i] = make_uint2(run.cnt[0], run.out[0]);      // the stream starts with nothing taken before it: case 0
-        run = imc::tile_combine(run, sums[i]);
-    }
-    if (threadIdx.x == ENC_SCAN_THREADS - 1) *new_n = sc[ENC_SCAN_THREADS - 1].cnt[0];
+    __shared__ imc::TileSummary sc[TILE_SCAN_THREADS];
+    const imc::TileSummary all = tile_scan_elements(
+        ntiles, imc::tile_identity(), sc, [&](uint32_t i) { return sums[i]; },
+        [](const imc::TileSummary &a, const imc::TileSummary &b) { return imc::tile_combine(a, b); },
+        [&](uint32_t i, const imc::TileSummary &run) { tile_in[i] = make_uint2(run.cnt[0], run.out[0]); });   // the stream starts with nothing taken before it: case 0
+    if (threadIdx.x == TILE_SCAN_THREADS - 1) *new_n = all.cnt[0];
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_scatter(const uint16_t *seq, uint32_t n, EncPass ps, const uint16_t *flags,
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_scatter(const uint16_t *seq, uint32_t n, EncPass ps, const uint16_t *flags,
                                                             const uint2 *tile_in, uint16_t *out)
 {
     __shared__ uint32_t hk[imc::kKeySlots];
     __shared__ uint16_t hv[imc::kKeySlots];
-    __shared__ uint32_t wave_tot[ENC_THREADS / 64];
-    __shared__ uint16_t stage[ENC_TILE];
+    __shared__ uint32_t wave_tot[TILE_THREADS / 64];
+    __shared__ uint16_t stage[TILE_SIZE];
     enc_build_keys(ps, hk, hv);
     const uint16_t one_a = ps.left[ps.z0], one_b = ps.right[ps.z0];
-    const uint32_t base = blockIdx.x * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
-    uint16_t x[ENC_ITEMS + 1];
+    const uint32_t base = blockIdx.x * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
+    uint16_t x[TILE_ITEMS + 1];
     enc_load_items(seq, base, x);
-    const uint32_t mask = flags[blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x];
+    const uint32_t mask = flags[blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x];
     const uint2 in = tile_in[blockIdx.x];
     imc::TileSummary s = imc::tile_identity();
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i)
+    for (int i = 0; i < TILE_ITEMS; ++i)
         if (base + i < n) s = imc::tile_step(s, (mask >> i) & 1u);
     uint32_t total;
     const imc::TileSummary before = imc::tile_unpack(enc_wg_scan(imc::tile_pack(s), wave_tot, total));
     uint32_t carry = in.y ? before.out[1] : before.out[0], w = in.y ? before.cnt[1] : before.cnt[0];
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i) {
+    for (int i = 0; i < TILE_ITEMS; ++i) {
         if (base + i < n) {
             const imc::EmitKind kind = imc::emit_step((mask >> i) & 1u, carry);
             if (kind != imc::kEmitNothing) {
                 const uint16_t v = kind == imc::kEmitToken ? enc_pair_token(ps, one_a, one_b, hk, hv, x[i], x[i + 1]) : x[i];
-                if (w < (uint32_t)ENC_TILE) stage[w] = v;
+                if (w < (uint32_t)TILE_SIZE) stage[w] = v;
                 ++w;
             }
         }
     }
     __syncthreads();
     const imc::TileSummary whole = imc::tile_unpack(total);
-    const uint32_t count = min(in.y ? whole.cnt[1] : whole.cnt[0], (uint32_t)ENC_TILE);
-    for (uint32_t j = threadIdx.x; j < count; j += ENC_THREADS)
+    const uint32_t count = min(in.y ? whole.cnt[1] : whole.cnt[0], (uint32_t)TILE_SIZE);
+    for (uint32_t j = threadIdx.x; j < count; j += TILE_THREADS)
         if (in.x + j < n) out[in.x + j] = stage[j];            // (a pass never lengthens the stream)
 }
 
 // ---- chunk starts ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_mark_summary(const uint16_t *seq, uint32_t n, imc::TileSummary *sums)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_mark_summary(const uint16_t *seq, uint32_t n, imc::TileSummary *sums)
 {
-    __shared__ uint32_t wave_tot[ENC_THREADS / 64];
-    const uint32_t base = blockIdx.x * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
-    uint16_t x[ENC_ITEMS + 1];
+    __shared__ uint32_t wave_tot[TILE_THREADS / 64];
+    const uint32_t base = blockIdx.x * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
+    uint16_t x[TILE_ITEMS + 1];
     enc_load_items(seq, base, x);
     uint32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i) c += (base + i < n && (x[i] & imc::kChunkMark)) ? 1u : 0u;
+    for (int i = 0; i < TILE_ITEMS; ++i) c += (base + i < n && (x[i] & imc::kChunkMark)) ? 1u : 0u;
     uint32_t total;
     (void)enc_wg_scan(imc::tile_pack(imc::TileSummary{{c, c}, {0u, 1u}}), wave_tot, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = imc::tile_unpack(total);
 }
 
 // pos[k] = position of the k-th marked element (k < K), pos[K] = n
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_mark_scatter(const uint16_t *seq, uint32_t n, const uint2 *tile_in, uint32_t *pos, uint32_t K)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_mark_scatter(const uint16_t *seq, uint32_t n, const uint2 *tile_in, uint32_t *pos, uint32_t K)
 {
-    __shared__ uint32_t wave_tot[ENC_THREADS / 64];
-    const uint32_t base = blockIdx.x * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
-    uint16_t x[ENC_ITEMS + 1];
+    __shared__ uint32_t wave_tot[TILE_THREADS / 64];
+    const uint32_t base = blockIdx.x * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
+    uint16_t x[TILE_ITEMS + 1];
     enc_load_items(seq, base, x);
     uint32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i) c += (base + i < n && (x[i] & imc::kChunkMark)) ? 1u : 0u;
+    for (int i = 0; i < TILE_ITEMS; ++i) c += (base + i < n && (x[i] & imc::kChunkMark)) ? 1u : 0u;
     uint32_t total;
     const imc::TileSummary before = imc::tile_unpack(enc_wg_scan(imc::tile_pack(imc::TileSummary{{c, c}, {0u, 1u}}), wave_tot, total));
     uint32_t k = tile_in[blockIdx.x].x + before.cnt[0];
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i)
+    for (int i = 0; i < TILE_ITEMS; ++i)
         if (base + i < n && (x[i] & imc::kChunkMark)) {
             if (k < K) pos[k] = base + i;
             ++k;
@@ -239,10 +203,10 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_mark_scatter(const uint16_t
 
 // Element t of the stream belongs to the chunk k with pos[k] <= t < pos[k + 1]; it goes to dst[k][t - pos[k]] without
 // its mark, as a byte (narrow) or as a 16-bit id.  The level buffers were sized from the same pos[].
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_snapshot(const uint16_t *seq, uint32_t n, const uint32_t *pos, uint32_t K,
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_snapshot(const uint16_t *seq, uint32_t n, const uint32_t *pos, uint32_t K,
                                                              uint8_t *const *dst, int narrow)
 {
-    const uint32_t t = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t t = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (t >= n) return;
     uint32_t lo = 0, hi = K;                                   // invariant: pos[lo] <= t < pos[hi]
     for (int step = 0; step < 32 && hi - lo > 1; ++step) {
@@ -257,19 +221,19 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_snapshot(const uint16_t *se
 }
 
 // counts[k][z] += occurrences of token z at positions >= 1 of chunk k (blockIdx.y = k); counts zeroed by the caller.
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_histogram(const uint16_t *seq, const uint32_t *pos, int alphabet, uint32_t *counts)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_histogram(const uint16_t *seq, const uint32_t *pos, int alphabet, uint32_t *counts)
 {
     __shared__ uint32_t bins[ENC_HIST_BINS];
-    for (int b = threadIdx.x; b < alphabet; b += ENC_THREADS) bins[b] = 0;
+    for (int b = threadIdx.x; b < alphabet; b += TILE_THREADS) bins[b] = 0;
     __syncthreads();
     const uint32_t k = blockIdx.y, lo = pos[k] + 1, hi = pos[k + 1];
-    const uint32_t stride = gridDim.x * (uint32_t)ENC_THREADS;
-    for (uint64_t t = (uint64_t)lo + blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x; t < hi; t += stride) {
+    const uint32_t stride = gridDim.x * (uint32_t)TILE_THREADS;
+    for (uint64_t t = (uint64_t)lo + blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x; t < hi; t += stride) {
         const uint32_t z = seq[t] & (uint32_t)(imc::kChunkMark - 1);
         if (z < (uint32_t)alphabet) atomicAdd(&bins[z], 1u);
     }
     __syncthreads();
-    for (int b = threadIdx.x; b < alphabet; b += ENC_THREADS)
+    for (int b = threadIdx.x; b < alphabet; b += TILE_THREADS)
         if (bins[b]) atomicAdd(&counts[(size_t)k * alphabet + b], bins[b]);
 }
 
@@ -281,21 +245,21 @@ __device__ inline uint32_t enc_symbol(const void *src, int sym_bytes, size_t t)
                           : static_cast<const uint32_t *>(src)[t];          // (a negative int32 is a huge unsigned value)
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_load(const void *src, int sym_bytes, uint32_t L, uint16_t *dst)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_load(const void *src, int sym_bytes, uint32_t L, uint16_t *dst)
 {
-    const uint32_t t = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t t = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (t < L) dst[t] = (uint16_t)(enc_symbol(src, sym_bytes, t) | (t == 0 ? (uint32_t)imc::kChunkMark : 0u));
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_validate(const void *src, int sym_bytes, uint32_t L, uint32_t nsym, uint32_t *first_bad)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_validate(const void *src, int sym_bytes, uint32_t L, uint32_t nsym, uint32_t *first_bad)
 {
-    const uint32_t t = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t t = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (t < L && enc_symbol(src, sym_bytes, t) >= nsym) atomicMin(first_bad, t);
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void k_enc_narrow(const void *src, int sym_bytes, uint32_t L, uint8_t *dst, int dst_wide)
+__global__ __launch_bounds__(TILE_THREADS) void k_enc_narrow(const void *src, int sym_bytes, uint32_t L, uint8_t *dst, int dst_wide)
 {
-    const uint32_t t = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t t = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (t >= L) return;
     const uint32_t v = enc_symbol(src, sym_bytes, t);
     if (dst_wide) reinterpret_cast<uint16_t *>(dst)[t] = (uint16_t)v;

@@ -5,7 +5,7 @@
 //
 // TEXT.  A slab of the file (cut after a whitespace byte, so no token crosses its end and the byte before it is no
 // digit) is parsed by three launches, ordered by kernel boundaries only:
-//   k_ing_text_summary   one workgroup per tile of ING_TILE bytes: the token starts of every thread's 16 bytes (one flag
+//   k_ing_text_summary   one workgroup per tile of TILE_SIZE bytes: the token starts of every thread's 16 bytes (one flag
 //                        word, kept for the scatter) and the tile's summary: token count, first bad byte, first token
 //                        that is not below nsym - with the byte at which the host loop detects it, its value and its
 //                        column within the tile -, and whether a digit run longer than 16 starts here (declined)
@@ -26,42 +26,39 @@
 #include <hip/hip_runtime.h>
 
 #include "ingest_tiles.hpp"
+#include "tile_scan.hpp"
 
-constexpr int ING_THREADS = 256;
-constexpr int ING_ITEMS = 16;                          // consecutive bytes per thread: one 16-bit flag word
-constexpr int ING_TILE = ING_THREADS * ING_ITEMS;      // 4096 bytes per workgroup
 constexpr int ING_HALO = 16;                           // bytes behind a tile that a token starting in it may read
 constexpr int ING_FRONT = 16;                          // LDS bytes in front of the tile (the last one: the byte before it)
-constexpr int ING_SCAN_THREADS = 1024;
-constexpr int ING_TILE_TOKENS = ING_TILE / 2;          // a token start needs a non-digit before it
+constexpr int ING_TILE_TOKENS = TILE_SIZE / 2;          // a token start needs a non-digit before it
 static_assert(ING_HALO >= (int)imc::kMaxTokenDigits, "the 17 bytes a token read looks at must be staged");
 
 // bytes a slab buffer must have for a slab of n bytes
-constexpr size_t ing_slab_alloc(size_t n) { return (n + ING_TILE - 1) / ING_TILE * ING_TILE + ING_HALO; }
+constexpr size_t ing_slab_alloc(size_t n) { return (n + TILE_SIZE - 1) / TILE_SIZE * TILE_SIZE + ING_HALO; }
 
-// The tile's bytes into LDS: sb[ING_FRONT + i] = slab[tile_base + i] for -1 <= i < ING_TILE + ING_HALO (16-byte loads;
+// The tile's bytes into LDS: sb[ING_FRONT + i] = slab[tile_base + i] for -1 <= i < TILE_SIZE + ING_HALO (16-byte loads;
 // the slab buffer is 16-byte aligned).  Ends with a barrier.
 __device__ inline void ing_stage_tile(const uint8_t *slab, uint32_t tile_base, uint8_t *sb)
 {
     const uint4 *src = reinterpret_cast<const uint4 *>(slab + tile_base);
     uint4 *dst = reinterpret_cast<uint4 *>(sb + ING_FRONT);
     dst[threadIdx.x] = src[threadIdx.x];
-    if (threadIdx.x == 0) dst[ING_THREADS] = src[ING_THREADS];
+    if (threadIdx.x == 0) dst[TILE_THREADS] = src[TILE_THREADS];
     if (threadIdx.x == 64) sb[ING_FRONT - 1] = tile_base ? slab[tile_base - 1] : (uint8_t)' ';
     __syncthreads();
 }
 
-__global__ __launch_bounds__(ING_THREADS) void k_ing_text_summary(const uint8_t *slab, uint32_t n, uint32_t nsym, uint16_t *flags,
+__global__ __launch_bounds__(TILE_THREADS) void k_ing_text_summary(const uint8_t *slab, uint32_t n, uint32_t nsym, uint16_t *flags,
                                                                  imc::IngestSummary *sums)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[ING_FRONT + ING_TILE + ING_HALO];
-    __shared__ imc::IngestSummary part[ING_THREADS];
-    const uint32_t tile_base = blockIdx.x * (uint32_t)ING_TILE;
+    __shared__ __attribute__((aligned(16))) uint8_t sb[ING_FRONT + TILE_SIZE + ING_HALO];
+    __shared__ imc::IngestSummary part[TILE_THREADS];
+    const uint32_t tile_base = blockIdx.x * (uint32_t)TILE_SIZE;
     ing_stage_tile(slab, tile_base, sb);
-    const uint32_t local = threadIdx.x * (uint32_t)ING_ITEMS;
+    const uint32_t local = threadIdx.x * (uint32_t)TILE_ITEMS;
     imc::IngestSummary s = imc::ingest_identity();
     uint32_t mask = 0;
-    for (int i = 0; i < ING_ITEMS; ++i) {
+    for (int i = 0; i < TILE_ITEMS; ++i) {
         const uint32_t at = tile_base + local + i;
         if (at < n) {
             const uint8_t *p = sb + ING_FRONT + local + i;
@@ -70,72 +67,37 @@ __global__ __launch_bounds__(ING_THREADS) void k_ing_text_summary(const uint8_t 
             s = imc::ingest_combine(s, one);
         }
     }
-    flags[blockIdx.x * (uint32_t)ING_THREADS + threadIdx.x] = (uint16_t)mask;
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < ING_THREADS; d <<= 1) {                // in thread order: the combine is not commutative
-        if ((threadIdx.x & (2 * d - 1)) == 0) part[threadIdx.x] = imc::ingest_combine(part[threadIdx.x], part[threadIdx.x + d]);
-        __syncthreads();
-    }
+    flags[blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x] = (uint16_t)mask;
+    tile_wg_reduce<TILE_THREADS>(s, part, [](const imc::IngestSummary &a, const imc::IngestSummary &b) { return imc::ingest_combine(a, b); });
     if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
 }
 
-// One workgroup.  tile_off[i] = tokens of the slab before tile i; *total = the slab's summary.  Every thread folds
-// ceil(ntiles / ING_SCAN_THREADS) consecutive summaries, the folds are scanned in LDS, and the thread walks its
-// summaries again from its own prefix.
-__global__ __launch_bounds__(ING_SCAN_THREADS) void k_ing_scan(const imc::IngestSummary *sums, uint32_t ntiles, uint32_t *tile_off,
-                                                              imc::IngestSummary *total)
+// One workgroup.  tile_off[i] = tokens of the slab before tile i; *total = the slab's summary.
+__global__ __launch_bounds__(TILE_SCAN_THREADS) void k_ing_scan(const imc::IngestSummary *sums, uint32_t ntiles, uint32_t *tile_off,
+                                                               imc::IngestSummary *total)
 {
-    __shared__ imc::IngestSummary sc[ING_SCAN_THREADS];
-    const uint32_t per = (ntiles + ING_SCAN_THREADS - 1) / ING_SCAN_THREADS;
-    const uint32_t lo = min(threadIdx.x * per, ntiles), hi = min(lo + per, ntiles);
-    imc::IngestSummary acc = imc::ingest_identity();
-    for (uint32_t i = lo; i < hi; ++i) acc = imc::ingest_combine(acc, sums[i]);
-    sc[threadIdx.x] = acc;
-    __syncthreads();
-    for (int d = 1; d < ING_SCAN_THREADS; d <<= 1) {           // inclusive scan in thread order
-        imc::IngestSummary v = sc[threadIdx.x];
-        if ((int)threadIdx.x >= d) v = imc::ingest_combine(sc[threadIdx.x - d], v);
-        __syncthreads();
-        sc[threadIdx.x] = v;
-        __syncthreads();
-    }
-    uint32_t run = threadIdx.x ? sc[threadIdx.x - 1].count : 0u;
-    for (uint32_t i = lo; i < hi; ++i) {
-        tile_off[i] = run;
-        run += sums[i].count;
-    }
-    if (threadIdx.x == ING_SCAN_THREADS - 1) *total = sc[ING_SCAN_THREADS - 1];
+    __shared__ imc::IngestSummary sc[TILE_SCAN_THREADS];
+    const imc::IngestSummary all = tile_scan_elements(
+        ntiles, imc::ingest_identity(), sc, [&](uint32_t i) { return sums[i]; },
+        [](const imc::IngestSummary &a, const imc::IngestSummary &b) { return imc::ingest_combine(a, b); },
+        [&](uint32_t i, const imc::IngestSummary &run) { tile_off[i] = run.count; });   // (of the walk's running summary only count is used)
+    if (threadIdx.x == TILE_SCAN_THREADS - 1) *total = all;
 }
 
 // out points at the slab's first column and has room for out_room symbols (bytes, or 16-bit values when wide).
-__global__ __launch_bounds__(ING_THREADS) void k_ing_text_scatter(const uint8_t *slab, uint32_t n, const uint16_t *flags, const uint32_t *tile_off,
+__global__ __launch_bounds__(TILE_THREADS) void k_ing_text_scatter(const uint8_t *slab, uint32_t n, const uint16_t *flags, const uint32_t *tile_off,
                                                                  uint8_t *out, uint32_t out_room, int wide)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[ING_FRONT + ING_TILE + ING_HALO];
+    __shared__ __attribute__((aligned(16))) uint8_t sb[ING_FRONT + TILE_SIZE + ING_HALO];
     __shared__ uint16_t stage[ING_TILE_TOKENS];
-    __shared__ uint32_t wave_tot[ING_THREADS / 64];
-    const uint32_t tile_base = blockIdx.x * (uint32_t)ING_TILE;
+    __shared__ uint32_t wave_tot[TILE_THREADS / 64];
+    const uint32_t tile_base = blockIdx.x * (uint32_t)TILE_SIZE;
     ing_stage_tile(slab, tile_base, sb);
-    const uint32_t local = threadIdx.x * (uint32_t)ING_ITEMS;
-    const uint32_t mask = flags[blockIdx.x * (uint32_t)ING_THREADS + threadIdx.x];
-    // exclusive scan of the threads' token counts
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t v = __popc(mask);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    if (lane == 63) wave_tot[wave] = v;
-    __syncthreads();
-    uint32_t w = v - __popc(mask), count = 0;
-#pragma unroll
-    for (int j = 0; j < ING_THREADS / 64; ++j) {
-        if (j < wave) w += wave_tot[j];
-        count += wave_tot[j];
-    }
-    for (int i = 0; i < ING_ITEMS; ++i)
+    const uint32_t local = threadIdx.x * (uint32_t)TILE_ITEMS;
+    const uint32_t mask = flags[blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x];
+    uint32_t count;                                             // exclusive scan of the threads' token counts
+    uint32_t w = tile_wg_scan((uint32_t)__popc(mask), 0u, [](uint32_t a, uint32_t b) { return a + b; }, wave_tot, count);
+    for (int i = 0; i < TILE_ITEMS; ++i)
         if ((mask >> i) & 1u) {
             const uint32_t at = tile_base + local + i;
             const imc::TokenRead t = imc::token_read(sb + ING_FRONT + local + i, at < n ? n - at : 0u);
@@ -145,7 +107,7 @@ __global__ __launch_bounds__(ING_THREADS) void k_ing_text_scatter(const uint8_t 
     __syncthreads();
     count = min(count, (uint32_t)ING_TILE_TOKENS);
     const uint32_t first = tile_off[blockIdx.x];
-    for (uint32_t j = threadIdx.x; j < count; j += ING_THREADS) {
+    for (uint32_t j = threadIdx.x; j < count; j += TILE_THREADS) {
         const uint32_t col = first + j;
         if (col < out_room) {
             if (wide) reinterpret_cast<uint16_t *>(out)[col] = stage[j];
@@ -156,9 +118,9 @@ __global__ __launch_bounds__(ING_THREADS) void k_ing_text_scatter(const uint8_t 
 
 // Columns 4 i .. 4 i + 3 of a 2-bit payload of L columns (pk: the slab's packed bytes, dst: the slab's first column, both
 // word aligned).  One word (bytes) or two (16-bit symbols) per thread; columns beyond L are written as zeros.
-__global__ __launch_bounds__(ING_THREADS) void k_ing_unpack2(const uint8_t *pk, uint32_t L, uint8_t *dst, int wide)
+__global__ __launch_bounds__(TILE_THREADS) void k_ing_unpack2(const uint8_t *pk, uint32_t L, uint8_t *dst, int wide)
 {
-    const uint32_t i = blockIdx.x * (uint32_t)ING_THREADS + threadIdx.x;
+    const uint32_t i = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (4 * (uint64_t)i >= L) return;
     uint32_t s[4];
 #pragma unroll
@@ -169,9 +131,9 @@ __global__ __launch_bounds__(ING_THREADS) void k_ing_unpack2(const uint8_t *pk, 
 
 // Columns 4 i .. 4 i + 3 of the pairwise rule on a[0..L) and b[0..L) (a, b and dst word aligned); columns beyond L are
 // written as zeros.
-__global__ __launch_bounds__(ING_THREADS) void k_ing_pairwise(const uint8_t *a, const uint8_t *b, uint32_t L, uint8_t *dst)
+__global__ __launch_bounds__(TILE_THREADS) void k_ing_pairwise(const uint8_t *a, const uint8_t *b, uint32_t L, uint8_t *dst)
 {
-    const uint32_t i = blockIdx.x * (uint32_t)ING_THREADS + threadIdx.x;
+    const uint32_t i = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (4 * (uint64_t)i >= L) return;
     const uint32_t wa = reinterpret_cast<const uint32_t *>(a)[i], wb = reinterpret_cast<const uint32_t *>(b)[i];
     uint32_t word = 0;

@@ -118,6 +118,7 @@ __global__ __launch_bounds__(SMP_SUMMARY_WIDE_THREADS) void k_smp_summary(SmpArg
 }
 
 // enter[j] = the state in which tile j is entered (tile 0: state 0, which its first column forgets)
+// (not tile_scan.hpp's scan: the element is an N-byte map in dynamic LDS, ping-pong buffers, several passes per run)
 __global__ __launch_bounds__(1024) void k_smp_scan(const uint8_t *__restrict__ summ, uint32_t ntiles, int N, uint8_t *__restrict__ enter)
 {
     extern __shared__ __attribute__((aligned(16))) char smp_lds[];

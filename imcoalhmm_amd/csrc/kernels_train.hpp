@@ -26,13 +26,13 @@
 #include "train_tiles.hpp"
 
 constexpr int TRN_HIST_SUBTILES = 8;                            // encoder tiles per workgroup of k_trn_pair_hist
-constexpr int TRN_HIST_TILE = TRN_HIST_SUBTILES * ENC_TILE;     // 32768 elements: the LDS bins are zeroed and flushed once per workgroup
+constexpr int TRN_HIST_TILE = TRN_HIST_SUBTILES * TILE_SIZE;     // 32768 elements: the LDS bins are zeroed and flushed once per workgroup
 constexpr int TRN_ARGMAX_THREADS = 1024;
 
 // src[src_first + t] -> dst[t] for t < count, without bit 15 (sym_bytes 1: bytes; 2: 16-bit symbols or stream elements)
-__global__ __launch_bounds__(ENC_THREADS) void k_trn_load(const void *src, int sym_bytes, uint32_t src_first, uint32_t count, uint16_t *dst)
+__global__ __launch_bounds__(TILE_THREADS) void k_trn_load(const void *src, int sym_bytes, uint32_t src_first, uint32_t count, uint16_t *dst)
 {
-    const uint32_t t = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t t = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (t >= count) return;
     const uint32_t v = sym_bytes == 1 ? (uint32_t) static_cast<const uint8_t *>(src)[(size_t)src_first + t]
                                       : (uint32_t) static_cast<const uint16_t *>(src)[(size_t)src_first + t];
@@ -42,22 +42,22 @@ __global__ __launch_bounds__(ENC_THREADS) void k_trn_load(const void *src, int s
 // counts[a * A + b] += adjacent pairs (seq[t], seq[t + 1]) = (a, b), t + 1 < n; the pair that straddles a tile edge
 // belongs to the tile of its first element.  counts zeroed by the caller.  LDS: A * A <= kTrnLdsBins.
 template <bool LDS>
-__global__ __launch_bounds__(ENC_THREADS) void k_trn_pair_hist(const uint16_t *seq, uint32_t n, uint32_t A, uint32_t *counts)
+__global__ __launch_bounds__(TILE_THREADS) void k_trn_pair_hist(const uint16_t *seq, uint32_t n, uint32_t A, uint32_t *counts)
 {
     __shared__ uint32_t bins[LDS ? imc::kTrnLdsBins : 1];
     const uint32_t nbins = A * A;
     if (LDS) {
-        for (uint32_t b = threadIdx.x; b < nbins && b < imc::kTrnLdsBins; b += ENC_THREADS) bins[b] = 0;
+        for (uint32_t b = threadIdx.x; b < nbins && b < imc::kTrnLdsBins; b += TILE_THREADS) bins[b] = 0;
         __syncthreads();
     }
     for (int sub = 0; sub < TRN_HIST_SUBTILES; ++sub) {
-        const uint32_t base = (blockIdx.x * (uint32_t)TRN_HIST_SUBTILES + sub) * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
+        const uint32_t base = (blockIdx.x * (uint32_t)TRN_HIST_SUBTILES + sub) * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
         if (base + 1 >= n) continue;                               // (no pair starts here; uniform exit is not needed: no barrier in the loop)
-        uint16_t x[ENC_ITEMS + 1];
+        uint16_t x[TILE_ITEMS + 1];
         enc_load_items(seq, base, x);
         uint32_t run_key = imc::kNoBin, run_n = 0;
 #pragma unroll
-        for (int i = 0; i < ENC_ITEMS; ++i) {
+        for (int i = 0; i < TILE_ITEMS; ++i) {
             const bool valid = base + i + 1 < n && x[i] < A && x[i + 1] < A;
             const uint32_t k = valid ? imc::pair_bin(x[i], x[i + 1], A) : imc::kNoBin;
             if (k == run_key) {
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_trn_pair_hist(const uint16_t *s
     }
     if (LDS) {
         __syncthreads();
-        for (uint32_t b = threadIdx.x; b < nbins && b < imc::kTrnLdsBins; b += ENC_THREADS)
+        for (uint32_t b = threadIdx.x; b < nbins && b < imc::kTrnLdsBins; b += TILE_THREADS)
             if (bins[b]) atomicAdd(&counts[b], bins[b]);
     }
 }
@@ -116,12 +116,12 @@ __global__ __launch_bounds__(TRN_ARGMAX_THREADS) void k_trn_argmax(const uint32_
 
 // keys / counts: `capacity` slots (a power of two >= 2 n), keys filled with kNoKey and counts zeroed by the caller.
 // *overflow is set if a key finds no slot within `capacity` probes (impossible at this load factor; the host checks).
-__global__ __launch_bounds__(ENC_THREADS) void k_trn_pair_count(const uint16_t *seq, uint32_t n, uint32_t capacity, uint32_t *keys, uint32_t *counts,
+__global__ __launch_bounds__(TILE_THREADS) void k_trn_pair_count(const uint16_t *seq, uint32_t n, uint32_t capacity, uint32_t *keys, uint32_t *counts,
                                                                uint32_t *overflow)
 {
-    const uint32_t base = blockIdx.x * (uint32_t)ENC_TILE + threadIdx.x * (uint32_t)ENC_ITEMS;
+    const uint32_t base = blockIdx.x * (uint32_t)TILE_SIZE + threadIdx.x * (uint32_t)TILE_ITEMS;
     if (base + 1 >= n) return;
-    uint16_t x[ENC_ITEMS + 1];
+    uint16_t x[TILE_ITEMS + 1];
     enc_load_items(seq, base, x);
     uint32_t run_key = imc::kNoKey, run_n = 0;
     auto add = [&](uint32_t k, uint32_t c) {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_trn_pair_count(const uint16_t *
         atomicOr(overflow, 1u);
     };
 #pragma unroll
-    for (int i = 0; i < ENC_ITEMS; ++i) {
+    for (int i = 0; i < TILE_ITEMS; ++i) {
         const uint32_t k = base + i + 1 < n ? imc::key_of(x[i], x[i + 1]) : imc::kNoKey;
         if (k == run_key) {
             ++run_n;
@@ -156,10 +156,10 @@ __global__ __launch_bounds__(ENC_THREADS) void k_trn_pair_count(const uint16_t *
 
 // list[i] = (count, key) of every slot with count >= threshold, i < *list_n in arbitrary order; entries beyond
 // list_capacity are counted but not written (the host checks).  *list_n zeroed by the caller.
-__global__ __launch_bounds__(ENC_THREADS) void k_trn_candidates(const uint32_t *keys, const uint32_t *counts, uint32_t capacity, uint32_t threshold,
+__global__ __launch_bounds__(TILE_THREADS) void k_trn_candidates(const uint32_t *keys, const uint32_t *counts, uint32_t capacity, uint32_t threshold,
                                                                uint2 *list, uint32_t list_capacity, uint32_t *list_n)
 {
-    const uint32_t s = blockIdx.x * (uint32_t)ENC_THREADS + threadIdx.x;
+    const uint32_t s = blockIdx.x * (uint32_t)TILE_THREADS + threadIdx.x;
     if (s >= capacity) return;
     const uint32_t k = keys[s], c = counts[s];
     if (k == imc::kNoKey || c < threshold) return;

@@ -15,6 +15,9 @@ imc_set_device_training(1), an untimed imc_set_device(0) first, then one warm-up
     branch   this tree:  the same two (pairwise_forwarders is unchanged: the leg shows the spread between two builds);
              (b) Alignment(path);  (c) Alignment(path).pairs();  pairs() of an open alignment;  (d) one triplet chunk of an
              open alignment
+With --parent-device (a parent that has the device path) the two trees are compared on that path instead: legs parent1
+and branch1, --runs fresh child processes each, interleaved, every child one round of (b) and of pairs() of the open
+alignment; the summary ends with the difference of the medians beside the min .. max spread of the parent's own runs.
 Reported: median [min .. max] over the timed rounds, and the crc32 of the six chunks' deepest token streams, which all legs
 must agree on.  A child that fails ends the run."""
 import argparse
@@ -69,6 +72,12 @@ def child(leg, path, tree, runs):
     def crc_of(fw):
         return ["%08x" % (zlib.crc32(fw[k].new_obs.astype(np.uint16).tobytes()) & 0xffffffff) for k in sorted(fw)]
 
+    if leg.endswith("1"):                                      # --parent-device: one round of the device path alone
+        from imcoalhmm_amd import Alignment
+        aln = timed("b Alignment(path)", lambda: Alignment(path), True)
+        fw = timed("  pairs() of an open alignment", aln.pairs, True)
+        print("RESULT " + json.dumps({"times": times, "crcs": crc_of(fw), "info": aln.info}), flush=True)
+        return
     for run in range(-1, runs):
         keep = run >= 0
         names = list(timed("read_fasta", lambda: prepare.read_fasta(path), keep))
@@ -99,6 +108,7 @@ def child(leg, path, tree, runs):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree")
+    ap.add_argument("--parent-device", action="store_true", help="compare the device path of the two trees (legs parent1, branch1)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--sizes", default="10000000,100000000")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "device_alignment_ab.txt"))
@@ -118,7 +128,7 @@ def main():
         env = dict(os.environ)
         for k in ("IMC_DEVICE_ENCODE", "IMC_DEVICE_INGEST", "IMC_DEVICE_TRAIN", "IMCOAL_FWD_LIB", "IMC_INGEST_SLAB_BYTES"):
             env.pop(k, None)
-        tree = os.path.abspath(args.parent_tree) if leg == "parent" else REPO
+        tree = os.path.abspath(args.parent_tree) if leg.startswith("parent") else REPO
         cmd = ["timeout", "-k", "10", "400", sys.executable, os.path.abspath(__file__), "--child", leg, path, tree, str(args.runs)]
         out = subprocess.run(cmd, capture_output=True, text=True, env=env)
         res = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -127,8 +137,11 @@ def main():
             return None
         return json.loads(res[0][7:])
 
-    say("# device_alignment_ab: per leg and size one child process: a warm-up round, then %d timed rounds; seconds, median [min .. max]" % args.runs)
-    say("# command: python profiles/tools/device_alignment_ab.py --parent-tree DIR --runs %d --sizes %s" % (args.runs, args.sizes))
+    if args.parent_device:
+        say("# device_alignment_ab --parent-device: per leg and size %d fresh child processes, legs interleaved, one round each; seconds, median [min .. max]" % args.runs)
+    else:
+        say("# device_alignment_ab: per leg and size one child process: a warm-up round, then %d timed rounds; seconds, median [min .. max]" % args.runs)
+    say("# command: python profiles/tools/device_alignment_ab.py --parent-tree DIR%s --runs %d --sizes %s" % (" --parent-device" if args.parent_device else "", args.runs, args.sizes))
     say("# parent = the parent commit's package and library; branch = this tree; imc_set_device_encoding(1) and imc_set_device_training(1) in both; default slab size")
     with tempfile.TemporaryDirectory() as data_dir:
         for n in [int(s) for s in args.sizes.split(",") if s]:
@@ -139,6 +152,26 @@ def main():
                 while fh.read(1 << 24):
                     pass
             say("#\n# 4 records x %d bases wrapped at 60: %d bytes, written and read back in %.1f s" % (n, os.path.getsize(path), time.time() - t0))
+            if args.parent_device:
+                rounds = {"parent1": [], "branch1": []}
+                for run in range(args.runs):
+                    for leg in rounds:
+                        r = run_child(leg, path)
+                        if r is None:
+                            return 1
+                        rounds[leg].append(r)
+                        say("run %d  n %-10d %-8s %s   crc32 %s" % (run, n, leg, "  ".join("%s %.3f" % (k.strip(), v[0]) for k, v in r["times"].items()), " ".join(r["crcs"])))
+                same = len({tuple(r["crcs"]) for rs in rounds.values() for r in rs}) == 1
+                say("# n %d: the six chunks' deepest token streams of all legs and runs %s" % (n, "IDENTICAL" if same else "DIFFER"))
+                say("# n %d: Alignment.info %s" % (n, json.dumps(rounds["branch1"][0]["info"], sort_keys=True)))
+                say("# this tree against the parent: difference of medians | spread (max - min) of the parent's own runs")
+                for name in list(rounds["parent1"][0]["times"]) + ["total"]:
+                    ts = {leg: [sum(v[0] for v in r["times"].values()) if name == "total" else r["times"][name][0] for r in rs] for leg, rs in rounds.items()}
+                    for leg in rounds:
+                        say("n %-10d %-8s %-32s %8.3f [%7.3f .. %7.3f]" % (n, leg, name, float(np.median(ts[leg])), min(ts[leg]), max(ts[leg])))
+                    diff, spread = float(np.median(ts["branch1"]) - np.median(ts["parent1"])), max(ts["parent1"]) - min(ts["parent1"])
+                    say("n %-10d branch1 - parent1 %-23s %+8.3f | %7.3f   %s" % (n, name, diff, spread, "inside" if diff <= spread else "OUTSIDE"))
+                continue
             got = {}
             for leg in ("parent", "branch"):
                 got[leg] = run_child(leg, path)

@@ -13,7 +13,9 @@ Workloads (3 symbols, bench.py's generator and seeds):
     pair1e8   two aligned sequences of 1e8 bases -> chunk: prepare.encode_pairwise + Forwarder.from_array against
               Forwarder.from_sequences (the parent and switch0 legs run the first, switch1 the second)
     sweep     text1e8 with the switch on at IMC_INGEST_SLAB_BYTES = 1, 4, 16, 64 and 256 MiB (--sweep-runs per size)
-Legs: parent (the parent commit's package and library), switch0 (this tree, imc_set_device_ingest(0)), switch1 (this
+Legs: parent (the parent commit's package and library; parent1, with --parent-device: the same with its device ingestion,
+for a parent that has one; the summary then ends with switch1 against parent1 per workload: the difference of the medians
+beside the min .. max spread of the parent's own runs), switch0 (this tree, imc_set_device_ingest(0)), switch1 (this
 tree, imc_set_device_ingest(1)); all three with imc_set_device_encoding(1), so that what differs between switch0 and
 switch1 is where the file becomes symbols.  Every measurement is one fresh child process under its own `timeout`; the legs
 are interleaved (parent, switch0, switch1, parent, ...).  The files are written once by this driver, which never touches
@@ -70,12 +72,12 @@ def child(workload, leg, data_dir, tree):
     _capi.check(lib.imc_set_device(0))                         # context creation, untimed
     _capi.check(lib.imc_set_device_encoding(1))
     if leg != "parent":
-        _capi.check(lib.imc_set_device_ingest(1 if leg == "switch1" else 0))
+        _capi.check(lib.imc_set_device_ingest(1 if leg.endswith("1") else 0))
     ext = ".imc" if workload == "cache1e8" else ".ziphmm"
     if workload == "pair1e8":
         s1, s2 = (open(os.path.join(data_dir, "pair_%d.seq" % k), "rb").read() for k in (1, 2))
         t0 = time.perf_counter()
-        if leg == "switch1":
+        if leg.endswith("1"):
             fw = [Forwarder.from_sequences(s1, s2)]
         else:
             obs = np.empty(len(s1), dtype=np.uint8)
@@ -101,6 +103,7 @@ def child(workload, leg, data_dir, tree):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree")
+    ap.add_argument("--parent-device", action="store_true", help="also run the parent with its device ingestion (leg parent1)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--sweep-runs", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "device_ingest_ab.txt"))
@@ -115,6 +118,7 @@ def main():
     import bench
     from imcoalhmm_amd import prepare
     names = [w for w in args.workloads.split(",") if w]
+    legs = ("parent", "parent1", "switch0", "switch1") if args.parent_device else LEGS
     lines = []
 
     def say(text):
@@ -127,7 +131,7 @@ def main():
             env.pop(k, None)
         if slab:
             env["IMC_INGEST_SLAB_BYTES"] = str(slab)
-        tree = os.path.abspath(args.parent_tree) if leg == "parent" else REPO
+        tree = os.path.abspath(args.parent_tree) if leg.startswith("parent") else REPO
         cmd = ["timeout", "-k", "10", str(WORKLOADS[w]["limit"]), sys.executable, os.path.abspath(__file__), "--child", w, leg, data_dir, tree]
         out = subprocess.run(cmd, capture_output=True, text=True, env=env)
         res = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -168,7 +172,7 @@ def main():
         say("# files written and read back in %.0f s (bench.py's generator and seeds; %.0f MB)" % (time.time() - t0, total / 1e6))
         for run in range(args.runs):
             for w in names:
-                for leg in LEGS:
+                for leg in legs:
                     r = run_child(w, leg, data_dir)
                     if r is None:
                         return 1
@@ -185,14 +189,20 @@ def main():
                     say("sweep run %d  slab %4d MiB  create %8.3f s  slabs %3d  crc %08x" % (run, mib, r["create_s"], r["slabs"], r["crc32_first_last"]))
     say("#\n# summary (seconds)")
     for w in names:
-        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"]) for leg in LEGS for r in results[(w, leg)]}
+        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"]) for leg in legs for r in results[(w, leg)]}
         say("# %s: token streams of all legs and runs %s" % (w, "IDENTICAL (alphabet, token total, crc32 of the first and last chunk's deepest stream)"
                                                               if len(same) == 1 else "DIFFER: %r" % sorted(same)))
-        for leg in LEGS:
+        for leg in legs:
             rs = results[(w, leg)]
             say("%-8s %-8s create %s   recompress %s   total %s   (path %s)" % (
                 w, leg, stat([r["create_s"] for r in rs]), stat([r["recompress_s"] for r in rs]), stat([r["create_s"] + r["recompress_s"] for r in rs]),
                 rs[0]["path"]))
+    if args.parent_device:
+        say("#\n# this tree against the parent, device path in both, total seconds: difference of medians | spread (max - min) of the parent's own runs")
+        for w in names:
+            tot = {leg: [r["create_s"] + r["recompress_s"] for r in results[(w, leg)]] for leg in ("switch1", "parent1")}
+            diff, spread = float(np.median(tot["switch1"]) - np.median(tot["parent1"])), max(tot["parent1"]) - min(tot["parent1"])
+            say("%-8s switch1 - parent1 %+8.3f | %7.3f   %s" % (w, diff, spread, "inside" if diff <= spread else "OUTSIDE"))
     if sweep:
         say("#\n# slab size sweep, text1e8 with the switch on (seconds to create)")
         for mib in SWEEP_MIB:

@@ -9,7 +9,8 @@ imports the package from it, so the parent's Python and the parent's library run
 Workloads, generator, seeds and method are those of device_encode_ab.py (one1e8: create 1 x 1e8 columns; c32: create
 32 x 1e7 columns, then recompress; a100: create 100 x 1e6 columns, then recompress; every measurement one fresh child
 process under its own `timeout`, legs interleaved, the device context created untimed, median [min .. max]).
-Legs: parent (the parent commit's package and library), switch0 (this tree, imc_set_device_training(0): the default),
+Legs: parent (the parent commit's package and library; parent1, with --parent-device: the same with its device trainer,
+for a parent that has one; the summary then ends with switch1 against parent1 per workload), switch0 (this tree, imc_set_device_training(0): the default),
 switch1 (this tree, imc_set_device_training(1)); all three with imc_set_device_encoding(1) and imc_set_device_ingest(1),
 so that what differs between switch0 and switch1 is the trainer alone.  Compared across legs and runs: the dictionary
 (alphabet, crc32 of its left / right lists), the token total and the crc32 of the first and last chunk's deepest stream.
@@ -45,7 +46,7 @@ def child(workload, leg, data_dir, tree):
     _capi.check(lib.imc_set_device_encoding(1))
     _capi.check(lib.imc_set_device_ingest(1))
     if leg != "parent":
-        _capi.check(lib.imc_set_device_training(1 if leg == "switch1" else 0))
+        _capi.check(lib.imc_set_device_training(1 if leg.endswith("1") else 0))
     t0 = time.perf_counter()
     fw = [Forwarder.from_array(a, 3) for a in arrays]
     t1 = time.perf_counter()
@@ -66,6 +67,7 @@ def child(workload, leg, data_dir, tree):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree")
+    ap.add_argument("--parent-device", action="store_true", help="also run the parent with its device trainer (leg parent1)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "device_training_ab.txt"))
     ap.add_argument("--workloads", default="one1e8,c32,a100")
@@ -78,6 +80,7 @@ def main():
     sys.path.insert(0, REPO)
     import bench
     names = [w for w in args.workloads.split(",") if w]
+    legs = ("parent", "parent1", "switch0", "switch1") if args.parent_device else LEGS
     lines = []
 
     def say(text):
@@ -96,11 +99,11 @@ def main():
         say("# data generated in %.0f s (bench.py's generator and seeds)" % (time.time() - t0))
         for run in range(args.runs):
             for w in names:
-                for leg in LEGS:
+                for leg in legs:
                     env = dict(os.environ, IMC_DEBUG_HOST="1")
                     for name in ("IMC_DEVICE_ENCODE", "IMC_DEVICE_INGEST", "IMC_DEVICE_TRAIN", "IMCOAL_FWD_LIB"):
                         env.pop(name, None)
-                    tree = os.path.abspath(args.parent_tree) if leg == "parent" else REPO
+                    tree = os.path.abspath(args.parent_tree) if leg.startswith("parent") else REPO
                     cmd = ["timeout", "-k", "10", str(WORKLOADS[w]["limit"]), sys.executable, os.path.abspath(__file__), "--child", w, leg, data_dir, tree]
                     out = subprocess.run(cmd, capture_output=True, text=True, env=env)
                     res = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -109,7 +112,7 @@ def main():
                         return 1
                     r = json.loads(res[0][7:])
                     r["phases"] = phases(out.stderr)
-                    if r["trainer"] != (1 if leg == "switch1" else 0):
+                    if r["trainer"] != (1 if leg.endswith("1") else 0):
                         say("# FAILED: %s %s run %d trained on path %d" % (w, leg, run, r["trainer"]))
                         return 1
                     results.setdefault((w, leg), []).append(r)
@@ -121,11 +124,11 @@ def main():
 
     say("#\n# summary (seconds)")
     for w in names:
-        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"], r["crc32_dictionary"]) for leg in LEGS for r in results[(w, leg)]}
+        same = {(r["alphabet"], r["tokens"], r["crc32_first_last"], r["crc32_dictionary"]) for leg in legs for r in results[(w, leg)]}
         say("# %s: dictionaries and token streams of all legs and runs %s" % (
             w, "IDENTICAL (alphabet, crc32 of the dictionary, token total, crc32 of the first and last chunk's deepest stream)"
             if len(same) == 1 else "DIFFER: %r" % sorted(same)))
-        for leg in LEGS:
+        for leg in legs:
             rs = results[(w, leg)]
             say("%-7s %-8s create %s   recompress %s   total %s" % (
                 w, leg, stat([r["create_s"] for r in rs]), stat([r["recompress_s"] for r in rs]), stat([r["create_s"] + r["recompress_s"] for r in rs])))
@@ -138,6 +141,12 @@ def main():
         tot = {leg: [r["create_s"] + r["recompress_s"] for r in results[(w, leg)]] for leg in ("switch0", "parent")}
         diff, spread = float(np.median(tot["switch0"]) - np.median(tot["parent"])), max(tot["parent"]) - min(tot["parent"])
         say("%-7s switch0 - parent %+8.3f | %7.3f   %s" % (w, diff, spread, "inside" if abs(diff) <= spread else "OUTSIDE"))
+    if args.parent_device:
+        say("#\n# this tree against the parent, device path in both, total seconds: difference of medians | spread (max - min) of the parent's own runs")
+        for w in names:
+            tot = {leg: [r["create_s"] + r["recompress_s"] for r in results[(w, leg)]] for leg in ("switch1", "parent1")}
+            diff, spread = float(np.median(tot["switch1"]) - np.median(tot["parent1"])), max(tot["parent1"]) - min(tot["parent1"])
+            say("%-7s switch1 - parent1 %+8.3f | %7.3f   %s" % (w, diff, spread, "inside" if diff <= spread else "OUTSIDE"))
     with open(args.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return 0

@@ -1,11 +1,12 @@
 // align_tiles_check.cpp - the parallel form of reading a FASTA alignment (csrc/align_tiles.hpp) against the host reader
 // imc::read_fasta (csrc/fasta_io.hpp), on the CPU.  The functions the alignment kernels call are driven here
-// sequentially, the way the device path runs them: the file goes through a buffer of the slab size (aln_slab_cut; what
-// lies behind the cut is carried into the next slab), and per slab the three launches - a summary per tile, folded from
-// single positions with aln_combine (and equal to aln_range over the tile), one scan that gives every tile its entry
-// state and its offsets from the state the slab is entered in, then every tile (in reverse order here: they are
-// independent) walks its bytes from its own entry alone, writes the kept bytes at its own offset and reports its
-// headers; the names come from the slab's bytes (aln_header_name).  The first slab that declines ends the file.
+// sequentially, the way the device path runs them: the file goes through the product's own loop (imc::slab_stream of
+// csrc/slab_stream.hpp: aln_slab_cut, what lies behind the cut is carried into the next slab), and per slab the three
+// launches - a summary per tile, folded from single positions with aln_combine (and equal to aln_range over the tile),
+// one scan that gives every tile its entry state and its offsets from the state the slab is entered in, then every tile
+// (in reverse order here: they are independent) walks its bytes from its own entry alone, writes the kept bytes at its
+// own offset and reports its headers; the names come from the slab's bytes (aln_header_name).  The first slab that
+// declines ends the file.
 //   (a) every string up to length 7 over {'>', 'A', 'c', ' ', '\n', '\r', '\t', 0x80}: one slab at tile sizes 1, 2, 3, 4, 7
 //       and 64, and every two-slab split the slab rule allows (first slab of 1 .. n - 1 bytes) at tile size 3
 //   (b) a few hundred random longer files that conform to what the device parser takes (wrapped and unwrapped lines, "\n"
@@ -17,6 +18,7 @@
 //       reference's rule on all triples over "ACGTacgtNn-" and on every byte in each position; aln_gather / aln_symbols
 //       against both encoders at every start residue and lengths around 16, from a buffer that ends where a device buffer
 //       ends.
+//   (d) the split of a one-workgroup scan among its threads (imc::scan_share) and the fold / scan / walk over it.
 // Built with -fsanitize=address,undefined.
 #include <algorithm>
 #include <cctype>
@@ -29,6 +31,7 @@
 
 #include "../imcoalhmm_amd/csrc/align_tiles.hpp"
 #include "../imcoalhmm_amd/csrc/obs_io.hpp"
+#include "../imcoalhmm_amd/csrc/slab_stream.hpp"
 
 static long g_compared = 0, g_declined = 0, g_conforming = 0;
 
@@ -94,7 +97,9 @@ static std::vector<imc::AlnSummary> t_sums, g_position;     // g_position[i]: th
 static std::vector<uint32_t> t_state, t_seq, t_hdr;
 static bool g_scatter_declined = false;                     // run the scatter of a slab that declines as well (the device does)
 
-// first_slab: bytes the first buffer holds (0: the whole file in one slab)
+// first_slab: bytes the first read delivers (0: the whole file in one slab); the second read delivers the rest.  The loop
+// is the product's (imc::slab_stream) over two buffers of the file's size, with the three launches as its "queue" and the
+// verdict and the names as its "judge".
 static void tiled_parse(const Bytes &data, size_t first_slab, size_t tile, Parsed &out)
 {
     out.declined = out.slab_declined = false;
@@ -104,85 +109,97 @@ static void tiled_parse(const Bytes &data, size_t first_slab, size_t tile, Parse
     uint32_t state = imc::kAlnStart0;
     uint8_t prev = '\n';
     uint64_t kept = 0;
-    static Bytes buf;                                        // scratch, kept between calls
+    static Bytes slabs[2];                                   // scratch, kept between calls
     static std::vector<imc::AlnRecord> table;
-    buf.clear();
-    size_t pos = 0, base = 0;                                // base: where buf[0] stands in the file
-    for (int round = 0;; ++round) {
-        const size_t want = round == 0 && first_slab ? first_slab : data.size();   // (the second buffer takes the rest)
-        const size_t take = std::min(want > buf.size() ? want - buf.size() : 0, data.size() - pos);
-        buf.insert(buf.end(), data.begin() + (long)pos, data.begin() + (long)(pos + take));
-        pos += take;
-        const bool at_eof = pos == data.size();
-        const size_t cut = imc::aln_slab_cut(buf.data(), buf.size(), at_eof, state);
-        if (cut == 0 && !at_eof) { out.declined = out.slab_declined = true; return; }
-        if (cut == 0) break;
-        const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + tile - 1) / tile);
-        CHECK(prev == (base ? data[base - 1] : '\n'));        // a byte's summary is the same in every tiling
-        // launch 1: tile summaries, from single positions
-        if (t_sums.size() < tiles) { t_sums.resize(tiles); t_state.resize(tiles); t_seq.resize(tiles); t_hdr.resize(tiles); }
-        for (uint32_t t = 0; t < tiles; ++t) {
-            const uint32_t lo = t * (uint32_t)tile, hi = std::min<uint32_t>(lo + (uint32_t)tile, n);
-            imc::AlnSummary s = imc::aln_identity();
-            for (uint32_t i = lo; i < hi; ++i) s = imc::aln_combine(s, g_position[base + i]);
-            if (first_slab == 0 || g_scatter_declined) {             // what a thread computes for its bytes at once
-                const imc::AlnSummary whole = imc::aln_range(buf.data() + lo, lo ? buf[lo - 1] : prev, hi - lo);
-                CHECK(std::memcmp(&s, &whole, sizeof s) == 0);
-            }
-            t_sums[t] = s;
-        }
-        // launch 2: the scan - maps first, then the counts in the resolved states
-        uint32_t map = imc::kAlnIdentityMap;
-        imc::AlnTotal total{state, 0, 0, 0};
-        imc::AlnSummary all = imc::aln_identity();
-        for (uint32_t t = 0; t < tiles; ++t) {
-            const uint32_t in = imc::aln_exit(map, state);
-            CHECK(in == total.exit);
-            t_state[t] = in; t_seq[t] = total.seq; t_hdr[t] = total.hdr;
-            total.seq += t_sums[t].seq[in];
-            total.hdr += t_sums[t].hdr[in];
-            total.decline |= imc::aln_declines(t_sums[t].map, in);
-            total.exit = imc::aln_exit(t_sums[t].map, in);
-            map = imc::aln_compose(map, t_sums[t].map);
-            all = imc::aln_combine(all, t_sums[t]);
-        }
-        const imc::AlnTotal folded = imc::aln_resolve(all, state);
-        CHECK(folded.exit == total.exit && folded.seq == total.seq && folded.hdr == total.hdr && folded.decline == total.decline);
-        // launch 3: the scatter, tiles in reverse order
-        table.assign(total.hdr, imc::AlnRecord{0u, 0u, 0u});
-        for (uint32_t t = total.decline && !g_scatter_declined ? 0 : tiles; t-- > 0;) {
-            const uint32_t lo = t * (uint32_t)tile, hi = std::min<uint32_t>(lo + (uint32_t)tile, n);
-            uint32_t st = t_state[t], at_seq = t_seq[t], at_hdr = t_hdr[t], pre = imc::kAlnIdentityMap;
-            for (uint32_t i = lo; i < hi; ++i) {
-                CHECK(st == imc::aln_exit(pre, t_state[t]));                      // the threads' map scan gives the same state
-                const uint8_t before = i ? buf[i - 1] : prev;
-                const imc::AlnStep step = imc::aln_step(st, before, buf[i]);
-                if (step.cls == imc::kAlnKept) {
-                    CHECK(kept + at_seq < out.bases.size());
-                    out.bases[kept + at_seq++] = buf[i];
-                } else if (step.cls == imc::kAlnHeaderStart) {
-                    CHECK(at_hdr < table.size());
-                    table[at_hdr++] = imc::AlnRecord{i, 0u, kept + at_seq};
+    const size_t slab = std::max<size_t>(data.size(), 1);
+    for (Bytes &b : slabs) b.assign(slab, 0);
+    uint8_t *const host[2] = {slabs[0].data(), slabs[1].data()};
+    size_t pos = 0, base = 0;                                // base: where the slab's first byte stands in the file
+    bool between_slabs = true;                               // false while a slab is judged: a decline is then the verdict's, else the cut's
+    imc::AlnTotal total{state, 0, 0, 0};
+    const int end = imc::slab_stream(
+        host, slab,
+        [&](uint8_t *dst, size_t want, bool &eof) {
+            const size_t take = std::min(pos == 0 && first_slab ? first_slab : want, data.size() - pos);
+            if (take) std::memcpy(dst, data.data() + pos, take);
+            pos += take;
+            if (pos == data.size()) eof = true;
+            return take;
+        },
+        [&](const uint8_t *buf, size_t fill, bool last) { return imc::aln_slab_cut(buf, fill, last, state); },
+        [&](int cur, size_t cut) -> int {
+            const uint8_t *buf = host[cur];
+            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + tile - 1) / tile);
+            CHECK(prev == (base ? data[base - 1] : '\n'));        // a byte's summary is the same in every tiling
+            // launch 1: tile summaries, from single positions
+            if (t_sums.size() < tiles) { t_sums.resize(tiles); t_state.resize(tiles); t_seq.resize(tiles); t_hdr.resize(tiles); }
+            for (uint32_t t = 0; t < tiles; ++t) {
+                const uint32_t lo = t * (uint32_t)tile, hi = std::min<uint32_t>(lo + (uint32_t)tile, n);
+                imc::AlnSummary s = imc::aln_identity();
+                for (uint32_t i = lo; i < hi; ++i) s = imc::aln_combine(s, g_position[base + i]);
+                if (first_slab == 0 || g_scatter_declined) {             // what a thread computes for its bytes at once
+                    const imc::AlnSummary whole = imc::aln_range(buf + lo, lo ? buf[lo - 1] : prev, hi - lo);
+                    CHECK(std::memcmp(&s, &whole, sizeof s) == 0);
                 }
-                st = step.next;
-                pre = imc::aln_compose(pre, g_position[base + i].map);
+                t_sums[t] = s;
             }
-            CHECK(at_seq == t_seq[t] + t_sums[t].seq[t_state[t]] && at_hdr == t_hdr[t] + t_sums[t].hdr[t_state[t]]);
-        }
-        if (total.decline || out.names.size() + total.hdr > imc::kMaxAlnRecords) { out.declined = true; return; }
-        for (const imc::AlnRecord &r : table) {
-            const std::string name = imc::aln_header_name(buf.data(), cut, r.slab_offset);
-            if (name.empty()) { out.declined = true; return; }
-            out.names.push_back(name);
-            out.start.push_back(r.start);
-        }
-        kept += total.seq;
-        state = total.exit;
-        prev = buf[cut - 1];
-        buf.erase(buf.begin(), buf.begin() + (long)cut);
-        base += cut;
-        if (at_eof) break;
-    }
+            // launch 2: the scan - maps first, then the counts in the resolved states
+            uint32_t map = imc::kAlnIdentityMap;
+            total = imc::AlnTotal{state, 0, 0, 0};
+            imc::AlnSummary all = imc::aln_identity();
+            for (uint32_t t = 0; t < tiles; ++t) {
+                const uint32_t in = imc::aln_exit(map, state);
+                CHECK(in == total.exit);
+                t_state[t] = in; t_seq[t] = total.seq; t_hdr[t] = total.hdr;
+                total.seq += t_sums[t].seq[in];
+                total.hdr += t_sums[t].hdr[in];
+                total.decline |= imc::aln_declines(t_sums[t].map, in);
+                total.exit = imc::aln_exit(t_sums[t].map, in);
+                map = imc::aln_compose(map, t_sums[t].map);
+                all = imc::aln_combine(all, t_sums[t]);
+            }
+            const imc::AlnTotal folded = imc::aln_resolve(all, state);
+            CHECK(folded.exit == total.exit && folded.seq == total.seq && folded.hdr == total.hdr && folded.decline == total.decline);
+            // launch 3: the scatter, tiles in reverse order
+            table.assign(total.hdr, imc::AlnRecord{0u, 0u, 0u});
+            for (uint32_t t = total.decline && !g_scatter_declined ? 0 : tiles; t-- > 0;) {
+                const uint32_t lo = t * (uint32_t)tile, hi = std::min<uint32_t>(lo + (uint32_t)tile, n);
+                uint32_t st = t_state[t], at_seq = t_seq[t], at_hdr = t_hdr[t], pre = imc::kAlnIdentityMap;
+                for (uint32_t i = lo; i < hi; ++i) {
+                    CHECK(st == imc::aln_exit(pre, t_state[t]));                      // the threads' map scan gives the same state
+                    const uint8_t before = i ? buf[i - 1] : prev;
+                    const imc::AlnStep step = imc::aln_step(st, before, buf[i]);
+                    if (step.cls == imc::kAlnKept) {
+                        CHECK(kept + at_seq < out.bases.size());
+                        out.bases[kept + at_seq++] = buf[i];
+                    } else if (step.cls == imc::kAlnHeaderStart) {
+                        CHECK(at_hdr < table.size());
+                        table[at_hdr++] = imc::AlnRecord{i, 0u, kept + at_seq};
+                    }
+                    st = step.next;
+                    pre = imc::aln_compose(pre, g_position[base + i].map);
+                }
+                CHECK(at_seq == t_seq[t] + t_sums[t].seq[t_state[t]] && at_hdr == t_hdr[t] + t_sums[t].hdr[t_state[t]]);
+            }
+            return 0;
+        },
+        [&](int cur, size_t cut) -> int {
+            between_slabs = false;
+            if (total.decline || out.names.size() + total.hdr > imc::kMaxAlnRecords) return imc::kSlabDeclined;
+            for (const imc::AlnRecord &r : table) {
+                const std::string name = imc::aln_header_name(host[cur], cut, r.slab_offset);
+                if (name.empty()) return imc::kSlabDeclined;
+                out.names.push_back(name);
+                out.start.push_back(r.start);
+            }
+            kept += total.seq;
+            state = total.exit;
+            prev = host[cur][cut - 1];
+            base += cut;
+            between_slabs = true;
+            return 0;
+        });
+    if (end == imc::kSlabDeclined) { out.declined = true; out.slab_declined = between_slabs; return; }
     if (std::set<std::string>(out.names.begin(), out.names.end()).size() != out.names.size()) { out.declined = true; return; }
     out.bases.resize(kept);
 }
@@ -319,6 +336,51 @@ static void check_column_rules()
         }
 }
 
+// ---- (d) the shares of the one-workgroup scan ---------------------------------------------------------------
+// imc::scan_share with 1024 threads: consecutive shares in thread order that cover [0, n) once; and the scan the kernels
+// run over them (tile_scan.hpp: every thread folds its share, the folds are scanned Hillis-Steele, every thread walks its
+// share from its prefix) under map composition, which is not commutative, against the plain left-to-right prefix.
+static void check_scan_shares()
+{
+    const uint32_t threads = 1024;
+    Rng rng(5);
+    std::vector<uint32_t> sizes = {0, 1, 1023, 1024, 1025, 2049};
+    for (uint32_t k = 1; k <= 3; ++k) { sizes.push_back(2050 * k - 1); sizes.push_back(2050 * k + 1); }
+    for (uint32_t n : sizes) {
+        uint32_t next = 0;
+        for (uint32_t t = 0; t < threads; ++t) {
+            const imc::ScanShare own = imc::scan_share(n, threads, t);
+            CHECK(own.lo == next && own.hi >= own.lo && own.hi <= n);
+            CHECK(own.hi - own.lo <= (n + threads - 1) / threads);
+            CHECK(own.hi > own.lo || own.lo == n);               // no empty share in front of a non-empty one
+            next = own.hi;
+        }
+        CHECK(next == n);
+        std::vector<uint32_t> maps(n), want(n), got(n, 0xffffffffu), fold(threads), step(threads);
+        for (uint32_t &m : maps) {                               // random maps: an exit state and a decline bit per entry state
+            m = 0;
+            for (uint32_t e = 0; e < imc::kAlnStates; ++e) m |= rng.below(imc::kAlnStates) << (3u * e) | rng.below(2) << (16u + e);
+        }
+        uint32_t run = imc::kAlnIdentityMap;
+        for (uint32_t i = 0; i < n; ++i) { want[i] = run; run = imc::aln_compose(run, maps[i]); }
+        for (uint32_t t = 0; t < threads; ++t) {
+            const imc::ScanShare own = imc::scan_share(n, threads, t);
+            fold[t] = imc::kAlnIdentityMap;
+            for (uint32_t i = own.lo; i < own.hi; ++i) fold[t] = imc::aln_compose(fold[t], maps[i]);
+        }
+        for (uint32_t d = 1; d < threads; d <<= 1) {
+            for (uint32_t t = 0; t < threads; ++t) step[t] = t >= d ? imc::aln_compose(fold[t - d], fold[t]) : fold[t];
+            fold.swap(step);
+        }
+        for (uint32_t t = 0; t < threads; ++t) {
+            const imc::ScanShare own = imc::scan_share(n, threads, t);
+            uint32_t before = t ? fold[t - 1] : imc::kAlnIdentityMap;
+            for (uint32_t i = own.lo; i < own.hi; ++i) { got[i] = before; before = imc::aln_compose(before, maps[i]); }
+        }
+        CHECK(got == want && fold[threads - 1] == run);
+    }
+}
+
 int main()
 {
     // (a) every short string
@@ -357,6 +419,7 @@ int main()
     CHECK(imc::aln_slab_cut(two, 2, false, imc::kAlnSeq) == 2);          // ... is a '>' inside a sequence line when entered in one
     CHECK(imc::aln_slab_cut(two, 10, true, imc::kAlnStart0) == 10);
     check_column_rules();
+    check_scan_shares();
     std::printf("align_tiles ok: %ld parses compared, %ld declined, %ld conforming files\n", g_compared, g_declined, g_conforming);
     return 0;
 }

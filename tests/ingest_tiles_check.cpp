@@ -1,10 +1,10 @@
 // ingest_tiles_check.cpp - the parallel form of observation ingestion (csrc/ingest_tiles.hpp) against the host loops of
 // csrc/obs_io.hpp, on the CPU.  The functions the ingestion kernels call are driven here sequentially, the way the device
-// path runs them: the file goes through a buffer of the slab size (slab_cut; what lies behind the cut is carried into the
-// next slab), and per slab the three launches - a summary per tile (folded from ingest_position) with the token-start
-// flags, one scan over the tile summaries for output offsets and the slab's summary, then every tile (in reverse order
-// here: they are independent) writes its tokens' values from its own offset alone.  The first slab whose verdict is not
-// "ok" ends the file, as on the device.
+// path runs them: the file goes through the product's own loop (imc::slab_stream of csrc/slab_stream.hpp: two buffers of
+// the slab size, slab_cut, what lies behind the cut is carried into the next slab), and per slab the three launches - a
+// summary per tile (folded from ingest_position) with the token-start flags, one scan over the tile summaries for output
+// offsets and the slab's summary, then every tile (in reverse order here: they are independent) writes its tokens' values
+// from its own offset alone.  The first slab whose verdict is not "ok" ends the file, as on the device.
 //   (a) every string up to length 7 over {'0','1','7',' ','\n','x'} at nsym 3 and 20
 //   (b) random longer strings: 1-3-digit tokens, leading zeros, whitespace runs of all six whitespace bytes, bad bytes,
 //       tokens of 16 digits (accepted) and of 17 and more (declined)
@@ -21,6 +21,7 @@
 
 #include "../imcoalhmm_amd/csrc/ingest_tiles.hpp"
 #include "../imcoalhmm_amd/csrc/obs_io.hpp"
+#include "../imcoalhmm_amd/csrc/slab_stream.hpp"
 
 static long g_compared = 0, g_declined = 0;
 
@@ -62,70 +63,74 @@ static void host_parse(const std::vector<uint8_t> &data, int nsym, Parsed &out)
 }
 
 // scratch of tiled_parse, kept between calls
-static std::vector<uint8_t> t_buf, t_flag;
+static std::vector<uint8_t> t_buf[2], t_flag;
 static std::vector<imc::IngestSummary> t_sums;
 static std::vector<uint32_t> t_off;
 
+// The product's loop (imc::slab_stream) over two buffers of the slab size, with the three launches as its "queue" and the
+// verdict as its "judge".
 static void tiled_parse(const std::vector<uint8_t> &data, size_t slab, size_t tile, uint32_t nsym, Parsed &out)
 {
     out.code = 0;
     out.msg.clear();
     out.sym.clear();
-    t_buf.assign(slab, 0);
-    size_t fill = 0, pos = 0;
+    for (auto &b : t_buf) b.assign(slab, 0);
+    uint8_t *const host[2] = {t_buf[0].data(), t_buf[1].data()};
+    size_t pos = 0;
     uint64_t cols = 0;
-    for (;;) {
-        const size_t take = std::min(slab - fill, data.size() - pos);
-        if (take) std::memcpy(t_buf.data() + fill, data.data() + pos, take);
-        pos += take;
-        fill += take;
-        const bool at_eof = pos == data.size();
-        const size_t cut = imc::slab_cut(t_buf.data(), fill, at_eof);
-        if (cut == 0) {
-            if (at_eof) return;
-            out.code = 1;                                   // a slab without whitespace
-            return;
-        }
-        const uint32_t n = (uint32_t)cut;
-        const uint8_t *b = t_buf.data();
-        const size_t ntiles = (n + tile - 1) / tile;
-        // launch 1: flags and tile summaries
-        t_flag.assign(n, 0);
-        t_sums.assign(ntiles, imc::ingest_identity());
-        for (size_t k = 0; k < ntiles; ++k) {
-            imc::IngestSummary s = imc::ingest_identity();
-            for (uint32_t i = (uint32_t)(k * tile); i < std::min<size_t>(n, (k + 1) * tile); ++i) {
-                const uint8_t prev = i ? b[i - 1] : (uint8_t)' ';
-                t_flag[i] = imc::token_start(prev, b[i]);
-                s = imc::ingest_combine(s, imc::ingest_position(b + i, prev, i, n, nsym));
+    imc::IngestSummary all = imc::ingest_identity();
+    out.code = imc::slab_stream(
+        host, slab,
+        [&](uint8_t *dst, size_t want, bool &eof) {
+            const size_t take = std::min(want, data.size() - pos);
+            if (take) std::memcpy(dst, data.data() + pos, take);
+            pos += take;
+            if (pos == data.size()) eof = true;
+            return take;
+        },
+        [](const uint8_t *buf, size_t fill, bool last) { return imc::slab_cut(buf, fill, last); },      // 0 before the end: a slab without whitespace
+        [&](int cur, size_t cut) -> int {
+            const uint32_t n = (uint32_t)cut;
+            const uint8_t *b = host[cur];
+            const size_t ntiles = (n + tile - 1) / tile;
+            // launch 1: flags and tile summaries
+            t_flag.assign(n, 0);
+            t_sums.assign(ntiles, imc::ingest_identity());
+            for (size_t k = 0; k < ntiles; ++k) {
+                imc::IngestSummary s = imc::ingest_identity();
+                for (uint32_t i = (uint32_t)(k * tile); i < std::min<size_t>(n, (k + 1) * tile); ++i) {
+                    const uint8_t prev = i ? b[i - 1] : (uint8_t)' ';
+                    t_flag[i] = imc::token_start(prev, b[i]);
+                    s = imc::ingest_combine(s, imc::ingest_position(b + i, prev, i, n, nsym));
+                }
+                t_sums[k] = s;
             }
-            t_sums[k] = s;
-        }
-        // launch 2: offsets and the slab's summary
-        t_off.assign(ntiles, 0);
-        imc::IngestSummary all = imc::ingest_identity();
-        for (size_t k = 0; k < ntiles; ++k) {
-            t_off[k] = all.count;
-            all = imc::ingest_combine(all, t_sums[k]);
-        }
-        const imc::IngestVerdict v = imc::ingest_verdict(all, n);
-        if (v.kind == imc::kIngestDeclined) { out.code = 1; return; }
-        if (v.kind == imc::kIngestBadByte) { out.code = -5; out.msg = std::string("unexpected character in ") + kPath; return; }
-        if (v.kind == imc::kIngestSymbol) { out.code = -2; out.msg = imc::symbol_error_text(v.value, cols + v.column, v.at_end); return; }
-        CHECK(cols + all.count <= imc::max_tokens_in(data.size()));
-        // launch 3: every tile writes its tokens from its own offset
-        out.sym.resize(cols + all.count, 0xffff);
-        for (size_t k = ntiles; k-- > 0;) {
-            uint32_t w = t_off[k];
-            for (uint32_t i = (uint32_t)(k * tile); i < std::min<size_t>(n, (k + 1) * tile); ++i)
-                if (t_flag[i]) out.sym[cols + w++] = (uint16_t)imc::token_read(b + i, n - i).value;
-            CHECK(w == t_off[k] + t_sums[k].count);
-        }
-        cols += all.count;
-        std::memmove(t_buf.data(), t_buf.data() + cut, fill - cut);
-        fill -= cut;
-        if (at_eof) return;
-    }
+            // launch 2: offsets and the slab's summary
+            t_off.assign(ntiles, 0);
+            all = imc::ingest_identity();
+            for (size_t k = 0; k < ntiles; ++k) {
+                t_off[k] = all.count;
+                all = imc::ingest_combine(all, t_sums[k]);
+            }
+            CHECK(cols + all.count <= imc::max_tokens_in(data.size()));
+            // launch 3: every tile writes its tokens from its own offset (whatever the verdict will be, as on the device)
+            out.sym.resize(cols + all.count, 0xffff);
+            for (size_t k = ntiles; k-- > 0;) {
+                uint32_t w = t_off[k];
+                for (uint32_t i = (uint32_t)(k * tile); i < std::min<size_t>(n, (k + 1) * tile); ++i)
+                    if (t_flag[i]) out.sym[cols + w++] = (uint16_t)imc::token_read(b + i, n - i).value;
+                CHECK(w == t_off[k] + t_sums[k].count);
+            }
+            return 0;
+        },
+        [&](int, size_t cut) -> int {
+            const imc::IngestVerdict v = imc::ingest_verdict(all, (uint32_t)cut);
+            if (v.kind == imc::kIngestDeclined) return imc::kSlabDeclined;
+            if (v.kind == imc::kIngestBadByte) { out.msg = std::string("unexpected character in ") + kPath; return -5; }
+            if (v.kind == imc::kIngestSymbol) { out.msg = imc::symbol_error_text(v.value, cols + v.column, v.at_end); return -2; }
+            cols += all.count;
+            return 0;
+        });
 }
 
 static size_t longest_digit_run(const std::vector<uint8_t> &d)

@@ -121,6 +121,16 @@ def test_device_parse_is_read_fasta(tmp_path, name, slab):
     assert_parsed(path, slab, "device").close()
 
 
+def test_device_parse_with_several_tiles_per_scan_thread(tmp_path):
+    """12 MB in two slabs: the first is cut at its last line end (2049 tiles, the last one short), so each of the threads
+    0 .. 682 of k_aln_scan owns three consecutive tiles, the threads behind them none, and record boundaries fall inside
+    such shares."""
+    data = fasta([(b"s%d" % k, bases(2_950_000, seed=60 + k)) for k in range(4)], wrap=60)
+    aln = assert_parsed(_write(tmp_path, "big.fa", data), 2 * 1024 * 4096 + 4097, "device")
+    assert aln.info["slabs"] == 2 and aln.info["records"] == 4
+    aln.close()
+
+
 # ---- declines fall back, identically -----------------------------------------------------------------------------
 def _spoiled(at, byte):
     data = bytearray(fasta(_three(3000), wrap=60))

@@ -1,6 +1,7 @@
 """The device encoder (csrc/kernels_encode.hpp) against the host encoder (imc::encode_levels) on the GPU: the same tokens,
 token counts and lengths at every level of the dictionary, exactly - across tile boundaries (4096 elements), for runs far
-longer than a tile, for byte merges, 16-bit rounds and 16-bit raw streams - and the entry points built on it:
+longer than a tile and than the 1024 tiles one thread each of the scan takes, for byte merges, 16-bit rounds and 16-bit
+raw streams - and the entry points built on it:
 Forwarder.from_device, imc_obs_token_counts, the batched imc_obs_recompress.  The oracle of the token comparisons is the
 host encoder itself; log-likelihoods are additionally held to the CPU oracle at the suite's 1e-11."""
 import os
@@ -64,6 +65,19 @@ def test_same_tokens_three_symbols(kind):
         a, b = host_and_device(obs, 3)
         assert a.compressed_length(16384)[1] == alpha, (kind, n)          # the chunks did go through the whole dictionary
         assert_same_chunk(a, b, (kind, n))
+
+
+SCAN_SHARES_N = 2 * 1024 * 4096 + 4097       # 2050 tiles: three per thread of the one-workgroup scan, a ragged last share, idle threads behind it
+
+
+@pytest.mark.parametrize("kind", ["compressible", "zeros"])
+def test_same_tokens_several_tiles_per_scan_thread(kind):
+    """Beyond 1024 tiles a thread of k_enc_scan owns several consecutive tiles; with zeros the carry crosses every tile
+    and every share boundary."""
+    _, alpha = _dictionary(3)
+    a, b = host_and_device(content(kind, SCAN_SHARES_N), 3)
+    assert a.compressed_length(16384)[1] == alpha
+    assert_same_chunk(a, b, (kind, SCAN_SHARES_N))
 
 
 @pytest.mark.parametrize("nsym", [65, 257])
@@ -137,6 +151,29 @@ def test_recompress_batched_on_the_device():
     for k in (2, 3):
         assert fw1[k].compressed_length(16384) == (arrays[k].size, 3)     # the two short chunks are still raw
     assert fw1[0].compressed_length(16384)[0] < 40_000 // 4
+
+
+def test_recompress_batched_several_tiles_per_scan_thread():
+    """Three chunks in one run of passes, 2052 tiles at the start: the chunk-start scan (k_enc_mark_*) and the passes'
+    scan both give a thread several tiles."""
+    L = _capi.lib()
+    arrays = [compressible(n, seed=60 + k) for k, n in enumerate((4_200_000, 4096, 4_200_000))]
+    seen = []
+    try:
+        for switch in (0, 1):
+            _capi.check(L.imc_dictionary_reset())
+            _state.clear()
+            set_device_encoding(switch)
+            fw = [Forwarder.from_array(a, 3) for a in arrays]
+            recompress(fw)
+            seen.append(fw)
+    finally:
+        set_device_encoding(0)
+        _capi.check(L.imc_dictionary_reset())
+    for k, (a, b) in enumerate(zip(*seen)):
+        assert a.sym2pair == b.sym2pair and len(a.sym2pair) > 8, k
+        assert_same_chunk(a, b, ("recompress", k))
+    assert seen[1][0].compressed_length(16384)[0] < 4_200_000 // 4
 
 
 GUARD_SCRIPT = textwrap.dedent('''

@@ -161,6 +161,33 @@ def test_errors_are_the_host_parsers(tmp_path):
     assert_same_error(_write(tmp_path, "wide.ziphmm", b"256 0 257 1"), 257, None, E_SYM)
 
 
+# The slab is cut behind its last whitespace byte, at 8 392 704 bytes here: 2049 tiles, three for each of the threads 0 .. 682
+# of the one-workgroup scan, idle threads behind them.
+SCAN_SHARES_SLAB = 2 * 1024 * 4096 + 4097
+
+
+def test_a_slab_of_several_tiles_per_scan_thread(tmp_path, dictionary3):
+    """12 MB of text in two slabs: in the first a thread of k_ing_scan owns three consecutive tiles (12288 bytes), in the
+    second one.  Then two faults in different threads' shares of the first slab, in both orders: the first one in file
+    order is reported, as by the host parser."""
+    obs = compressible(6_000_000, seed=77)
+    data = np.stack([obs + ord("0"), np.full(obs.size, ord(" "), dtype=np.uint8)], axis=1).tobytes()     # text_of(obs): digits at even offsets
+    assert data[:8] == text_of(obs[:4])
+    path = _write(tmp_path, "big.ziphmm", data)
+    a, b = assert_same_file(path, 3, SCAN_SHARES_SLAB, "text", obs)
+    assert _capi.last_ingest()["slabs"] == 2
+    assert b.compressed_length(16384)[1] == dictionary3
+    share = 3 * 4096
+    early, late = 100 * share + 5000, 600 * share + 7000                   # digits in the shares of threads 100 and 600 ...
+    assert early < late < SCAN_SHARES_SLAB - 1 and early // share != late // share    # ... both in front of the first slab's cut
+    for first, second, code in ((b"9", b"x", _capi.IMC_ERR_SYMBOL), (b"x", b"9", _capi.IMC_ERR_IO)):
+        bad = bytearray(data)
+        bad[early:early + 1], bad[late:late + 1] = first, second
+        rc, msg, _ = assert_same_error(_write(tmp_path, "bad.ziphmm", bytes(bad)), 3, SCAN_SHARES_SLAB, code)
+        if first == b"9":
+            assert msg == b"symbol 9 at column %d >= nsym" % (early // 2)
+
+
 # ---- cache --------------------------------------------------------------------------------------------------
 def _cache(nsym_file, bits, L, payload):
     return MAGIC + struct.pack("<IIQ", nsym_file, bits, L) + payload
