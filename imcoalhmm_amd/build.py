@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU, so this runs in the build container and the resulting .so
 travels to the GPU box with the repository snapshot.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -10,9 +11,9 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG, "csrc", "imcoal_fwd.hip")
 HDR = os.path.join(os.path.dirname(PKG), "include", "imcoal_fwd.h")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(PKG), "include", "imcoal_model.h"), os.path.join(os.path.dirname(PKG), "include", "imcoal_sample.h")] + [os.path.join(PKG, "csrc", f) for f in
-                     ("kernels_plain.hpp", "kernels_zip.hpp", "kernels_stitch.hpp", "kernels_big.hpp", "kernels_zip2.hpp", "kernels_zip3.hpp", "kernels_zip4.hpp", "pair_dict.hpp", "encode_tiles.hpp", "kernels_encode.hpp", "train_tiles.hpp", "kernels_train.hpp", "ingest_tiles.hpp", "kernels_ingest.hpp", "align_tiles.hpp", "kernels_align.hpp", "tile_scan.hpp", "slab_stream.hpp", "fasta_io.hpp", "plan_host.hpp", "planner_host.hpp", "obs_io.hpp",
-                      "model_host.hpp", "kernels_model.hpp", "sample_tiles.hpp", "kernels_sample.hpp")]
+# Everything the one hipcc command can read: a source that is not here cannot be included (tests/test_build_deps_cpu.py).
+DEPS = sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")) + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) +
+              glob.glob(os.path.join(os.path.dirname(PKG), "include", "*.h")))
 LIB = os.path.join(PKG, "libimcoal_fwd.so")
 
 

@@ -16,12 +16,13 @@
 // (imc::GroupKind) by the host-only planner in planner_host.hpp; the kernel families themselves are described in
 // DESIGN.md section 5.
 //
-// Host side, in the order of this file: context and device memory (dev_alloc, DevBuf); chunks and dictionaries (the
-// pieces a chunk is made of - padded buffers, obs_new, dictionary_for - then the one level loop install_levels with its
-// host and device sources, obs_upload / obs_from_device, the device ingestion of files and sequence pairs, resident
-// alignments, recompress_alphabet; the training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's and the
-// parses ingest_tiles.hpp's and align_tiles.hpp's); the kernel table, the launch plan (Group / Level / Plan own their device buffers)
-// and its builder, one enqueue function per kernel family, the model layer, the C ABI.
+// Host side, in the order of this file (every function stands behind what it calls; the run-time options are
+// options_host.hpp's record): context and device memory (dev_alloc, DevBuf); chunks and dictionaries (padded buffers, obs_new
+// and the owner of a chunk under construction, the level loop install_levels with its host and device sources, the device
+// trainer, dictionary_for, obs_upload / obs_from_device, device ingestion of files and sequence pairs, resident alignments; the
+// training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's, the parses ingest_tiles.hpp's and align_tiles.hpp's);
+// the kernel table, the launch plan (Group / Level / Plan own their device buffers), the plan list with recompress_alphabet
+// behind it, the plan builder, one enqueue function per kernel family, the model layer, the sampler, the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +56,7 @@
 #include "kernels_zip2.hpp"
 #include "kernels_zip3.hpp"
 #include "kernels_zip4.hpp"
+#include "options_host.hpp"
 #include "pair_dict.hpp"
 #include "kernels_encode.hpp"
 #include "kernels_train.hpp"
@@ -101,8 +103,34 @@ using imc::round_up;
 
 constexpr size_t STAGE_KERNEL_MAX_BYTES = 1u << 20;   // parameter sets up to this size are fetched by k_stage_params (enqueue)
 
-hipError_t dev_alloc(void **p, size_t bytes);
-void dev_free(void *p);
+// ---- device memory -----------------------------------------------------------------------------------
+// Every device buffer of the library comes from here.  Normal mode: hipMalloc / hipFree.  Guard mode (IMC_GUARD=1, a
+// test facility): each buffer is its own virtual-memory reservation with NO mapping behind its last 16-byte unit, so
+// a kernel that reads or writes even one vector load past a buffer's declared size faults deterministically instead of
+// silently touching whatever the allocator happened to place next (tests/test_gpu_guard.py runs the create / free /
+// compression-flip / create sequence of round 1's unexplained fault this way).  dev_free stands here, in front of DictDev, whose
+// destructor calls it; dev_alloc reads the context and follows ensure_ctx().
+struct GuardRec { hipDeviceptr_t va; size_t va_size; hipMemGenericAllocationHandle_t handle; hipDeviceptr_t map; size_t map_size; };
+// (never destroyed: the context `g` - whose dictionaries free device buffers in their destructors - outlives every
+// other static at process exit, and dev_free must still find the guard records then; a plain static map is destroyed
+// first and the lookup walked freed nodes: "malloc_consolidate(): invalid chunk size" at exit under IMC_GUARD=1)
+std::map<void *, GuardRec> &g_guard = *new std::map<void *, GuardRec>();
+
+void dev_free(void *p)
+{
+    if (!p) return;
+    auto it = g_guard.find(p);
+    if (it == g_guard.end()) { (void)hipFree(p); return; }
+    (void)hipDeviceSynchronize();
+    (void)hipMemUnmap(it->second.map, it->second.map_size);
+    (void)hipMemRelease(it->second.handle);
+    // The address range is NOT given back (hipMemAddressFree): a freed guard buffer stays unmapped for the rest of the
+    // process, so a use after free faults too - and no later buffer can be mapped at an address some CU may still hold a
+    // translation for.  (Round 3: with the ranges recycled, a Forwarder created right after another had been freed
+    // sometimes evaluated to a wrong value in every plan - 3 of 4 processes, under IMC_GUARD=1 only, never with hipMalloc -
+    // and a later launch faulted at an address nobody had computed; with the ranges kept, neither was seen again.)
+    g_guard.erase(it);
+}
 
 struct DictDev : imc::TrainedDict {                // one trained dictionary (dict, depth, order: pair_dict.hpp) + its device copy
     uint16_t *d_left = nullptr, *d_right = nullptr;
@@ -125,65 +153,17 @@ struct Ctx {
     hipStream_t stream = nullptr;
     int cus = 256;
     uint64_t next_obs_id = 1, next_dict_id = 1;
-    size_t seg_override = 0;
-    int compression = 1;      // 0 = raw symbol stream, 1 = pair-compressed token stream where possible
-    int kernel_pref = 0;      // 0 = automatic, 1 = vector kernels (k_propagate / k_zpropagate), 2 = blocked (k_zpropagate2)
+    imc::Options opt;         // the knobs (options_host.hpp): set by the ABI's setters and by the table of variables
     bool profile = false;
-    bool rank1_handoff = true; // IMC_RANK1=0 switches the rank-one hand-off of the GEMM chain off (A/B measurements)
-    int blocked_variant = 4;  // register-blocked kernel: 4 = fp64 MFMA 4x4x4 with the hybrid LDS/L2 table where it pays
-                              // (k_zpropagate4) and the LDS table otherwise (k_zpropagate3); 3 = LDS table only;
-                              // 5 = hybrid wherever it is possible (tests); 2 = k_zpropagate2 (DPP, VALU).
-                              // IMC_BLOCKED=2|3|4|5 at start-up
-    int wide_blocked = -1;    // 25-32 states on the blocked MFMA scan (k_zpropagate4<7 | 8>, four wavefronts per workgroup, streamed
-                              // table) instead of the vector / GEMM-chain kernels: -1 = where the cost model prefers it, 0 = never,
-                              // 1 = wherever every dictionary of the call has a token level the scan can run (IMC_WIDE_BLOCKED).
-                              // Automatic mode only (imc_set_compression(1)): the pinned modes keep their kernels.
-    int z4_stream = -1;       // k_zpropagate4's table: -1 = streamed (nothing cached in LDS) while the launch's tables are
-                              // cache resident, 0 = always the hybrid LDS cache, 1 = always streamed (IMC_Z4_STREAM)
-    bool table_pairs = true;  // IMC_TABLE_PAIRS=0: k_zpropagate4's table one dictionary depth per launch (A/B measurements)
-    int table_triples = -1;   // three dictionary depths per table launch, one wavefront per token (k_z4_level3): -1 = up to 12 states
-                              // (measured at 10 states: 106 vs 108 us and 113.5 vs 116 us per evaluation; at 20 states 54 vs 52.5 us for
-                              // the table - 2197 wavefronts of 125 MFMAs in the depth 7-9 launch - so pairs stay; again with the column-split
-                              // pairs: 253.3 / 256.4 vs 258.8 / 260.2 us per evaluation, profiles/table_split_sweep.txt), 0 = never, 1 = always
-                              // (IMC_TABLE_TRIPLES)
-    bool table_split = true;  // IMC_TABLE_SPLIT=0: every two-depth table launch in the four-tokens-per-wavefront form (A/B measurements).
-                              // Otherwise a launch takes the column-split form (one token per wavefront, k_z4_level2<., ., W>) while it is
-                              // latency: entries x parameter sets <= table_split_max, about one wavefront per SIMD.  Beyond that the build
-                              // is throughput and the four-tokens form issues 1.6x fewer matrix instructions (at 20 states) in 4x fewer wavefronts.
-    int table_split_max = -1; // -1: four per compute unit (IMC_TABLE_SPLIT_MAX)
-    bool xcd_affine = true;   // k_zpropagate4: a parameter set's workgroups all on one XCD when B is 2, 4 or a multiple of 8 (IMC_XCD_AFFINE=0: off)
-    int fuse_tail = 1;        // the chunk's last workgroup finishes the chunk (zip3_tail) instead of k_chain launches: 1 = where a chunk is
-                              // at most four workgroups (one in-wavefront fold; measured: 100 x 1e6 columns -1.5 us, and +6 us at 13
-                              // workgroups of 20 states, where the chain's twenty parallel wavefronts win), 2 = wherever possible, 0 = never (IMC_FUSE_TAIL)
-    bool chain_lds = false;   // IMC_CHAIN_LDS=1: k_chain's step hands its vector round through LDS, not lane to lane (A/B measurements)
-    bool fuse_head = true;    // IMC_FUSE_HEAD=0: k_stage_params + k_z4_raw as launches of their own (A/B measurements)
-    bool pack_table = true;   // IMC_PACK_TABLE=0: the mat-vec chain reads the padded table (A/B measurements)
-    int device_encode = -1;   // token streams of new / recompressed chunks: 0 = encoded on the host (imc::encode_levels), 1 = on the
-                              // device from the symbols already there (kernels_encode.hpp; the same tokens).  -1: not set yet -
-                              // IMC_DEVICE_ENCODE at start-up, else 0 (imc_set_device_encoding)
-    bool guard = false;       // IMC_GUARD=1: every device buffer ends flush against an unmapped guard range (dev_alloc)
-    bool use_graphs = false;  // IMC_GRAPH=1: replay each plan's launch sequence as a hipGraph (measured: no gain, the
-                              // per-evaluation latency is kernel time + kernel boundaries, not host launch cost)
     std::vector<Ev3> events;
     std::map<int, std::shared_ptr<DictDev>> dicts;   // by raw alphabet size
     uint64_t last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t last_ingest[4] = {0, 0, 0, 0};      // imc_last_ingest: path, bytes sent to the device, slabs, columns
-    int device_ingest = -1;   // imc_obs_create_from_text: 0 = the host parser (obs_io.hpp), 1 = the file's bytes go to the device
-                              // in slabs and are parsed / unpacked there (kernels_ingest.hpp).  -1: not set yet - IMC_DEVICE_INGEST
-                              // at start-up, else 0 (imc_set_device_ingest)
-    int device_train = -1;    // dictionary training: 0 = imc::train_dictionary on the host, 1 = on the device wherever the sample is
-                              // there (kernels_train.hpp; the same dictionary).  -1: not set yet - IMC_DEVICE_TRAIN at start-up,
-                              // else 0 (imc_set_device_training)
     uint64_t last_training[4] = {0, 0, 0, 0};    // imc_last_training: path, symbols in the sample, byte-phase attempts, 16-bit rounds
     uint64_t r1_checked = 0, r1_collapsed = 0;   // last call: operator segments tested / certified rank one
     std::string last_kernels;   // propagate kernels of the last enqueue, e.g. "k_zpropagate2<5>[tokens]"
     std::vector<const void *> lds_opted;   // kernels of this device that may use LDS_BUDGET bytes of dynamic LDS (allow_lds_budget)
 } g;
-
-void drop_plans();
-void drop_plans_using(imc_obs *const *obs, size_t n);
-void wait_all_idle(std::unique_lock<std::mutex> &lk);
-void model_release();
 
 int ensure_ctx()
 {
@@ -212,46 +192,30 @@ int ensure_ctx()
         return fail(IMC_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     g.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    g.use_graphs = std::getenv("IMC_GRAPH") != nullptr;
-    if (const char *gd = std::getenv("IMC_GUARD")) g.guard = std::atoi(gd) != 0;
-    if (const char *bv = std::getenv("IMC_BLOCKED")) { const int v = std::atoi(bv); if (v >= 2 && v <= 5) g.blocked_variant = v; }
-    if (const char *r1 = std::getenv("IMC_RANK1")) g.rank1_handoff = std::atoi(r1) != 0;
-    if (const char *pt = std::getenv("IMC_PACK_TABLE")) g.pack_table = std::atoi(pt) != 0;
-    if (const char *tp = std::getenv("IMC_TABLE_PAIRS")) g.table_pairs = std::atoi(tp) != 0;
-    if (const char *fh = std::getenv("IMC_FUSE_HEAD")) g.fuse_head = std::atoi(fh) != 0;
-    if (const char *ts = std::getenv("IMC_TABLE_SPLIT")) g.table_split = std::atoi(ts) != 0;
-    if (const char *tm = std::getenv("IMC_TABLE_SPLIT_MAX")) g.table_split_max = std::max(0, std::atoi(tm));
-    if (const char *tt = std::getenv("IMC_TABLE_TRIPLES")) g.table_triples = std::atoi(tt) != 0 ? 1 : 0;
-    if (const char *ft = std::getenv("IMC_FUSE_TAIL")) g.fuse_tail = std::max(0, std::min(2, std::atoi(ft)));
-    if (const char *xa = std::getenv("IMC_XCD_AFFINE")) g.xcd_affine = std::atoi(xa) != 0;
-    if (const char *cl = std::getenv("IMC_CHAIN_LDS")) g.chain_lds = std::atoi(cl) != 0;
-    if (const char *wb = std::getenv("IMC_WIDE_BLOCKED")) { const int v = std::atoi(wb); if (v >= -1 && v <= 1) g.wide_blocked = v; }
-    if (g.device_encode < 0) {
-        const char *de = std::getenv("IMC_DEVICE_ENCODE");
-        g.device_encode = de && std::atoi(de) == 1 ? 1 : 0;
-    }
-    if (const char *zs = std::getenv("IMC_Z4_STREAM")) { const int v = std::atoi(zs); if (v >= -1 && v <= 1) g.z4_stream = v; }
+    imc::read_options(g.opt, imc::ReadAt::Context, imc::process_env);
     g.pid = me;
     g.ready = true;
     return IMC_OK;
 }
 
-// ---- device memory -----------------------------------------------------------------------------------
-// Every device buffer of the library comes from here.  Normal mode: hipMalloc / hipFree.  Guard mode (IMC_GUARD=1, a
-// test facility): each buffer is its own virtual-memory reservation with NO mapping behind its last 16-byte unit, so
-// a kernel that reads or writes even one vector load past a buffer's declared size faults deterministically instead of
-// silently touching whatever the allocator happened to place next (tests/test_gpu_guard.py runs the create / free /
-// compression-flip / create sequence of round 1's unexplained fault this way).
-struct GuardRec { hipDeviceptr_t va; size_t va_size; hipMemGenericAllocationHandle_t handle; hipDeviceptr_t map; size_t map_size; };
-// (never destroyed: the context `g` - whose dictionaries free device buffers in their destructors - outlives every
-// other static at process exit, and dev_free must still find the guard records then; a plain static map is destroyed
-// first and the lookup walked freed nodes: "malloc_consolidate(): invalid chunk size" at exit under IMC_GUARD=1)
-std::map<void *, GuardRec> &g_guard = *new std::map<void *, GuardRec>();
+// A device switch of the record (device_encode, device_ingest, device_train; g_mu held, no device needed): its variable
+// decides until the API has set it.
+int device_mode(int imc::Options::*field) { return imc::device_switch(g.opt, field, imc::process_env); }
 
+// ... and its setter (imc_set_device_encoding / _ingest / _training; takes g_mu): 0 or 1, anything else is `refusal`.
+int set_device_mode(int imc::Options::*field, int mode, const char *refusal)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, refusal);
+    g.opt.*field = mode;
+    return IMC_OK;
+}
+
+// (device memory, continued)
 hipError_t dev_alloc(void **p, size_t bytes)
 {
     bytes = std::max<size_t>(bytes, 16);
-    if (!g.guard) return hipMalloc(p, bytes);
+    if (!g.opt.guard) return hipMalloc(p, bytes);
     hipMemAllocationProp prop{};
     prop.type = hipMemAllocationTypePinned;
     prop.location.type = hipMemLocationTypeDevice;
@@ -280,22 +244,6 @@ hipError_t dev_alloc(void **p, size_t bytes)
     g_guard[user] = r;
     *p = user;
     return hipSuccess;
-}
-
-void dev_free(void *p)
-{
-    if (!p) return;
-    auto it = g_guard.find(p);
-    if (it == g_guard.end()) { (void)hipFree(p); return; }
-    (void)hipDeviceSynchronize();
-    (void)hipMemUnmap(it->second.map, it->second.map_size);
-    (void)hipMemRelease(it->second.handle);
-    // The address range is NOT given back (hipMemAddressFree): a freed guard buffer stays unmapped for the rest of the
-    // process, so a use after free faults too - and no later buffer can be mapped at an address some CU may still hold a
-    // translation for.  (Round 3: with the ranges recycled, a Forwarder created right after another had been freed
-    // sometimes evaluated to a wrong value in every plan - 3 of 4 processes, under IMC_GUARD=1 only, never with hipMalloc -
-    // and a later launch faulted at an address nobody had computed; with the ranges kept, neither was seen again.)
-    g_guard.erase(it);
 }
 
 // One device buffer and its owner: allocated by dev_alloc (so guard mode applies), freed by dev_free when the owner
@@ -428,21 +376,6 @@ struct PhaseTimer {
     static bool enabled() { static const bool on = std::getenv("IMC_DEBUG_HOST") != nullptr; return on; }
 };
 
-// A chunk that holds nothing on the device yet (g_mu held, context ready); null: out of host memory.
-imc_obs *obs_new(size_t L, int nsym)
-{
-    auto *o = new (std::nothrow) imc_obs();
-    if (!o) return nullptr;
-    o->id = g.next_obs_id++;
-    o->pid = g.pid;
-    o->device = g.device;
-    o->nsym = nsym;
-    o->L = L;
-    o->wide_raw = nsym > imc::kByteAlphabet;
-    std::fill(o->alphabet, o->alphabet + imc::kNumLevels, nsym);
-    return o;
-}
-
 void release_tokens(imc_obs *o)          // the chunk falls back to its raw symbols
 {
     for (int l = 0; l < imc::kNumLevels; ++l)
@@ -457,6 +390,53 @@ void obs_release(imc_obs *o)
 {
     dev_free(o->d_sym);
     release_tokens(o);
+}
+
+// One owner for a chunk under construction: whatever the chunk holds on the device goes with it.
+struct ObsDeleter {
+    void operator()(imc_obs *o) const
+    {
+        obs_release(o);
+        delete o;
+    }
+};
+using ObsOwner = std::unique_ptr<imc_obs, ObsDeleter>;
+
+constexpr const char *kHostAllocFailed = "host allocation failed";
+
+// A chunk that holds nothing on the device yet (g_mu held, context ready); null: out of host memory (kHostAllocFailed).
+ObsOwner obs_new(size_t L, int nsym)
+{
+    ObsOwner o(new (std::nothrow) imc_obs());
+    if (!o) return o;
+    o->id = g.next_obs_id++;
+    o->pid = g.pid;
+    o->device = g.device;
+    o->nsym = nsym;
+    o->L = L;
+    o->wide_raw = nsym > imc::kByteAlphabet;
+    std::fill(o->alphabet, o->alphabet + imc::kNumLevels, nsym);
+    return o;
+}
+
+// The end of every creation (g_mu held): the finished chunk goes to the caller; a failed one keeps the first error's
+// text, waits until nothing of it is in flight on g.stream, and is released with its owner.
+int obs_finish(int rc, ObsOwner &o, imc_obs **out)
+{
+    if (rc != IMC_OK) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(g.stream);
+        o.reset();
+        return fail(rc, msg);
+    }
+    *out = o.release();
+    return IMC_OK;
+}
+
+// A chunk holds fewer than 2^31 columns (every creation checks its length before any HIP call).
+int check_columns(uint64_t L)
+{
+    return L >= (uint64_t)1 << 31 ? fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)") : IMC_OK;
 }
 
 // Train a pair dictionary on host symbols; host work only, called without g_mu.  The two experiment variables are read at
@@ -485,16 +465,6 @@ void note_training(uint64_t path, const imc::TrainStats &st)
     g.last_training[0] = path; g.last_training[1] = st.sample; g.last_training[2] = st.attempts; g.last_training[3] = st.rounds;
 }
 
-// The switch of imc_set_device_training (g_mu held; no device needed): IMC_DEVICE_TRAIN decides until it is set.
-int device_train_mode()
-{
-    if (g.device_train < 0) {
-        const char *dt = std::getenv("IMC_DEVICE_TRAIN");
-        g.device_train = dt && std::atoi(dt) == 1 ? 1 : 0;
-    }
-    return g.device_train;
-}
-
 // n symbols (`unit` bytes each: 1, or 2 beyond 256 symbols) in device memory: a chunk's d_sym or its head.  A training
 // sample on the device is the concatenation of such pieces.
 struct TrainPiece {
@@ -502,9 +472,6 @@ struct TrainPiece {
     int unit;
     size_t n;
 };
-
-// The dictionary imc::train_dictionary gives for the concatenated pieces (L symbols), trained on the device (below).
-int device_train(const TrainPiece *pieces, size_t n_pieces, int nsym, size_t L, uint64_t trained_on, std::shared_ptr<DictDev> *out);
 
 // Device copy of a freshly trained dictionary (g_mu held, context ready).
 int upload_dictionary(const std::shared_ptr<DictDev> &nd)
@@ -529,44 +496,6 @@ int publish_dictionary(int nsym, const std::shared_ptr<DictDev> &nd)
 {
     if (int rc = upload_dictionary(nd)) return rc;
     g.dicts[nsym] = nd;
-    return IMC_OK;
-}
-
-// The dictionary a new chunk of L columns is encoded with (the preprocess_raw_observations analogue, hmm.py:16): the
-// one published for its alphabet; else, for the first chunk long enough, one trained now; else none (*dd stays null).
-// Called and left with lk (g_mu) held and the context ready; the lock is released while training runs.  head(&symbols)
-// supplies the training symbols - at least imc::training_head() of the chunk - and is called, under the lock, only when
-// a dictionary has to be trained.  With imc_set_device_training(1) and the chunk's symbols on the device (`dev`, all L
-// of them; else null) the dictionary is trained there instead, with the lock held, and nothing comes back to the host.
-// must_train(): whether a call now would train one.
-bool must_train(size_t L, int nsym)
-{
-    return g.compression && imc::compressible(L, nsym) && g.dicts.find(nsym) == g.dicts.end() && L >= imc::TrainLimits().train_min;
-}
-
-template <class Head>
-int dictionary_for(std::unique_lock<std::mutex> &lk, size_t L, int nsym, Head &&head, const TrainPiece *dev, std::shared_ptr<DictDev> *dd)
-{
-    if (!g.compression || !imc::compressible(L, nsym)) return IMC_OK;
-    auto it = g.dicts.find(nsym);
-    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }
-    if (L < imc::TrainLimits().train_min) return IMC_OK;
-    std::shared_ptr<DictDev> nd;
-    if (dev && device_train_mode() == 1) {
-        if (int rc = device_train(dev, 1, nsym, L, L, &nd)) return rc;
-    } else {
-        HostSymbols sym{};
-        if (int rc = head(&sym)) return rc;
-        imc::TrainStats st;
-        lk.unlock();
-        nd = make_dictionary(sym, nsym, L, &st);                         // host only, unlocked
-        lk.lock();
-        note_training(0, st);
-    }
-    it = g.dicts.find(nsym);
-    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }        // another thread published one meanwhile: use that
-    if (int rc = publish_dictionary(nsym, nd)) return rc;
-    *dd = nd;
     return IMC_OK;
 }
 
@@ -922,6 +851,53 @@ int device_train(const TrainPiece *pieces, size_t n_pieces, int nsym, size_t L, 
     return IMC_OK;
 }
 
+// The dictionary a new chunk of L columns is encoded with (the preprocess_raw_observations analogue, hmm.py:16): the
+// one published for its alphabet; else, for the first chunk long enough, one trained now; else none (*dd stays null).
+// Called and left with lk (g_mu) held and the context ready; the lock is released while training runs.  head(&symbols)
+// supplies the training symbols - at least imc::training_head() of the chunk - and is called, under the lock, only when
+// a dictionary has to be trained.  With imc_set_device_training(1) and the chunk's symbols on the device (`dev`, all L
+// of them; else null) the dictionary is trained there instead, with the lock held, and nothing comes back to the host.
+// must_train(): whether a call now would train one.
+bool must_train(size_t L, int nsym)
+{
+    return g.opt.compression && imc::compressible(L, nsym) && g.dicts.find(nsym) == g.dicts.end() && L >= imc::TrainLimits().train_min;
+}
+
+template <class Head>
+int dictionary_for(std::unique_lock<std::mutex> &lk, size_t L, int nsym, Head &&head, const TrainPiece *dev, std::shared_ptr<DictDev> *dd)
+{
+    if (!g.opt.compression || !imc::compressible(L, nsym)) return IMC_OK;
+    auto it = g.dicts.find(nsym);
+    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }
+    if (L < imc::TrainLimits().train_min) return IMC_OK;
+    std::shared_ptr<DictDev> nd;
+    if (dev && device_mode(&imc::Options::device_train) == 1) {
+        if (int rc = device_train(dev, 1, nsym, L, L, &nd)) return rc;
+    } else {
+        HostSymbols sym{};
+        if (int rc = head(&sym)) return rc;
+        imc::TrainStats st;
+        lk.unlock();
+        nd = make_dictionary(sym, nsym, L, &st);                         // host only, unlocked
+        lk.lock();
+        note_training(0, st);
+    }
+    it = g.dicts.find(nsym);
+    if (it != g.dicts.end()) { *dd = it->second; return IMC_OK; }        // another thread published one meanwhile: use that
+    if (int rc = publish_dictionary(nsym, nd)) return rc;
+    *dd = nd;
+    return IMC_OK;
+}
+
+// The host symbols into the chunk's own padded buffer.
+int upload_symbols(imc_obs *o, const HostSymbols &sym)
+{
+    const hipError_t e = o->wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(sym.wide), sym.n * sizeof(imc::tok_t), &o->d_sym)
+                                     : upload_padded(sym.bytes, sym.n, &o->d_sym);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP, std::string("observation upload: ") + hipGetErrorString(e));
+    return IMC_OK;
+}
+
 // obs_upload for the creation that trains its alphabet's dictionary, with imc_set_device_training(1): the symbols go up
 // first and the dictionary is trained from the chunk's own buffer; the encoder is the one imc_set_device_encoding names.
 // lk (g_mu) held, context ready.
@@ -929,37 +905,27 @@ int obs_upload_and_train(std::unique_lock<std::mutex> &lk, const HostSymbols &sy
 {
     PhaseTimer tm;
     HIP_TRY(hipSetDevice(g.device));
-    imc_obs *o = obs_new(sym.n, nsym);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    auto give_up = [&](int rc) {
-        const std::string msg = g_err;
-        obs_release(o);
-        delete o;
-        return fail(rc, msg);
-    };
-    const hipError_t e = o->wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(sym.wide), sym.n * sizeof(imc::tok_t), &o->d_sym)
-                                     : upload_padded(sym.bytes, sym.n, &o->d_sym);
-    if (e != hipSuccess) {
-        g_err = std::string("observation upload: ") + hipGetErrorString(e);
-        return give_up(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP);
-    }
+    ObsOwner o = obs_new(sym.n, nsym);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    if (int rc = upload_symbols(o.get(), sym)) return obs_finish(rc, o, out);
     tm.mark();
     std::shared_ptr<DictDev> dd;
     const TrainPiece piece{o->d_sym, o->wide_raw ? 2 : 1, sym.n};
-    if (int rc = dictionary_for(lk, sym.n, nsym, [](HostSymbols *) -> int { return IMC_OK; }, &piece, &dd)) return give_up(rc);
+    if (int rc = dictionary_for(lk, sym.n, nsym, [](HostSymbols *) -> int { return IMC_OK; }, &piece, &dd)) return obs_finish(rc, o, out);
     tm.mark();
     if (dd && dd->dict.alphabet > nsym) {
         int rc;
-        if (on_device) rc = device_encode(dd, &o, 1);
+        imc_obs *const chunk = o.get();
+        if (on_device) rc = device_encode(dd, &chunk, 1);
         else {
             imc::EncodedLevels enc;
             lk.unlock();                             // host only, unlocked (a published dictionary is immutable; nobody else holds o)
             imc::encode_levels(dd->dict, sym.bytes, sym.wide, sym.n, enc);
             lk.lock();
             (void)hipSetDevice(g.device);
-            rc = install_encoding(o, dd, enc);
+            rc = install_encoding(chunk, dd, enc);
         }
-        if (rc != IMC_OK) return give_up(rc);
+        if (rc != IMC_OK) return obs_finish(rc, o, out);
     }
     tm.mark();
     if (PhaseTimer::enabled())
@@ -967,8 +933,7 @@ int obs_upload_and_train(std::unique_lock<std::mutex> &lk, const HostSymbols &sy
                      tm.ms(0), tm.ms(1), tm.ms(2), on_device ? "device" : "host");
     g.last_ingest[0] = g.last_ingest[1] = g.last_ingest[2] = 0;   // (imc_last_ingest: parsed and validated on the host)
     g.last_ingest[3] = sym.n;
-    *out = o;
-    return IMC_OK;
+    return obs_finish(IMC_OK, o, out);
 }
 
 // Build a chunk from validated host symbols (exactly one of host / host16 is non-null when L > 0).  Called WITHOUT g_mu.
@@ -979,8 +944,8 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
     std::shared_ptr<DictDev> dd;
     std::unique_lock<std::mutex> lk(g_mu);
     if (int rc = ensure_ctx()) return rc;
-    const bool on_device = g.device_encode == 1;
-    if (device_train_mode() == 1 && must_train(L, nsym)) return obs_upload_and_train(lk, sym, nsym, on_device, out);
+    const bool on_device = g.opt.device_encode == 1;
+    if (device_mode(&imc::Options::device_train) == 1 && must_train(L, nsym)) return obs_upload_and_train(lk, sym, nsym, on_device, out);
     if (int rc = dictionary_for(lk, L, nsym, [&](HostSymbols *s) -> int { *s = sym; return IMC_OK; }, nullptr, &dd)) return rc;
     lk.unlock();
     tm.mark();
@@ -993,23 +958,13 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
     lk.lock();
     if (int rc = ensure_ctx()) return rc;
     HIP_TRY(hipSetDevice(g.device));
-    imc_obs *o = obs_new(L, nsym);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    const hipError_t e = o->wide_raw ? upload_padded(reinterpret_cast<const uint8_t *>(host16), L * sizeof(imc::tok_t), &o->d_sym)
-                                     : upload_padded(host, L, &o->d_sym);
-    if (e != hipSuccess) {
-        obs_release(o);
-        delete o;
-        return fail(e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,
-                    std::string("observation upload: ") + hipGetErrorString(e));
-    }
+    ObsOwner o = obs_new(L, nsym);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    if (int rc = upload_symbols(o.get(), sym)) return obs_finish(rc, o, out);
     tm.mark();
     if (zipped) {
-        if (int rc = on_device ? device_encode(dd, &o, 1) : install_encoding(o, dd, enc)) {
-            obs_release(o);
-            delete o;
-            return rc;
-        }
+        imc_obs *const chunk = o.get();
+        if (int rc = on_device ? device_encode(dd, &chunk, 1) : install_encoding(chunk, dd, enc)) return obs_finish(rc, o, out);
     }
     tm.mark();
     if (PhaseTimer::enabled())   // (host encoder: "encode" is encode_levels and "install" the upload of its streams; device encoder: all of it is "install")
@@ -1017,8 +972,7 @@ int obs_upload(const uint8_t *host, const imc::tok_t *host16, size_t L, int nsym
                      tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host");
     g.last_ingest[0] = g.last_ingest[1] = g.last_ingest[2] = 0;   // (imc_last_ingest: parsed and validated on the host)
     g.last_ingest[3] = L;
-    *out = o;
-    return IMC_OK;
+    return obs_finish(IMC_OK, o, out);
 }
 
 // d_sym must be device memory of the library's device, `bytes` long: an error, never a fault (g_mu held, context ready).
@@ -1110,16 +1064,6 @@ int finish_device_chunk(std::unique_lock<std::mutex> &lk, imc_obs *o)
     return dd && dd->dict.alphabet > o->nsym ? device_encode(dd, &o, 1) : IMC_OK;
 }
 
-// The switch of imc_set_device_ingest (g_mu held; no device needed): IMC_DEVICE_INGEST decides until it is set.
-int device_ingest_mode()
-{
-    if (g.device_ingest < 0) {
-        const char *di = std::getenv("IMC_DEVICE_INGEST");
-        g.device_ingest = di && std::atoi(di) == 1 ? 1 : 0;
-    }
-    return g.device_ingest;
-}
-
 void note_ingest(uint64_t path, uint64_t bytes, uint64_t slabs, uint64_t columns)
 {
     g.last_ingest[0] = path; g.last_ingest[1] = bytes; g.last_ingest[2] = slabs; g.last_ingest[3] = columns;
@@ -1135,19 +1079,12 @@ int obs_from_device(const void *d_src, size_t L, int nsym, int sym_bytes, hipStr
     if (L)
         if (int rc = check_device_range(d_src, L * (size_t)sym_bytes)) return rc;
     HIP_TRY(hipStreamSynchronize(user_stream));   // what the caller queued on its stream has produced the symbols
-    imc_obs *o = obs_new(L, nsym);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    int rc = adopt_device_symbols(o, d_src, sym_bytes, "outside [0,nsym)");
-    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
-    if (rc != IMC_OK) {
-        const std::string msg = g_err;
-        obs_release(o);
-        delete o;
-        return fail(rc, msg);
-    }
-    note_ingest(0, 0, 0, L);
-    *out = o;
-    return IMC_OK;
+    ObsOwner o = obs_new(L, nsym);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    int rc = adopt_device_symbols(o.get(), d_src, sym_bytes, "outside [0,nsym)");
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
+    if (rc == IMC_OK) note_ingest(0, 0, 0, L);
+    return obs_finish(rc, o, out);
 }
 
 // ---- device ingestion -------------------------------------------------------------------------------------
@@ -1233,20 +1170,6 @@ int ingest_pump(std::unique_lock<std::mutex> &lk, IngestStage &st, uint64_t tota
     return IMC_OK;
 }
 
-// A new chunk whose creation failed, or the finished one (g_mu held).
-int ingest_result(int rc, imc_obs *o, imc_obs **out)
-{
-    if (rc != IMC_OK) {
-        const std::string msg = g_err;
-        (void)hipStreamSynchronize(g.stream);
-        obs_release(o);
-        delete o;
-        return fail(rc, msg);
-    }
-    *out = o;
-    return IMC_OK;
-}
-
 // Text file of file_bytes bytes, fp at its start.  *declined: the device parser does not take this file (a slab without
 // whitespace, a digit run beyond 16) - nothing was created, the host parser reads it from its start.  Errors are the host
 // parser's, in file order: slab k's verdict is looked at before slab k + 1 is queued.
@@ -1306,16 +1229,16 @@ int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes,
     lk.lock();
     if (end == imc::kSlabDeclined) { *declined = true; return IMC_OK; }
     if (end != imc::kSlabDone) return end;
-    if (cols >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(cols)) return rc;
     HIP_TRY(hipSetDevice(g.device));
-    imc_obs *o = obs_new((size_t)cols, nsym);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    int rc = adopt_device_symbols(o, symbols.get(), (int)unit, ">= nsym");
+    ObsOwner o = obs_new((size_t)cols, nsym);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    int rc = adopt_device_symbols(o.get(), symbols.get(), (int)unit, ">= nsym");
     st.release();
     symbols.reset();
-    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
     if (rc == IMC_OK) note_ingest(1, sent, slabs, cols);
-    return ingest_result(rc, o, out);
+    return obs_finish(rc, o, out);
 }
 
 // Cache file, fp behind its header h (checked).  The payload goes up packed: 2-bit files are unpacked by the device into the
@@ -1327,8 +1250,8 @@ int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHea
     IngestStage st;
     DevBuf<uint8_t> raw;
     if (int rc = st.alloc(slab, payload > slab ? 2 : 1)) return rc;
-    imc_obs *o = obs_new((size_t)L, nsym);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    ObsOwner o = obs_new((size_t)L, nsym);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
     const size_t unit = o->wide_raw ? sizeof(imc::tok_t) : 1;
     uint64_t slabs = 0;
     auto fill = [&](int b, uint64_t, uint64_t len) -> int {
@@ -1336,7 +1259,7 @@ int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHea
     };
     auto work = [&]() -> int {
         if (h.bits == 2) {
-            if (int rc = alloc_symbols(o)) return rc;
+            if (int rc = alloc_symbols(o.get())) return rc;
             if (int rc = ingest_pump(lk, st, payload, slab, &slabs, fill, [&](int b, uint64_t off, uint64_t len) -> int {
                     const uint32_t columns = (uint32_t)std::min<uint64_t>(4 * len, L - 4 * off);
                     HIP_TRY(hipMemcpyAsync(st.dev[b].get(), st.host[b], (size_t)len, hipMemcpyHostToDevice, g.stream));
@@ -1355,14 +1278,14 @@ int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHea
             }))
             return rc;
         st.release();
-        const int rc = adopt_device_symbols(o, raw.get(), (int)(h.bits / 8), ">= nsym");
+        const int rc = adopt_device_symbols(o.get(), raw.get(), (int)(h.bits / 8), ">= nsym");
         raw.reset();
         return rc;
     };
     int rc = work();
-    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
     if (rc == IMC_OK) note_ingest(2, payload, slabs, L);
-    return ingest_result(rc, o, out);
+    return obs_finish(rc, o, out);
 }
 
 // imc_obs_create_from_text on the device path (arguments checked).  Opening the file, its size, the magic and the cache
@@ -1382,7 +1305,7 @@ int obs_from_file_device(const char *path, int nsym, imc_obs **out, bool *declin
         const imc::IoResult hr = imc::read_cache_header(fp, path, nsym, h);
         if (hr.code) return fail(hr.code, hr.msg);
         if (h.bits == 16 && nsym <= imc::kByteAlphabet) { *declined = true; return IMC_OK; }   // (the host reader narrows before it validates)
-        if (h.L >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+        if (int rc = check_columns(h.L)) return rc;
     } else
         std::rewind(fp);
     std::unique_lock<std::mutex> lk(g_mu);
@@ -1400,10 +1323,10 @@ int obs_from_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **ou
     const size_t columns = std::min<size_t>(ingest_slab_bytes() / 2, std::max<size_t>(L, imc::kMinSlabBytes / 2)), half = (columns + 15) & ~(size_t)15;
     IngestStage st;
     if (int rc = st.alloc(2 * half, L > half ? 2 : 1)) return rc;
-    imc_obs *o = obs_new(L, 3);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
+    ObsOwner o = obs_new(L, 3);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
     uint64_t slabs = 0;
-    int rc = alloc_symbols(o);
+    int rc = alloc_symbols(o.get());
     if (rc == IMC_OK)
         rc = ingest_pump(lk, st, L, half, &slabs,
                          [&](int b, uint64_t off, uint64_t len) -> int {
@@ -1418,9 +1341,9 @@ int obs_from_pairwise(const char *seq1, const char *seq2, size_t L, imc_obs **ou
                              return IMC_OK;
                          });
     st.release();
-    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
     if (rc == IMC_OK) note_ingest(3, 2 * (uint64_t)L, slabs, L);
-    return ingest_result(rc, o, out);
+    return obs_finish(rc, o, out);
 }
 
 // ---- resident alignments ------------------------------------------------------------------------------------
@@ -1540,7 +1463,7 @@ int aln_open(const char *path, imc_aln **out)
     struct stat sb;
     const bool regular = fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode);   // (a pipe cannot be read twice)
     std::unique_ptr<imc_aln> a(new (std::nothrow) imc_aln());
-    if (!a) { std::fclose(fp); return fail(IMC_ERR_OOM, "host allocation failed"); }
+    if (!a) { std::fclose(fp); return fail(IMC_ERR_OOM, kHostAllocFailed); }
     bool declined = !regular;
     {
         struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{fp};
@@ -1577,9 +1500,9 @@ int obs_from_alignment(const imc_aln *a, const uint64_t *offsets, int k, size_t 
     if (int rc = ensure_ctx()) return rc;
     if (a->pid != g.pid) return fail(IMC_ERR_HIP, "alignment was opened in another process");
     HIP_TRY(hipSetDevice(g.device));
-    imc_obs *o = obs_new(L, k == 2 ? 3 : 65);
-    if (!o) return fail(IMC_ERR_OOM, "host allocation failed");
-    int rc = alloc_symbols(o);
+    ObsOwner o = obs_new(L, k == 2 ? 3 : 65);
+    if (!o) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    int rc = alloc_symbols(o.get());
     if (rc == IMC_OK && L) {
         const dim3 grid((uint32_t)((L + (size_t)ALN_COLUMNS * TILE_THREADS - 1) / ((size_t)ALN_COLUMNS * TILE_THREADS)));
         if (k == 2)
@@ -1588,9 +1511,9 @@ int obs_from_alignment(const imc_aln *a, const uint64_t *offsets, int k, size_t 
             hipLaunchKernelGGL(k_aln_columns<3>, grid, dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)a->d_bases, offsets[0], offsets[1], offsets[2], (uint32_t)L, o->d_sym);
         if (hipGetLastError() != hipSuccess) rc = fail(IMC_ERR_HIP, "alignment: the column kernel could not be launched");
     }
-    if (rc == IMC_OK) rc = finish_device_chunk(lk, o);
+    if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
     if (rc == IMC_OK) note_ingest(4, 0, 0, L);
-    return ingest_result(rc, o, out);
+    return obs_finish(rc, o, out);
 }
 
 // The deepest level within alphabet_limit at which the chunk holds a token stream; -1: none, its raw symbols
@@ -1602,101 +1525,6 @@ int token_level(const imc_obs *obs, int alphabet_limit)
         for (int l = 0; l < imc::kNumLevels; ++l)
             if (obs->alphabet[l] <= alphabet_limit && obs->alphabet[l] > obs->nsym && obs->d_tok[l]) level = l;
     return level;
-}
-
-// Joint re-compression of the chunks of one alphabet (imc_obs_recompress), called without g_mu: a new dictionary is
-// trained on a sample drawn evenly from ALL the chunks, they are re-encoded with it, and it replaces the alphabet's
-// dictionary.
-int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
-{
-    // (in creation order, not in address order: the training sample is the concatenation of the chunks' heads, and with
-    // pointer order the dictionary - alphabet, token counts, now and then whether the byte phase filled its 256 entries
-    // at all - changed from run to run of the same program)
-    std::sort(obs.begin(), obs.end(), [](const imc_obs *x, const imc_obs *y) { return x->id < y->id; });
-    obs.erase(std::unique(obs.begin(), obs.end()), obs.end());
-    const bool wide_raw = nsym > imc::kByteAlphabet;
-    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
-    PhaseTimer tm;
-    size_t total = 0;
-    for (imc_obs *o : obs) total += o->L;
-    if (total < imc::TrainLimits().train_min) return IMC_OK;
-    // ---- sample: the raw symbols come back to the host (the chunks keep them on the device) - all of them for the host
-    //      encoder, only the training heads when the device encodes ----
-    //      With imc_set_device_training(1) the sample stays where it is: the heads are the pieces of a device training,
-    //      and with the device encoder nothing comes back at all.
-    const size_t share = imc::recompress_share(obs.size(), wide_raw);
-    std::vector<std::vector<uint8_t>> raw(obs.size());
-    bool train_on_device = false;
-    size_t copied = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        train_on_device = device_train_mode() == 1;
-        // nothing to gain if these chunks already share a dictionary trained on at least this much data
-        // (a second Likelihood over the same forwarders, a subset of a recompressed set)
-        bool same = obs[0]->dict != nullptr;
-        for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
-        if (same && obs[0]->dict->trained_on >= total) return IMC_OK;
-        HIP_TRY(hipSetDevice(g.device));
-        for (size_t k = 0; k < obs.size() && !(train_on_device && on_device); ++k) {
-            raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
-            HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
-            copied += raw[k].size();
-        }
-    }
-    std::vector<uint8_t> sample;
-    if (!train_on_device) sample = imc::recompress_sample(raw, share, unit);
-    tm.mark();
-    // ---- train (host, unlocked - or on the device, under the lock) ----
-    std::shared_ptr<DictDev> nd;
-    if (train_on_device) {
-        std::vector<TrainPiece> pieces;
-        size_t sample_len = 0;
-        for (imc_obs *o : obs) {
-            pieces.push_back({o->d_sym, (int)unit, std::min(o->L, share)});
-            sample_len += pieces.back().n;
-        }
-        std::lock_guard<std::mutex> lk(g_mu);
-        HIP_TRY(hipSetDevice(g.device));
-        if (int rc = device_train(pieces.data(), pieces.size(), nsym, sample_len, total, &nd)) return rc;
-    } else {
-        imc::TrainStats st;
-        nd = make_dictionary(symbols_in(sample, wide_raw), nsym, total, &st);
-        std::vector<uint8_t>().swap(sample);
-        std::lock_guard<std::mutex> lk(g_mu);
-        note_training(0, st);
-    }
-    tm.mark();
-    // ---- encode (host encoder only; unlocked) ----
-    std::vector<imc::EncodedLevels> enc(obs.size());
-    const bool zipped = nd->dict.alphabet > nsym;
-    if (zipped && !on_device)
-        for (size_t k = 0; k < obs.size(); ++k) {
-            const HostSymbols sym = symbols_in(raw[k], wide_raw);
-            imc::encode_levels(nd->dict, sym.bytes, sym.wide, obs[k]->L, enc[k]);
-            std::vector<uint8_t>().swap(raw[k]);
-        }
-    tm.mark();
-    // ---- install: swap the streams in under the lock ----
-    std::unique_lock<std::mutex> lk(g_mu);
-    wait_all_idle(lk);
-    HIP_TRY(hipSetDevice(g.device));
-    HIP_TRY(hipDeviceSynchronize());                 // nothing of these chunks is in flight any more
-    drop_plans_using(obs.data(), obs.size());        // plans hold raw pointers into the old streams
-    if (!zipped) return IMC_OK;                      // (incompressible sample: keep what the chunks have)
-    if (int rc = publish_dictionary(nsym, nd)) return rc;   // later chunks of this alphabet share it too
-    if (on_device) {                                 // all chunks of the alphabet in one batched run of passes
-        for (imc_obs *o : obs) release_tokens(o);
-        if (int rc = device_encode(nd, obs.data(), obs.size())) return rc;
-    } else
-        for (size_t k = 0; k < obs.size(); ++k) {
-            release_tokens(obs[k]);
-            if (int rc = install_encoding(obs[k], nd, enc[k])) return rc;
-        }
-    tm.mark();
-    if (PhaseTimer::enabled())
-        std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder, %s trainer, %zu symbol bytes to the host)\n",
-                     obs.size(), total, tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host", train_on_device ? "device" : "host", copied);
-    return IMC_OK;
 }
 
 // ---- kernel table ---------------------------------------------------------------------------------
@@ -1920,11 +1748,27 @@ struct Level {             // one level of the stitch hierarchy (level 0 = propa
     DevBuf<int> d_EX, d_EMAX;
 };
 
+// What a cached plan answers to: the call's chunks and shape, and the options it was built under (opt: the context's
+// record of that moment, the device's size and the per-call variables).  Two keys are equal when a plan of one may be
+// replayed for the other: imc::same_plan_options decides it for the record, and the debug flags do not count.
+struct PlanKey {
+    std::vector<uint64_t> chunk_ids;
+    int N = 0, S = 0, B = 0;
+    bool op_mode = false;               // imc_forward_state(as_operator)
+    imc::PlanOptions opt;
+    bool operator==(const PlanKey &o) const
+    {
+        return chunk_ids == o.chunk_ids && N == o.N && S == o.S && B == o.B && op_mode == o.op_mode && opt.force_level == o.opt.force_level &&
+               imc::same_plan_options(opt, o.opt);
+    }
+};
+
 struct Plan {
-    std::vector<uint64_t> key;
+    const PlanKey key;               // (key.opt: what the builder and every launch of this plan read their options from)
     KernelChoice *kc = nullptr;
     bool wide = false;               // 25-32 states on the blocked scan (PlanBuilder::wide)
-    int N = 0, S = 0, B = 0, n_chunks = 0;
+    const int &N = key.N, &S = key.S, &B = key.B;   // the key holds the call's shape: one copy (a Plan is neither copied nor moved)
+    const int n_chunks = (int)key.chunk_ids.size();
     uint32_t n_segs = 0, n_vecs = 0;
     std::vector<Group> groups;
     size_t pstride = 0;
@@ -1959,7 +1803,7 @@ struct Plan {
     uint64_t calls = 0;
     uint64_t lp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::string kernels;
-    Plan() = default;
+    explicit Plan(PlanKey k) : key(std::move(k)) {}
     Plan(const Plan &) = delete;
     Plan &operator=(const Plan &) = delete;
     // The device buffers free themselves (DevBuf members: after this body, so the pinned slots and events now go
@@ -1999,10 +1843,105 @@ void drop_plans_using(imc_obs *const *obs, size_t n)
 {
     for (auto it = g_plans.begin(); it != g_plans.end();) {
         bool uses = false;
-        for (size_t k = 0; k < (size_t)(*it)->n_chunks; ++k)
-            for (size_t q = 0; q < n; ++q) uses |= (*it)->key[k] == obs[q]->id;
+        for (uint64_t id : (*it)->key.chunk_ids)
+            for (size_t q = 0; q < n; ++q) uses |= id == obs[q]->id;
         it = uses ? g_plans.erase(it) : std::next(it);
     }
+}
+
+// Joint re-compression of the chunks of one alphabet (imc_obs_recompress; chunk work, but behind the plan list, whose plans it drops), called without g_mu: a new dictionary is
+// trained on a sample drawn evenly from ALL the chunks, they are re-encoded with it, and it replaces the alphabet's
+// dictionary.
+int recompress_alphabet(int nsym, std::vector<imc_obs *> &obs, bool on_device)
+{
+    // (in creation order, not in address order: the training sample is the concatenation of the chunks' heads, and with
+    // pointer order the dictionary - alphabet, token counts, now and then whether the byte phase filled its 256 entries
+    // at all - changed from run to run of the same program)
+    std::sort(obs.begin(), obs.end(), [](const imc_obs *x, const imc_obs *y) { return x->id < y->id; });
+    obs.erase(std::unique(obs.begin(), obs.end()), obs.end());
+    const bool wide_raw = nsym > imc::kByteAlphabet;
+    const size_t unit = wide_raw ? sizeof(imc::tok_t) : 1;
+    PhaseTimer tm;
+    size_t total = 0;
+    for (imc_obs *o : obs) total += o->L;
+    if (total < imc::TrainLimits().train_min) return IMC_OK;
+    // ---- sample: the raw symbols come back to the host (the chunks keep them on the device) - all of them for the host
+    //      encoder, only the training heads when the device encodes ----
+    //      With imc_set_device_training(1) the sample stays where it is: the heads are the pieces of a device training,
+    //      and with the device encoder nothing comes back at all.
+    const size_t share = imc::recompress_share(obs.size(), wide_raw);
+    std::vector<std::vector<uint8_t>> raw(obs.size());
+    bool train_on_device = false;
+    size_t copied = 0;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        train_on_device = device_mode(&imc::Options::device_train) == 1;
+        // nothing to gain if these chunks already share a dictionary trained on at least this much data
+        // (a second Likelihood over the same forwarders, a subset of a recompressed set)
+        bool same = obs[0]->dict != nullptr;
+        for (imc_obs *o : obs) same = same && o->dict == obs[0]->dict;
+        if (same && obs[0]->dict->trained_on >= total) return IMC_OK;
+        HIP_TRY(hipSetDevice(g.device));
+        for (size_t k = 0; k < obs.size() && !(train_on_device && on_device); ++k) {
+            raw[k].resize((on_device ? std::min(obs[k]->L, share) : obs[k]->L) * unit);
+            HIP_TRY(hipMemcpy(raw[k].data(), obs[k]->d_sym, raw[k].size(), hipMemcpyDeviceToHost));
+            copied += raw[k].size();
+        }
+    }
+    std::vector<uint8_t> sample;
+    if (!train_on_device) sample = imc::recompress_sample(raw, share, unit);
+    tm.mark();
+    // ---- train (host, unlocked - or on the device, under the lock) ----
+    std::shared_ptr<DictDev> nd;
+    if (train_on_device) {
+        std::vector<TrainPiece> pieces;
+        size_t sample_len = 0;
+        for (imc_obs *o : obs) {
+            pieces.push_back({o->d_sym, (int)unit, std::min(o->L, share)});
+            sample_len += pieces.back().n;
+        }
+        std::lock_guard<std::mutex> lk(g_mu);
+        HIP_TRY(hipSetDevice(g.device));
+        if (int rc = device_train(pieces.data(), pieces.size(), nsym, sample_len, total, &nd)) return rc;
+    } else {
+        imc::TrainStats st;
+        nd = make_dictionary(symbols_in(sample, wide_raw), nsym, total, &st);
+        std::vector<uint8_t>().swap(sample);
+        std::lock_guard<std::mutex> lk(g_mu);
+        note_training(0, st);
+    }
+    tm.mark();
+    // ---- encode (host encoder only; unlocked) ----
+    std::vector<imc::EncodedLevels> enc(obs.size());
+    const bool zipped = nd->dict.alphabet > nsym;
+    if (zipped && !on_device)
+        for (size_t k = 0; k < obs.size(); ++k) {
+            const HostSymbols sym = symbols_in(raw[k], wide_raw);
+            imc::encode_levels(nd->dict, sym.bytes, sym.wide, obs[k]->L, enc[k]);
+            std::vector<uint8_t>().swap(raw[k]);
+        }
+    tm.mark();
+    // ---- install: swap the streams in under the lock ----
+    std::unique_lock<std::mutex> lk(g_mu);
+    wait_all_idle(lk);
+    HIP_TRY(hipSetDevice(g.device));
+    HIP_TRY(hipDeviceSynchronize());                 // nothing of these chunks is in flight any more
+    drop_plans_using(obs.data(), obs.size());        // plans hold raw pointers into the old streams
+    if (!zipped) return IMC_OK;                      // (incompressible sample: keep what the chunks have)
+    if (int rc = publish_dictionary(nsym, nd)) return rc;   // later chunks of this alphabet share it too
+    if (on_device) {                                 // all chunks of the alphabet in one batched run of passes
+        for (imc_obs *o : obs) release_tokens(o);
+        if (int rc = device_encode(nd, obs.data(), obs.size())) return rc;
+    } else
+        for (size_t k = 0; k < obs.size(); ++k) {
+            release_tokens(obs[k]);
+            if (int rc = install_encoding(obs[k], nd, enc[k])) return rc;
+        }
+    tm.mark();
+    if (PhaseTimer::enabled())
+        std::fprintf(stderr, "[imc host] recompress %zu chunks, %zu columns: copy back %.1f ms, train %.1f ms, encode %.1f ms, install %.1f ms (%s encoder, %s trainer, %zu symbol bytes to the host)\n",
+                     obs.size(), total, tm.ms(0), tm.ms(1), tm.ms(2), tm.ms(3), on_device ? "device" : "host", train_on_device ? "device" : "host", copied);
+    return IMC_OK;
 }
 
 void publish_last(const Plan *p)     // what imc_last_plan() / imc_last_kernels() report: the plan just enqueued
@@ -2043,13 +1982,13 @@ struct PlanBuilder {
     const imc_obs *const *chunks = nullptr;
     int n_chunks = 0, N = 0, S = 0, B = 0;
     bool op_mode = false;               // imc_forward_state(as_operator): no segment is a chunk's "first"
-    imc::PlanOptions opt;               // the options the decision was taken under
     KernelChoice *kc = nullptr;
     // 25-32 states: kc is the vector kernels' entry and every dictionary's chunks run its streamed blocked scan
     // (k_zpropagate4<7 | 8>); chunks without tokens stay on the vector kernels.
     bool wide = false;
-    bool mfma() const { return kc->use3(opt.blocked_variant) || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
+    bool mfma() const { return kc->use3(opt().blocked_variant) || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
     std::unique_ptr<Plan> p;
+    const imc::PlanOptions &opt() const { return p->key.opt; }   // the options the decision was taken under: the plan's
     std::vector<int> chunk_group;       // chunk -> index into p->groups
     std::vector<SegDesc> segs;          // all segments, chunk order
     std::vector<uint8_t> seg_first;
@@ -2272,7 +2211,7 @@ struct PlanBuilder {
                     for (size_t z = 0; z < chunks[f]->tok_count[gr.level].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[gr.level][z];
                 const std::vector<uint16_t> ids = imc::hot_order(cnt);
                 const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
-                bl.stream_table = wide || imc::z4_streamed(opt, tables, B);
+                bl.stream_table = wide || imc::z4_streamed(opt(), tables, B);
                 bl.n_hot = bl.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
                 bl.hot.assign(ids.begin(), ids.begin() + bl.n_hot);
                 bl.phases = imc::xcd_phases(B, (int)bl.blocks.size());
@@ -2305,7 +2244,7 @@ struct PlanBuilder {
             ch.big_blocks = imc::deal_slabs<BigBlock>(ch.seg_ids, ch.seg_out, seg_first, kc->big_nslab);
             u.put(ch.d_big_blocks, ch.big_blocks);
             u.alloc(gr.d_Ctab, (size_t)B * gr.A * np2 * 8);
-            if ((gr.kind == Group::Kind::MatVecChain || ch.rank1) && N < kc->NP && g.pack_table)   // the mat-vec chain reads a packed copy
+            if ((gr.kind == Group::Kind::MatVecChain || ch.rank1) && N < kc->NP && opt().pack_table)   // the mat-vec chain reads a packed copy
                 u.alloc(ch.d_Cpack, (size_t)B * gr.A * N * (size_t)(N + (N & 1)) * 8);
             u.alloc(gr.d_cex, (size_t)B * gr.A * 4 + 16);
             if (ch.rank1) {
@@ -2358,22 +2297,19 @@ void gather_facts(const imc_obs *const *chunks, int n_chunks, std::vector<imc::C
 
 int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, bool op_mode, Plan **out)
 {
-    // What the planner reads of the context and the environment.  The three variables are read here, once per call, not
-    // at context creation: tests set IMC_FORCE_LEVEL between calls.
+    // The options of this call: the context's record as it stands, the device's size, and the planner's three variables -
+    // read here, once per call, not at context creation: tests set IMC_FORCE_LEVEL between calls.
+    PlanKey key;
+    key.chunk_ids.reserve(n_chunks);
+    for (int f = 0; f < n_chunks; ++f) key.chunk_ids.push_back(chunks[f]->id);
+    key.N = N; key.S = S; key.B = B; key.op_mode = op_mode;
+    static_cast<imc::Options &>(key.opt) = g.opt;
+    key.opt.cus = g.cus;
     const char *force_level = std::getenv("IMC_FORCE_LEVEL");   // (experiments / tests)
-    imc::PlanOptions opt;
-    opt.cus = g.cus; opt.compression = g.compression; opt.kernel_pref = g.kernel_pref; opt.blocked_variant = g.blocked_variant;
-    opt.wide_blocked = g.wide_blocked; opt.z4_stream = g.z4_stream; opt.xcd_affine = g.xcd_affine; opt.table_pairs = g.table_pairs;
-    opt.rank1_handoff = g.rank1_handoff; opt.seg_override = g.seg_override;
-    opt.force_level = force_level ? std::atoi(force_level) : -1;
-    opt.debug = std::getenv("IMC_DEBUG") != nullptr;
-    opt.debug_levels = std::getenv("IMC_DEBUG_LEVELS") != nullptr;
-    std::vector<uint64_t> key;
-    key.reserve(n_chunks + 6);
-    for (int f = 0; f < n_chunks; ++f) key.push_back(chunks[f]->id);
-    key.push_back((uint64_t)N); key.push_back((uint64_t)S); key.push_back((uint64_t)B);
-    key.push_back((uint64_t)g.seg_override); key.push_back((uint64_t)(g.compression * 4 + g.kernel_pref + (op_mode ? 64 : 0) + g.blocked_variant * 128 + (g.z4_stream + 1) * 1024 + (g.wide_blocked + 1) * 4096));
-    key.push_back(force_level ? (uint64_t)(opt.force_level + 1) : 0u);
+    key.opt.force_level = force_level ? std::atoi(force_level) : -1;
+    key.opt.debug = std::getenv("IMC_DEBUG") != nullptr;
+    key.opt.debug_levels = std::getenv("IMC_DEBUG_LEVELS") != nullptr;
+    const imc::PlanOptions &opt = key.opt;
     for (auto it = g_plans.begin(); it != g_plans.end(); ++it) {
         if ((*it)->key == key) {
             g_plans.splice(g_plans.begin(), g_plans, it);
@@ -2404,9 +2340,9 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
         }
     }
     PlanBuilder pb;
-    pb.chunks = chunks; pb.n_chunks = n_chunks; pb.N = N; pb.S = S; pb.B = B; pb.op_mode = op_mode; pb.opt = opt; pb.kc = kc; pb.wide = wide;
-    pb.p = std::make_unique<Plan>();
-    pb.p->key = key; pb.p->kc = kc; pb.p->wide = wide; pb.p->N = N; pb.p->S = S; pb.p->B = B; pb.p->n_chunks = n_chunks;
+    pb.chunks = chunks; pb.n_chunks = n_chunks; pb.N = N; pb.S = S; pb.B = B; pb.op_mode = op_mode; pb.kc = kc; pb.wide = wide;
+    pb.p = std::make_unique<Plan>(std::move(key));
+    pb.p->kc = kc; pb.p->wide = wide;
     pb.chunk_group = std::move(dec.chunk_group);
     for (imc::GroupDecision &gd : dec.groups) {
         Group gr;
@@ -2472,6 +2408,7 @@ struct Launch {
     double *out;
     bool allow_tail;
     KernelChoice *kc = p->kc;
+    const imc::PlanOptions &opt = p->key.opt;   // the options the plan was built under
     int B = p->B;
     bool fuse_head = false;       // the first table launch fetches the parameters itself: no k_stage_params, no k_z4_raw
     bool direct_params = false;   // the few workgroups of a small k_zpropagate3 launch fetch them themselves
@@ -2535,13 +2472,13 @@ int Launch::fetch_params()
     for (const Group &gr : p->groups)
         if (gr.n_vecs) { ++active; only = &gr; }
     const size_t head_lds = p->pstride * 8;
-    fuse_head = g.fuse_head && active == 1 && only->global_table() && g.table_pairs && only->blk.d_tab_desc2 && !only->blk.tab2.empty() &&
+    fuse_head = opt.fuse_head && active == 1 && only->global_table() && opt.table_pairs && only->blk.d_tab_desc2 && !only->blk.tab2.empty() &&
                 kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
     // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
     // columns): each of its few workgroups fetches the parameter set itself
-    direct_params = g.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3(g.blocked_variant) && pbytes <= STAGE_KERNEL_MAX_BYTES &&
+    direct_params = opt.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3(opt.blocked_variant) && pbytes <= STAGE_KERNEL_MAX_BYTES &&
                     only->blk.blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
-                    ((kc->blocked_lds(only->A, g.blocked_variant) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
+                    ((kc->blocked_lds(only->A, opt.blocked_variant) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
     if (fuse_head || direct_params) {
         // (nothing to enqueue here)
     } else if (pbytes <= STAGE_KERNEL_MAX_BYTES) {
@@ -2668,7 +2605,7 @@ BigArgs Launch::blocked_args(const Group &gr)
     ba.n_group_segs = (uint32_t)gr.blk.blocks.size();
     ba.tab_order = gr.blk.d_tab_order.get(); ba.tab_lvl = gr.blk.d_tab_lvl.get(); ba.tab_nlvl = gr.blk.tab_nlvl;
     ba.hot = gr.blk.d_hot.get(); ba.n_hot = gr.blk.n_hot; ba.tab_desc = gr.blk.d_tab_desc.get();
-    if (gr.blk.d_tails && (g.fuse_tail == 2 || (g.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (p->kc->use3(g.blocked_variant) || p->wide)) {
+    if (gr.blk.d_tails && (opt.fuse_tail == 2 || (opt.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (kc->use3(opt.blocked_variant) || p->wide)) {
         ba.tail = gr.blk.d_tails.get(); ba.tailX = gr.blk.d_tailX.get(); ba.tailE = gr.blk.d_tailE.get(); ba.tail_arrive = gr.blk.d_tail_arrive.get();
         ba.tail_out = out; ba.tail_stride = gr.blk.tail_stride;
         tail_used = true;
@@ -2686,7 +2623,7 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
         hipLaunchKernelGGL(kc->zip4_raw, dim3((unsigned)p->S + 1, (unsigned)B), dim3(256), 0, stream, ba);
         HIP_TRY(hipGetLastError());
     }
-    if (g.table_pairs && (g.table_triples == 1 || (g.table_triples < 0 && kc->NP <= 12)) && gr.blk.d_tab_desc3 && kc->zip4_level3) {
+    if (opt.table_pairs && (opt.table_triples == 1 || (opt.table_triples < 0 && kc->NP <= 12)) && gr.blk.d_tab_desc3 && kc->zip4_level3) {
         if (int rc = allow_lds_budget(kc->zip4_level3)) return rc;
         if (int rc = allow_lds_budget(kc->zip4_level3_first)) return rc;
         for (const auto &lc : gr.blk.tab3) {          // three dictionary depths per launch, one wavefront per token
@@ -2700,10 +2637,10 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
             head = false;
             HIP_TRY(hipGetLastError());
         }
-    } else if (g.table_pairs && gr.blk.d_tab_desc2 && kc->zip4_level2) {
-        const size_t split_max = g.table_split_max >= 0 ? (size_t)g.table_split_max : (size_t)4 * g.cus;
+    } else if (opt.table_pairs && gr.blk.d_tab_desc2 && kc->zip4_level2) {
+        const size_t split_max = opt.table_split_max >= 0 ? (size_t)opt.table_split_max : (size_t)4 * opt.cus;
         for (const auto &lc : gr.blk.tab2) {          // two dictionary depths per launch
-            if (g.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
+            if (opt.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
                 if (head)
                     hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
                                        dim3(Z4_SPLIT_WAVES_FIRST * 64), p->pstride * 8, stream, ba,
@@ -2743,7 +2680,7 @@ int Launch::zip4(const Group &gr)
     // XCD-affine grid (BigArgs::n_phases): with the two-dimensional grid every XCD's L2 sees the tables of all
     // B parameter sets
     dim3 scan_grid(ba.n_group_segs, (unsigned)B);
-    if (g.xcd_affine && B > 1) {
+    if (opt.xcd_affine && B > 1) {
         const imc::PhaseTable &t = gr.blk.phases;
         ba.n_phases = t.n_phases;
         for (int k = 0; k < t.n_phases; ++k) { ba.ph_begin[k] = t.ph_begin[k]; ba.ph_first[k] = t.ph_first[k]; ba.ph_sets[k] = t.ph_sets[k]; }
@@ -2760,10 +2697,10 @@ int Launch::zip4(const Group &gr)
 int Launch::zip32(const Group &gr)
 {
     BigArgs ba = blocked_args(gr);
-    const bool v3 = kc->use3(g.blocked_variant);
+    const bool v3 = kc->use3(opt.blocked_variant);
     void (*scan)(BigArgs) = v3 ? kc->zip3 : kc->zip2;
     if (int rc = allow_lds_budget(scan)) return rc;
-    size_t lds3 = kc->blocked_lds(gr.A, g.blocked_variant);
+    size_t lds3 = kc->blocked_lds(gr.A, opt.blocked_variant);
     if (direct_params) { ba.params_src = p->h_params_dev[p->slot]; lds3 = ((lds3 + 15) & ~(size_t)15) + p->pstride * 8; }
     hipLaunchKernelGGL(scan, dim3(ba.n_group_segs, (unsigned)p->B), dim3(Z2WAVES * 64), lds3, stream, ba);
     note(std::string(v3 ? "k_zpropagate3<" : "k_zpropagate2<") + std::to_string(kc->NP / 4) + ">" + stream_tag(gr));
@@ -2817,7 +2754,7 @@ int Launch::stitch() const
         }
         const int threads = (int)round_up((size_t)NP, 64);
         const bool last_level = l + 2 == p->levels.size();
-        hipLaunchKernelGGL(g.chain_lds ? kc->chain_lds : kc->chain, dim3(ot.n_chains, (unsigned)B), dim3(threads), 0, stream,
+        hipLaunchKernelGGL(opt.chain_lds ? kc->chain_lds : kc->chain, dim3(ot.n_chains, (unsigned)B), dim3(threads), 0, stream,
                            ot.d_chains.get(), N, in.n_segs, in.n_vecs, in.d_P.get(), in.d_EX.get(), in.d_EMAX.get(),
                            ot.n_vecs, ot.d_P.get(), ot.d_EX.get(), (last_level && p->finish_fused) ? out : (double *)nullptr, p->n_chunks);
         HIP_TRY(hipGetLastError());
@@ -2956,14 +2893,14 @@ int run_batch(const imc_obs *const *chunks, int n_chunks, int B, int N, int S, c
         ~Busy() { p->busy = false; g_cv.notify_all(); }
     } busy(p);
     const auto h1 = now();
-    if (int rc = stage_params(p, pis, Ts, Es, g.use_graphs)) return rc;
+    if (int rc = stage_params(p, pis, Ts, Es, p->key.opt.use_graphs)) return rc;
     const size_t n_out = (size_t)B * n_chunks;
     for (size_t k = 0; k < n_out; ++k) reinterpret_cast<volatile uint64_t *>(p->h_out)[k] = OUT_SENTINEL;
     std::atomic_thread_fence(std::memory_order_release);
     const auto h2 = now();
     // First call of a plan runs eagerly (kernel attributes get set); the second is captured into a hipGraph that
     // every later call replays: one graph launch instead of ~8 stream operations per evaluation.
-    const bool use_graph = !g.profile && g.use_graphs && p->calls >= 1;
+    const bool use_graph = !g.profile && p->key.opt.use_graphs && p->calls >= 1;
     if (use_graph && !p->graph) {
         hipGraph_t gr = nullptr;
         HIP_TRY(hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
@@ -3024,7 +2961,7 @@ int run_state(const imc_obs *const *chunks, int n_chunks, bool op_mode, int B, i
     HIP_TRY(hipSetDevice(g.device));
     Plan *p = nullptr;
     if (int rc = build_plan(chunks, n_chunks, N, S, B, op_mode, &p)) return rc;
-    if (int rc = stage_params(p, pis, Ts, Es, g.use_graphs)) return rc;
+    if (int rc = stage_params(p, pis, Ts, Es, p->key.opt.use_graphs)) return rc;
     if (int rc = enqueue(p, g.stream, p->d_out.get(), false)) return rc;      // (the log-likelihoods are not read here; the state comes from the stitch levels)
     ++p->calls;
     publish_last(p);
@@ -3065,7 +3002,7 @@ struct ModelDev { ModelBuf in, work, out; bool attr_set = false; } g_model;
 hipError_t model_reserve(ModelBuf &b, size_t bytes)
 {
     bytes = round_up(std::max<size_t>(bytes, 16), 16);
-    if (g.guard ? b.cap == bytes : b.cap >= bytes) return hipSuccess;
+    if (g.opt.guard ? b.cap == bytes : b.cap >= bytes) return hipSuccess;
     dev_free(b.p);
     b.p = nullptr;
     b.cap = 0;
@@ -3433,7 +3370,7 @@ int imc_obs_create(const uint8_t *sym, size_t L, int nsym, imc_obs **out)
     if (!out) return fail(IMC_ERR_ARG, "out is null");
     if (nsym < 1 || nsym > 256) return fail(IMC_ERR_ARG, "nsym must be in [1,256] for byte symbols (larger alphabets: imc_obs_create_i32)");
     if (L && !sym) return fail(IMC_ERR_ARG, "sym is null");
-    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(L)) return rc;
     for (size_t t = 0; t < L; ++t)
         if (sym[t] >= nsym) return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(sym[t]) + " at column " + std::to_string(t) + " >= nsym");
     return obs_upload(sym, nullptr, L, nsym, out);
@@ -3444,7 +3381,7 @@ int imc_obs_create_i32(const int32_t *sym, size_t L, int nsym, imc_obs **out)
     if (!out) return fail(IMC_ERR_ARG, "out is null");
     if (nsym < 1 || nsym > imc::kMaxRawAlphabet) return fail(IMC_ERR_ARG, "nsym must be in [1," + std::to_string(imc::kMaxRawAlphabet) + "]");
     if (L && !sym) return fail(IMC_ERR_ARG, "sym is null");
-    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(L)) return rc;
     for (size_t t = 0; t < L; ++t)
         if (sym[t] < 0 || sym[t] >= nsym)
             return fail(IMC_ERR_SYMBOL, "symbol " + std::to_string(sym[t]) + " at column " + std::to_string(t) + " outside [0,nsym)");
@@ -3463,7 +3400,7 @@ int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out)
     bool on_device;
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        on_device = device_ingest_mode() == 1;
+        on_device = device_mode(&imc::Options::device_ingest) == 1;
     }
     if (on_device) {                                    // parsed / unpacked on the device, unless the device parser declines the file
         bool declined = false;
@@ -3474,13 +3411,13 @@ int imc_obs_create_from_text(const char *path, int nsym, imc_obs **out)
         std::vector<imc::tok_t> wide;
         const imc::IoResult rw = imc::read_observation_file(path, nsym, wide);
         if (rw.code) return fail(rw.code, rw.msg);
-        if (wide.size() >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+        if (int rc = check_columns(wide.size())) return rc;
         return obs_upload(nullptr, wide.data(), wide.size(), nsym, out);
     }
     std::vector<uint8_t> sym;
     const imc::IoResult r = imc::read_observation_file(path, nsym, sym);
     if (r.code) return fail(r.code, r.msg);
-    if (sym.size() >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(sym.size())) return rc;
     return obs_upload(sym.data(), nullptr, sym.size(), nsym, out);
 }
 
@@ -3489,16 +3426,13 @@ int imc_obs_create_pairwise(const char *seq1, const char *seq2, size_t L, imc_ob
     // every argument check before any HIP call
     if (!out) return fail(IMC_ERR_ARG, "out is null");
     if (L && (!seq1 || !seq2)) return fail(IMC_ERR_ARG, "null sequence");
-    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(L)) return rc;
     return obs_from_pairwise(seq1, seq2, L, out);
 }
 
 int imc_set_device_ingest(int mode)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device ingest mode must be 0 (host parser) or 1 (device parser)");
-    g.device_ingest = mode;
-    return IMC_OK;
+    return set_device_mode(&imc::Options::device_ingest, mode, "device ingest mode must be 0 (host parser) or 1 (device parser)");
 }
 
 int imc_last_ingest(uint64_t *out4)
@@ -3511,10 +3445,7 @@ int imc_last_ingest(uint64_t *out4)
 
 int imc_set_device_training(int mode)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device training mode must be 0 (host trainer) or 1 (device trainer)");
-    g.device_train = mode;
-    return IMC_OK;
+    return set_device_mode(&imc::Options::device_train, mode, "device training mode must be 0 (host trainer) or 1 (device trainer)");
 }
 
 int imc_last_training(uint64_t *out4)
@@ -3645,7 +3576,7 @@ int imc_obs_create_from_alignment(const imc_aln *aln, const int *members, int k,
         if (aln->length[(size_t)members[j]] != L)
             return fail(IMC_ERR_ARG, "sequences differ in length: " + aln->names[(size_t)members[0]] + " has " + std::to_string(L) + " bases, " +
                                          aln->names[(size_t)members[j]] + " has " + std::to_string(aln->length[(size_t)members[j]]));
-    if (L >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(L)) return rc;
     return obs_from_alignment(aln, offsets, k, (size_t)L, out);
 }
 
@@ -3708,8 +3639,8 @@ int imc_obs_recompress(imc_obs *const *chunks, int n_chunks)
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (int rc = ensure_ctx()) return rc;
-        if (!g.compression) return IMC_OK;
-        on_device = g.device_encode == 1;
+        if (!g.opt.compression) return IMC_OK;
+        on_device = g.opt.device_encode == 1;
         for (int f = 0; f < n_chunks; ++f) {
             imc_obs *o = chunks[f];
             if (!o) return fail(IMC_ERR_ARG, "chunk is null");
@@ -3730,7 +3661,7 @@ int imc_obs_create_device(const void *d_sym, size_t L, int nsym, int sym_bytes, 
     if (nsym < 1 || nsym > imc::kMaxRawAlphabet) return fail(IMC_ERR_ARG, "nsym must be in [1," + std::to_string(imc::kMaxRawAlphabet) + "]");
     if (sym_bytes == 1 && nsym > imc::kByteAlphabet) return fail(IMC_ERR_ARG, "byte symbols cannot carry more than 256 symbols");
     if (L && !d_sym) return fail(IMC_ERR_ARG, "d_sym is null");
-    if (L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, "chunk too long (limit 2^31-1 columns per chunk)");
+    if (int rc = check_columns(L)) return rc;
     return obs_from_device(d_sym, L, nsym, sym_bytes, (hipStream_t)hip_stream, out);
 }
 
@@ -3750,10 +3681,7 @@ int imc_obs_token_counts(const imc_obs *obs, int alphabet_limit, uint32_t *count
 
 int imc_set_device_encoding(int mode)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, "device encoding mode must be 0 (host encoder) or 1 (device encoder)");
-    g.device_encode = mode;
-    return IMC_OK;
+    return set_device_mode(&imc::Options::device_encode, mode, "device encoding mode must be 0 (host encoder) or 1 (device encoder)");
 }
 
 int imc_obs_free(imc_obs *obs)
@@ -3813,7 +3741,7 @@ int imc_forward_batch_device(const imc_obs *const *chunks, int n_chunks, int B, 
     if (int rc = build_plan(chunks, n_chunks, N, S, B, false, &p)) return rc;
     // no stream synchronisation here: the parameters go through the two-slot pinned staging (stage_params waits only
     // for the upload issued two calls ago), and nothing is read back - the call returns once everything is enqueued
-    if (int rc = stage_params(p, pis, Ts, Es, g.use_graphs)) return rc;
+    if (int rc = stage_params(p, pis, Ts, Es, p->key.opt.use_graphs)) return rc;
     if (int rc = enqueue(p, st, p->d_out.get())) return rc;
     ++p->calls;
     publish_last(p);
@@ -3825,7 +3753,7 @@ int imc_forward_batch_device(const imc_obs *const *chunks, int n_chunks, int B, 
 int imc_set_segment_length(size_t columns)
 {
     std::lock_guard<std::mutex> lk(g_mu);
-    g.seg_override = columns;
+    g.opt.seg_override = columns;
     return IMC_OK;
 }
 
@@ -3833,8 +3761,8 @@ int imc_set_compression(int mode)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     if (mode < 0 || mode > 5) return fail(IMC_ERR_ARG, "compression mode must be in [0,5]");
-    g.compression = (mode == 1 || mode == 2 || mode == 3) ? 1 : 0;
-    g.kernel_pref = (mode == 2 || mode == 4) ? 1 : (mode == 3 || mode == 5) ? 2 : 0;
+    g.opt.compression = (mode == 1 || mode == 2 || mode == 3) ? 1 : 0;
+    g.opt.kernel_pref = (mode == 2 || mode == 4) ? 1 : (mode == 3 || mode == 5) ? 2 : 0;
     return IMC_OK;
 }
 
@@ -3883,10 +3811,8 @@ const char *imc_last_kernels(void)
 
 int imc_set_rank1_handoff(int on)
 {
-    std::unique_lock<std::mutex> lk(g_mu);
-    wait_all_idle(lk);
-    if (g.rank1_handoff != (on != 0)) drop_plans();   // cached plans were built for the other setting
-    g.rank1_handoff = on != 0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    g.opt.rank1_handoff = on != 0;          // (part of the plan key, as every option below: cached plans of the other setting stay valid)
     return IMC_OK;
 }
 
@@ -3902,7 +3828,7 @@ int imc_set_blocked_kernel(int variant)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     if (variant < 2 || variant > 5) return fail(IMC_ERR_ARG, "blocked kernel variant must be 2 (VALU/DPP), 3 (fp64 MFMA, LDS table), 4 (+ hybrid table, default) or 5 (hybrid wherever possible)");
-    g.blocked_variant = variant;            // (part of the plan key: cached plans of the other variant stay valid)
+    g.opt.blocked_variant = variant;
     return IMC_OK;
 }
 
@@ -3910,7 +3836,7 @@ int imc_set_table_streaming(int mode)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     if (mode < -1 || mode > 1) return fail(IMC_ERR_ARG, "table streaming mode must be -1 (automatic), 0 (hybrid LDS cache) or 1 (streamed)");
-    g.z4_stream = mode;                     // (part of the plan key)
+    g.opt.z4_stream = mode;
     return IMC_OK;
 }
 
@@ -3918,7 +3844,7 @@ int imc_set_wide_blocked(int mode)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     if (mode < -1 || mode > 1) return fail(IMC_ERR_ARG, "wide blocked mode must be -1 (automatic), 0 (never) or 1 (wherever possible)");
-    g.wide_blocked = mode;                  // (part of the plan key)
+    g.opt.wide_blocked = mode;
     return IMC_OK;
 }
 

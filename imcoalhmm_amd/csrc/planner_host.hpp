@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "options_host.hpp"
 #include "pair_dict.hpp"
 #include "plan_host.hpp"
 
@@ -55,12 +56,10 @@ enum class GroupKind {
     MatVecChain,     // ... every chunk is one segment: mat-vec chain (k_big_vector), no operators
 };
 
-// What the planner reads of the context and the environment; build_plan fills one per call.
-struct PlanOptions {
+// What the planner reads: the options record (options_host.hpp; the planner's own fields are its first group), the
+// device's size and the per-call variables; build_plan fills one per call and the plan keeps it.
+struct PlanOptions : Options {
     int cus = 256;
-    int compression = 1, kernel_pref = 0, blocked_variant = 4, wide_blocked = -1, z4_stream = -1;   // (as in the context)
-    bool xcd_affine = true, table_pairs = true, rank1_handoff = true;
-    size_t seg_override = 0;
     int force_level = -1;              // IMC_FORCE_LEVEL (experiments only: pin the dictionary level index), -1 when none
     bool debug = false;                // IMC_DEBUG: the estimates of the families considered, on stderr
     bool debug_levels = false;         // IMC_DEBUG_LEVELS: ... of every dictionary level considered

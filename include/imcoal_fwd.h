@@ -34,30 +34,38 @@
  * imc_obs_create_device) runs on the library's stream with the mutex held.  Device ingestion (imc_set_device_ingest(1),
  * imc_obs_create_pairwise, imc_aln_open_fasta) reads its file outside the mutex and holds it for its launches.
  *
- * Environment (diagnostics only, read when a plan is built / the context is created):
- *   IMC_DEBUG=1        print the planner's cost estimates to stderr
- *   IMC_FORCE_LEVEL=k  pin the pair-dictionary level index (experiments; ignored if the level does not fit)
+ * Environment.  csrc/options_host.hpp holds the table (imc::kOptionVars: name, field, parse rule, when it is read); this
+ * list names the same set.  Read at every context creation (first library call; again after imc_set_device moves to
+ * another device) unless it says otherwise:
  *   IMC_GRAPH=1        replay each plan as a hipGraph (measured: no gain)
  *   IMC_GUARD=1        test facility: every device buffer is its own virtual-memory mapping that ends flush against an
  *                      unmapped range, so any access past a buffer's end faults at once (tests/test_gpu_guard.py)
- *   IMC_DEBUG_R1=1     print where each operator segment was certified rank one (hand-off checkpoints) to stderr
- *   IMC_DEBUG_HOST=1   print the host time per phase of the synchronous entry points (plan, stage, enqueue, wait)
- *                      and of chunk creation / imc_obs_recompress (copy back, training, encoding, upload)
+ *   IMC_BLOCKED=2..5, IMC_RANK1=0, IMC_Z4_STREAM=-1|0|1, IMC_WIDE_BLOCKED=-1|0|1   see the setters below
+ *   IMC_DEVICE_ENCODE=0|1 (context creation), IMC_DEVICE_INGEST=0|1, IMC_DEVICE_TRAIN=0|1 (first use): the device
+ *                      switches, consulted only while their setter has not been called
  *   A/B switches for measurements (the default is the faster setting): IMC_TABLE_PAIRS=0 (k_zpropagate4's table one
  *   dictionary depth per launch instead of two), IMC_PACK_TABLE=0 (the mat-vec chain reads the 16-padded operator
- *   table), IMC_Z4_STREAM / IMC_BLOCKED / IMC_RANK1 (see the setters below), IMC_DICT_MIN_COUNT=n and
- *   IMC_DICT_MAX_DEPTH=d (dictionary training: occurrences a pair needs; cap on a token's depth),
- *   IMC_FUSE_HEAD=0 (the parameters fetched by a k_stage_params launch and the raw operators built by k_z4_raw, instead
- *   of by the evaluation's first table launch / by each workgroup of a small launch), IMC_TABLE_SPLIT=0 (every two-depth
- *   table launch builds four tokens per wavefront; by default a launch of at most IMC_TABLE_SPLIT_MAX entries x parameter
- *   sets - four per compute unit - gives each token a wavefront and splits its products by column tile over the four
- *   MFMA blocks: same bits, shorter launches), IMC_TABLE_TRIPLES=0|1 (three
- *   dictionary depths per table launch, one wavefront per token: never / always; default: up to 12 states, where it is 2 % faster), IMC_FUSE_TAIL=0|1|2 (the chunk's
- *   last workgroup finishes the chunk instead of stitch launches: never / chunks of at most four workgroups (default) /
- *   wherever a chunk is at most 32 workgroups; 2 changes results by re-association only),
+ *   table), IMC_FUSE_HEAD=0 (the parameters fetched by a k_stage_params launch and the raw operators built by k_z4_raw,
+ *   instead of by the evaluation's first table launch / by each workgroup of a small launch), IMC_TABLE_SPLIT=0 (every
+ *   two-depth table launch builds four tokens per wavefront; by default a launch of at most IMC_TABLE_SPLIT_MAX entries x
+ *   parameter sets - four per compute unit - gives each token a wavefront and splits its products by column tile over
+ *   the four MFMA blocks: same bits, shorter launches), IMC_TABLE_TRIPLES=0|1 (three dictionary depths per table launch,
+ *   one wavefront per token: never / always; default: up to 12 states, where it is 2 % faster), IMC_FUSE_TAIL=0|1|2 (the
+ *   chunk's last workgroup finishes the chunk instead of stitch launches: never / chunks of at most four workgroups
+ *   (default) / wherever a chunk is at most 32 workgroups; 2 changes results by re-association only),
  *   IMC_XCD_AFFINE=0 (k_zpropagate4 on a plain (blocks, parameter sets) grid: by default its one-dimensional grid puts all
  *   workgroups of a parameter set on one XCD - two or four for the last B % 8 sets - so that a set's operator table is read
- *   through one L2 instead of all eight; placement only, every bit of every result is the same)
+ *   through one L2 instead of all eight; placement only, every bit of every result is the same), IMC_CHAIN_LDS=1 (the
+ *   stitch's chain step hands its vector round through LDS, not lane to lane)
+ * Read at every call that uses them (tests set them between calls of one process):
+ *   IMC_DEBUG=1        print the planner's cost estimates to stderr; IMC_DEBUG_LEVELS=1: of every dictionary level
+ *   IMC_FORCE_LEVEL=k  pin the pair-dictionary level index (experiments; ignored if the level does not fit)
+ *   IMC_DEBUG_R1=1     print where each operator segment was certified rank one (hand-off checkpoints) to stderr
+ *   IMC_DICT_MIN_COUNT=n, IMC_DICT_MAX_DEPTH=d   dictionary training: occurrences a pair needs; cap on a token's depth
+ *   IMC_INGEST_SLAB_BYTES   slab size of device ingestion (below); IMC_SAMPLE_TILE, IMC_SAMPLE_LDS: imcoal_sample.h
+ * Read once per process, at the first call that uses it:
+ *   IMC_DEBUG_HOST=1   print the host time per phase of the synchronous entry points (plan, stage, enqueue, wait)
+ *                      and of chunk creation / imc_obs_recompress (copy back, training, encoding, upload)
  *
  * fork(): a child forked AFTER the parent's first imc_* call gets IMC_ERR_HIP from every call (HIP state does not
  * survive fork and nothing of the parent's is touched); fork chain processes first, or use the spawn start method.

@@ -7,7 +7,11 @@ The planner's decisions (csrc/planner_host.hpp) the same way: tests/planner_host
 dictionaries, puts small stand-ins behind the kernel table's LDS size functions and sweeps states, parameter sets, chunk
 sets, compression modes, a forced segment length and the operator mode through decide_groups(), checking the grouping,
 the kernel family against the gates, segment lengths, the chain's slot target, the rank-one checkpoints, forced
-dictionary levels and determinism."""
+dictionary levels and determinism.
+
+The options record (csrc/options_host.hpp) the same way: tests/options_host_check.cpp checks the defaults, what every
+environment variable's text does to its field and when (through an injected lookup, not setenv), that a device switch
+the API has set is not overridden, and which fields the plan-key comparison covers."""
 import os
 import shutil
 import subprocess
@@ -37,3 +41,7 @@ def test_plan_host_under_asan_ubsan(tmp_path):
 
 def test_planner_host_under_asan_ubsan(tmp_path):
     _check_under_asan_ubsan(tmp_path, "planner_host_check", "planner_host ok")
+
+
+def test_options_host_under_asan_ubsan(tmp_path):
+    _check_under_asan_ubsan(tmp_path, "options_host_check", "options_host ok")
