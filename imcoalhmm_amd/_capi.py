@@ -78,6 +78,10 @@ SIGNATURES = [
       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
     ("imc_encode_triplet", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _u8p]),
     ("imc_aln_open_fasta", ctypes.c_int, [ctypes.c_char_p, _vpp]),
+    ("imc_read_phylip", ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    ("imc_aln_open_phylip", ctypes.c_int, [ctypes.c_char_p, _vpp]),
     ("imc_aln_count", ctypes.c_int, [ctypes.c_void_p]),
     ("imc_aln_name", ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int]),
     ("imc_aln_length", ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),

@@ -1437,6 +1437,121 @@ int aln_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_b
     return IMC_OK;
 }
 
+}  // namespace
+
+// (the PHYLIP kernels, with phylip_tiles.hpp and phylip_io.hpp, in front of their only users)
+#include "kernels_phylip.hpp"
+
+namespace {
+
+// imc_aln_open_phylip: the same slabs and staging buffers, parsed by kernels_phylip.hpp (the rules: phylip_tiles.hpp).
+// PHYLIP file of file_bytes bytes, fp at its start, into a (empty).  The host parses the header line from the first slab's
+// staged bytes and sizes the resident buffer (n * length, record r at r * length), the line table and the name table from
+// it; a slab is cut anywhere, and the cursor at the end of slab k is read from its total before slab k + 1 is queued.
+// After the last slab the name lengths, the names and the last n lines of the line table come back: every record's kept
+// bytes must be the header's length.  *declined: the device parser does not take this file; a holds nothing then.
+int phy_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, imc_aln *a, bool *declined)
+{
+    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
+    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(imc::kPhyMaxLines, file_bytes / 2 + 2);   // (a counted line behind another takes two bytes)
+    const uint64_t lines_max = slab / 2 + 2;                              // lines that can start in one slab
+    IngestStage st;
+    DevBuf<uint8_t> bases, names;
+    DevBuf<imc::PhySummary> sums;
+    DevBuf<imc::PhyCursor> tile_in;
+    DevBuf<imc::PhyTotal> total;
+    DevBuf<uint32_t> cnt, off, nlen, part;
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::PhyTotal))) return rc;
+    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::PhySummary)));
+    HIP_TRY(tile_in.alloc(tiles_max * sizeof(imc::PhyCursor)));
+    HIP_TRY(total.alloc(sizeof(imc::PhyTotal)));
+    HIP_TRY(cnt.alloc((size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(off.alloc((size_t)cap * sizeof(uint32_t)));
+    imc::PhyTotal *verdict = static_cast<imc::PhyTotal *>(st.pinned);
+    imc::PhylipHeader header;
+    imc::PhyCursor at{imc::kPhyCol0, 0u, 0u, 0u};
+    uint64_t sent = 0, slabs = 0;
+    uint32_t prev = '\n', nrec = 0, length = 0, rows = 0, pieces = 0;
+    bool at_eof = false;
+    lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
+    const int end = imc::slab_stream(
+        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [&](const uint8_t *, size_t fill, bool last) { at_eof = last; return fill; },
+        [&](int cur, size_t cut) -> int {
+            Relock held(lk);
+            HIP_TRY(hipSetDevice(g.device));
+            if (!slabs) {                                               // the header, and what is sized from it
+                if (!imc::phy_first_slab_header(st.host[cur], cut, at_eof, file_bytes, header)) return imc::kSlabDeclined;
+                nrec = (uint32_t)header.n;
+                length = (uint32_t)header.length;
+                rows = imc::phy_chain_rows(lines_max, nrec);
+                pieces = imc::phy_chain_pieces(lines_max, nrec, rows);
+                HIP_TRY(bases.alloc((size_t)std::max<uint64_t>(16, ((uint64_t)nrec * length + 15) & ~(uint64_t)15)));
+                HIP_TRY(names.alloc((size_t)nrec * imc::kPhyNameMax));
+                HIP_TRY(nlen.alloc((size_t)nrec * sizeof(uint32_t)));
+                HIP_TRY(part.alloc((size_t)pieces * nrec * sizeof(uint32_t)));
+                HIP_TRY(hipMemsetAsync(cnt.get(), 0, (size_t)cap * sizeof(uint32_t), g.stream));
+                HIP_TRY(hipMemsetAsync(nlen.get(), 0, (size_t)nrec * sizeof(uint32_t), g.stream));
+                HIP_TRY(hipMemsetAsync(names.get(), 0, (size_t)nrec * imc::kPhyNameMax, g.stream));
+                HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(imc::PhyTotal), g.stream));
+            }
+            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE);
+            const uint32_t units = (uint32_t)(((uint64_t)pieces * nrec + TILE_THREADS - 1) / TILE_THREADS);
+            const uint8_t *d_slab = st.dev[cur].get();
+            HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
+            hipLaunchKernelGGL(k_phy_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, sums.get());
+            hipLaunchKernelGGL(k_phy_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::PhySummary *)sums.get(), tiles, at, tile_in.get(), total.get());
+            hipLaunchKernelGGL(k_phy_count, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, (const imc::PhyCursor *)tile_in.get(), nrec, cnt.get(), nlen.get(),
+                               cap);
+            hipLaunchKernelGGL(k_phy_partial, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), (const imc::PhyTotal *)total.get(), at.lines, cap,
+                               nrec, rows, pieces, part.get());
+            hipLaunchKernelGGL(k_phy_offsets, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), off.get(), (const uint32_t *)part.get(),
+                               (const imc::PhyTotal *)total.get(), at.lines, cap, nrec, rows, pieces);
+            hipLaunchKernelGGL(k_phy_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, (const imc::PhyCursor *)tile_in.get(), nrec, length,
+                               (const uint32_t *)off.get(), cap, bases.get(), names.get(), total.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::PhyTotal), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipEventRecord(st.done[cur], g.stream));
+            sent += cut;
+            ++slabs;
+            return IMC_OK;
+        },
+        [&](int cur, size_t cut) -> int {
+            const hipError_t waited = hipEventSynchronize(st.done[cur]);
+            Relock held(lk);
+            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
+            const imc::PhyTotal t = verdict[cur];
+            // (an open line far beyond the header's length cannot belong to a record of that length: its counters stay 32-bit)
+            if (t.decline || t.flags || t.end.lines > cap || t.end.P > (uint64_t)length + imc::kPhyNameMax) return imc::kSlabDeclined;
+            at = t.end;
+            prev = st.host[cur][cut - 1];
+            return IMC_OK;
+        });
+    lk.lock();
+    if (end == imc::kSlabDeclined || (end == imc::kSlabDone && (!slabs || at.lines < (uint64_t)nrec + 1))) { *declined = true; return IMC_OK; }
+    if (end != imc::kSlabDone) return end;
+    // the names and every record's kept bytes: the last n lines of the table hold one line of every record
+    std::vector<uint32_t> name_len(nrec), tail_cnt(nrec), tail_off(nrec);
+    std::vector<char> name_bytes((size_t)nrec * imc::kPhyNameMax);
+    HIP_TRY(hipSetDevice(g.device));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    HIP_TRY(hipMemcpy(name_len.data(), nlen.get(), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(name_bytes.data(), names.get(), name_bytes.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tail_cnt.data(), cnt.get() + (at.lines - nrec), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tail_off.data(), off.get() + (at.lines - nrec), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::set<std::string> seen;
+    for (uint32_t r = 0; r < nrec; ++r) {
+        if ((uint64_t)tail_off[r] + tail_cnt[r] != length || name_len[r] == 0 || name_len[r] >= imc::kPhyNameMax) { *declined = true; return IMC_OK; }
+        a->names.emplace_back(name_bytes.data() + (size_t)r * imc::kPhyNameMax, name_len[r]);
+        a->start.push_back((uint64_t)r * length);
+        a->length.push_back(length);
+        if (!seen.insert(a->names.back()).second) { *declined = true; return IMC_OK; }
+    }
+    a->d_bases = bases.release();                                       // the alignment owns the buffer now
+    a->info[0] = 1; a->info[1] = sent; a->info[2] = slabs; a->info[3] = nrec;
+    return IMC_OK;
+}
+
 // The records of the host reader into a: one buffer of the bases' size, uploaded record by record.
 int aln_upload_host(const imc::FastaRecords &r, imc_aln *a)
 {
@@ -1455,8 +1570,11 @@ int aln_upload_host(const imc::FastaRecords &r, imc_aln *a)
     return IMC_OK;
 }
 
-// imc_aln_open_fasta (arguments checked).  Opening the file needs no device.
-int aln_open(const char *path, imc_aln **out)
+// imc_aln_open_fasta, imc_aln_open_phylip (arguments checked): the format says which device parser runs and which host
+// reader takes a file it declines.  Opening the file needs no device.
+enum AlnFormat { kAlnFasta, kAlnPhylip };
+
+int aln_open(const char *path, AlnFormat format, imc_aln **out)
 {
     FILE *fp = std::fopen(path, "rb");
     if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
@@ -1473,14 +1591,14 @@ int aln_open(const char *path, imc_aln **out)
         a->pid = g.pid;
         a->device = g.device;
         if (regular) {
-            const int rc = aln_parse_device(lk, fp, (uint64_t)sb.st_size, a.get(), &declined);
+            const int rc = (format == kAlnFasta ? aln_parse_device : phy_parse_device)(lk, fp, (uint64_t)sb.st_size, a.get(), &declined);
             if (rc != IMC_OK) { (void)hipStreamSynchronize(g.stream); return rc; }
         }
     }
     if (declined) {                                     // the host reader, from the start of the file, without g_mu
         a->names.clear(); a->start.clear(); a->length.clear();
         imc::FastaRecords records;
-        const imc::IoResult r = imc::read_fasta(path, records);
+        const imc::IoResult r = format == kAlnFasta ? imc::read_fasta(path, records) : imc::read_phylip(path, records);
         if (r.code) return fail(r.code, r.msg);
         std::unique_lock<std::mutex> lk(g_mu);
         if (int rc = aln_upload_host(records, a.get())) {
@@ -3490,12 +3608,9 @@ int imc_encode_triplet(const char *seq1, const char *seq2, const char *seq3, siz
     return IMC_OK;
 }
 
-int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
+// imc_read_fasta, imc_read_phylip: record `index` of what the host reader gave, into the caller's buffers.
+static int copy_record(const imc::FastaRecords &r, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
 {
-    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
-    imc::FastaRecords r;
-    const imc::IoResult io = imc::read_fasta(path, r);
-    if (io.code) return fail(io.code, io.msg);
     *count = (int)r.names.size();
     if (index < 0 || (size_t)index >= r.names.size()) {
         if (length) *length = 0;
@@ -3508,10 +3623,34 @@ int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capa
     return IMC_OK;
 }
 
+int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
+{
+    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
+    imc::FastaRecords r;
+    const imc::IoResult io = imc::read_fasta(path, r);
+    if (io.code) return fail(io.code, io.msg);
+    return copy_record(r, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
+}
+
+int imc_read_phylip(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
+{
+    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
+    imc::FastaRecords r;
+    const imc::IoResult io = imc::read_phylip(path, r);
+    if (io.code) return fail(io.code, io.msg);
+    return copy_record(r, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
+}
+
 int imc_aln_open_fasta(const char *path, imc_aln **out)
 {
     if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
-    return aln_open(path, out);
+    return aln_open(path, kAlnFasta, out);
+}
+
+int imc_aln_open_phylip(const char *path, imc_aln **out)
+{
+    if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
+    return aln_open(path, kAlnPhylip, out);
 }
 
 int imc_aln_count(const imc_aln *aln) { return aln ? (int)aln->names.size() : 0; }

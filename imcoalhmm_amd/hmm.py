@@ -337,13 +337,21 @@ class Alignment(object):
     ``SeqIO.to_dict`` at scripts/prepare-alignments.py:66.  The records are found on the device; a file the device parser
     declines is read by the host reader (``parser`` says which, "device" or "host"), with the same result.  Any pair's or
     triplet's chunk is then built from the resident sequences (``forwarder``, ``pairs``) without a sequence on the host or
-    an upload per pair.  Use as a context manager, or ``close()``; chunks built from it stay valid."""
+    an upload per pair.  Use as a context manager, or ``close()``; chunks built from it stay valid.
 
-    def __init__(self, path):
+    ``in_format="phylip"`` opens a PHYLIP file the same way (``imc_aln_open_phylip``), sequential or interleaved, as
+    ``prepare.read_phylip`` reads it: the format of seq-gen's output that the reference's simulation workflows prepare."""
+
+    FORMATS = {"fasta": "imc_aln_open_fasta", "phylip": "imc_aln_open_phylip"}
+
+    def __init__(self, path, in_format="fasta"):
         self._h = None
+        if in_format not in self.FORMATS:
+            raise ValueError("in_format must be 'fasta' or 'phylip', got %r" % (in_format,))
+        self.in_format = in_format
         h = ctypes.c_void_p()
         L = _capi.lib()
-        _capi.check(L.imc_aln_open_fasta(os.fsencode(path), ctypes.byref(h)))
+        _capi.check(getattr(L, self.FORMATS[in_format])(os.fsencode(path), ctypes.byref(h)))
         self._h = h.value
         self._pid = os.getpid()
         self.path = path

@@ -84,16 +84,26 @@ def encode_triplet(seq1, seq2, seq3):
 def read_fasta_native(path):
     """``read_fasta`` by the library's host reader (``imc_read_fasta``, csrc/fasta_io.hpp): {name: bytes} in file order
     for ASCII files; IOError for a header without a name and for a byte >= 0x80."""
-    L = _capi.lib()
+    return _read_native(_capi.lib().imc_read_fasta, path)
+
+
+def read_phylip_native(path):
+    """``read_phylip`` by the library's host reader (``imc_read_phylip``, csrc/phylip_io.hpp): {name: bytes} in file order
+    for ASCII files; IOError for what that header lists - a bad header, too few name lines, a repeated name, a record whose
+    length differs from the header's, a byte >= 0x80."""
+    return _read_native(_capi.lib().imc_read_phylip, path)
+
+
+def _read_native(read, path):
     count, length = ctypes.c_int(0), ctypes.c_size_t(0)
-    _capi.check(L.imc_read_fasta(os.fsencode(path), -1, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
+    _capi.check(read(os.fsencode(path), -1, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
     out = {}
     for k in range(count.value):
-        _capi.check(L.imc_read_fasta(os.fsencode(path), k, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
+        _capi.check(read(os.fsencode(path), k, None, 0, None, 0, ctypes.byref(length), ctypes.byref(count)))
         room = 4096
         while True:                                     # (a name is never empty: grow the buffer until it fits)
             name, seq = ctypes.create_string_buffer(room), ctypes.create_string_buffer(max(length.value, 1))
-            _capi.check(L.imc_read_fasta(os.fsencode(path), k, name, len(name), seq, length.value, ctypes.byref(length), ctypes.byref(count)))
+            _capi.check(read(os.fsencode(path), k, name, len(name), seq, length.value, ctypes.byref(length), ctypes.byref(count)))
             if name.value:
                 break
             room *= 16

@@ -153,6 +153,23 @@ typedef struct imc_aln imc_aln;   /* an alignment whose sequences are resident i
  * bases' size for the host reader), kept as it is - it is NOT trimmed to the bases after the parse (headers and line
  * breaks are under 2 % of a wrapped file) - plus, during the call, the two slabs and the tile tables. */
 int imc_aln_open_fasta(const char *path, imc_aln **out);
+/* Open a PHYLIP file ONCE, sequential (one line per record, seq-gen's output) or interleaved: the same contract, slabs,
+ * staging buffers, errors and memory notes as imc_aln_open_fasta, with the parser of csrc/kernels_phylip.hpp.  The result is
+ * what imc_read_phylip gives for the same file, i.e. what prepare.read_phylip defines - not the PHYLIP standard: wrapped
+ * sequential records and strict 10-column names without a blank are read as that function reads them.  The host parses the
+ * header line from the first slab; the device numbers the non-blank lines, keeps a table of every line's kept bytes, and
+ * writes record r at r * length of a buffer of exactly n * length bytes (rounded up to 16) and the names into a table of
+ * its own, so a slab may end anywhere, a name included.  The device parser takes lines that end in "\n" or "\r\n", a
+ * header of two digit-only words separated and surrounded by spaces only, name lines that start at column 0 with a name
+ * of the bytes 0x21-0x7e followed by nothing or by spaces and then bytes 0x21-0x7e and spaces, later lines of those bytes
+ * and spaces, and empty or spaces-only lines anywhere.  It DECLINES anything else - a tab or any other control byte, a
+ * lone '\r', a byte >= 0x80, a space in front of a name, a third header word, a header line that does not end inside the
+ * first slab, n == 0, n > 4096, n * length larger than the file, length >= 2^31, a name of 256 bytes or more, a repeated
+ * name, fewer than n name lines, a record whose bases differ in number from length, more than 2^24 non-blank lines - and
+ * so does anything that is not a regular file: the host reader then reads the file from its start, so every error is
+ * imc_read_phylip's.  Nothing is ever written outside the n * length bytes.  Device memory during the call, beyond the two
+ * slabs and the tile tables: eight bytes per possible line (half the file's bytes, at most 2^24 lines). */
+int imc_aln_open_phylip(const char *path, imc_aln **out);
 int imc_aln_count(const imc_aln *aln);
 const char *imc_aln_name(const imc_aln *aln, int index);          /* owned by the alignment */
 size_t imc_aln_length(const imc_aln *aln, int index);
@@ -228,6 +245,13 @@ int imc_encode_pairwise(const char *seq1, const char *seq2, size_t L, uint8_t *s
  * opened, a header without a name and a byte >= 0x80. */
 int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity,
                    char *seq_out, size_t seq_capacity, size_t *length, int *count);
+/* The same for a PHYLIP file (csrc/phylip_io.hpp, the C++ statement of prepare.read_phylip for ASCII files: sequential or
+ * interleaved, name = first word of a name line).  IMC_ERR_IO for a file that cannot be opened, a byte >= 0x80, a file
+ * without a header line, a header with fewer than two words or a word that is not decimal digits only or does not fit,
+ * n == 0, fewer than n name lines, a repeated name, and a record whose length differs from the header's (the message
+ * names the record, its length and the header's). */
+int imc_read_phylip(const char *path, int index, char *name_out, size_t name_capacity,
+                    char *seq_out, size_t seq_capacity, size_t *length, int *count);
 /* The triplet rule of scripts/prepare-alignments.py:134-146: i1 + 4*i2 + 16*i3 with A,C,G,T -> 0..3 (either case),
  * 64 when any of the three bases is not in ACGT.  nsym = 65. */
 int imc_encode_triplet(const char *seq1, const char *seq2, const char *seq3, size_t L, uint8_t *sym_out);
