@@ -27,6 +27,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <set>
+#include <string>
+#include <vector>
 
 #include "fasta_io.hpp"
 #include "ingest_tiles.hpp"
@@ -239,5 +242,52 @@ inline std::string aln_header_name(const uint8_t *slab, size_t n, size_t at)
     while (end < n && slab[end] != '\n' && slab[end] != '\r') ++end;
     return fasta_first_word(slab + at, end - at);
 }
+
+// ---- what the host decides ------------------------------------------------------------------------------------
+// A FASTA file's pass: what the host carries from slab to slab, and every rule that looks at it (answers: ingest_tiles.hpp).
+struct AlnSession {
+    uint32_t state = kAlnStart0;     // the next slab is entered in it
+    uint32_t prev = '\n';            // the byte in front of the next slab
+    uint64_t kept = 0;               // bases of the slabs accepted so far
+    std::vector<std::string> names;  // of the records so far
+    std::vector<uint64_t> start;     // ... and the kept bytes in front of each
+
+    size_t cut(const uint8_t *buf, size_t fill, bool last) const { return aln_slab_cut(buf, fill, last, state); }
+
+    // t: the total of the slab (its `cut` bytes at `slab`) behind the accepted ones; room: the bases the buffer holds.
+    // fetch(first, count, recs) points recs at the records first .. first + count - 1 of the scatter's table and answers as a
+    // rule does; it is asked only for a slab that is not declined and holds a header.
+    template <class Fetch>
+    IoResult accept(const AlnTotal &t, Fetch &&fetch, const uint8_t *slab, size_t cut, uint64_t room)
+    {
+        if (t.decline || (uint64_t)names.size() + t.hdr > kMaxAlnRecords) return rule_declines();
+        if (kept + t.seq > room) return io_fail(kRuleHip, "alignment: more bases than the file can hold");
+        if (t.hdr) {                                                    // the names, from the slab's bytes
+            const AlnRecord *recs = nullptr;
+            const IoResult fetched = fetch((uint32_t)names.size(), t.hdr, recs);
+            if (fetched.code) return fetched;
+            for (uint32_t k = 0; k < t.hdr; ++k) {
+                const size_t at = (size_t)recs[k].slab_offset + 1;
+                if (at > cut || recs[k].start > kept + t.seq) return io_fail(kRuleHip, "alignment: a header outside its slab");
+                std::string name = aln_header_name(slab, cut, at - 1);
+                if (name.empty()) return rule_declines();
+                names.push_back(std::move(name));
+                start.push_back(recs[k].start);
+            }
+        }
+        kept += t.seq;
+        state = t.exit;
+        prev = slab[cut - 1];
+        return IoResult();
+    }
+
+    // Behind the last slab: a repeated name declines; else every record's length, from the starts.
+    IoResult finish(std::vector<uint64_t> &length) const
+    {
+        if (std::set<std::string>(names.begin(), names.end()).size() != names.size()) return rule_declines();
+        for (size_t k = 0; k < start.size(); ++k) length.push_back((k + 1 < start.size() ? start[k + 1] : kept) - start[k]);
+        return IoResult();
+    }
+};
 
 }  // namespace imc

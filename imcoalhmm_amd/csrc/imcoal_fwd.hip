@@ -62,6 +62,7 @@
 #include "kernels_train.hpp"
 #include "kernels_ingest.hpp"
 #include "kernels_align.hpp"
+#include "kernels_phylip.hpp"
 #include "slab_stream.hpp"
 #include "plan_host.hpp"
 #include "planner_host.hpp"
@@ -1170,65 +1171,99 @@ int ingest_pump(std::unique_lock<std::mutex> &lk, IngestStage &st, uint64_t tota
     return IMC_OK;
 }
 
-// Text file of file_bytes bytes, fp at its start.  *declined: the device parser does not take this file (a slab without
-// whitespace, a digit run beyond 16) - nothing was created, the host parser reads it from its start.  Errors are the host
-// parser's, in file order: slab k's verdict is looked at before slab k + 1 is queued.
-int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, const char *path, int nsym, imc_obs **out, bool *declined)
+// One pass of a regular file of file_bytes bytes, fp at its start, through the device parser of its format: ingest_pump's
+// counterpart for inputs that must be cut.  The slab is sized from the setting and the file, the stage gets its two
+// buffers and pinned room for two totals (and pinned_behind bytes behind them), and the file goes through
+// imc::slab_stream - read, and the carry copied, WITHOUT g_mu; uploads, launches and copies on g.stream with g_mu held;
+// slab k's total is looked at before slab k + 1 is cut.  The format says the rest:
+//   buffers(slab)                 allocate what is sized from the slab, total among it (once, in front of the loop)
+//   first(h_slab, cut)            what the first slab's bytes decide, in front of its upload (IMC_OK, kSlabDeclined, a fail())
+//   cut_of(buf, fill, last)       the format's slab rule
+//   launch(d_slab, n, tiles)      the kernels over the n bytes (tiles tiles) of the slab; they leave its Total in total
+//   accept(t, h_slab, cut)        the format's rules on that Total, an imc::IoResult; its errors become fail()
+// prefix words a failed wait.  *declined: the device parser does not take this file and the caller's host reader reads it
+// from its start; pass says how far the device got.
+struct SlabPass {
+    uint64_t sent = 0, slabs = 0;
+};
+
+int no_first_slab_work(const uint8_t *, size_t) { return IMC_OK; }
+
+static_assert(imc::kRuleSymbol == IMC_ERR_SYMBOL && imc::kRuleHip == IMC_ERR_HIP && imc::kRuleIo == IMC_ERR_IO && imc::kSlabDone == IMC_OK,
+              "the rules' codes are the library's");
+
+template <class Total, class Buffers, class First, class Cut, class Launch, class Accept>
+int slab_pass(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, const char *prefix, IngestStage &st, size_t pinned_behind, const DevBuf<Total> &total,
+              Buffers &&buffers, First &&first, Cut &&cut_of, Launch &&launch, Accept &&accept, SlabPass &pass, bool *declined)
 {
-    const bool wide = nsym > imc::kByteAlphabet;
-    const size_t unit = wide ? sizeof(imc::tok_t) : 1;
-    const uint64_t room = imc::max_tokens_in(file_bytes);
     const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
-    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
-    IngestStage st;
-    DevBuf<uint8_t> symbols;
-    DevBuf<uint16_t> flags;
-    DevBuf<imc::IngestSummary> sums, total;
-    DevBuf<uint32_t> tile_off;
-    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::IngestSummary))) return rc;
-    HIP_TRY(symbols.alloc(room * unit));
-    HIP_TRY(flags.alloc(tiles_max * TILE_THREADS * sizeof(uint16_t)));
-    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::IngestSummary)));
-    HIP_TRY(total.alloc(sizeof(imc::IngestSummary)));
-    HIP_TRY(tile_off.alloc(tiles_max * sizeof(uint32_t)));
-    imc::IngestSummary *verdict = static_cast<imc::IngestSummary *>(st.pinned);
-    uint64_t cols = 0, sent = 0, slabs = 0;
+    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(Total) + pinned_behind)) return rc;
+    if (int rc = buffers(slab)) return rc;
+    Total *verdict = static_cast<Total *>(st.pinned);
     lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
     const int end = imc::slab_stream(
-        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [](const uint8_t *buf, size_t fill, bool last) { return imc::slab_cut(buf, fill, last); },
+        st.host, slab, imc::FileSlabReader{fp, file_bytes}, cut_of,
         [&](int cur, size_t cut) -> int {
             Relock held(lk);
             HIP_TRY(hipSetDevice(g.device));
-            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE);
+            if (!pass.slabs)
+                if (int rc = first(st.host[cur], cut)) return rc;
             HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
-            hipLaunchKernelGGL(k_ing_text_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (uint32_t)nsym, flags.get(),
-                               sums.get());
-            hipLaunchKernelGGL(k_ing_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::IngestSummary *)sums.get(), tiles, tile_off.get(), total.get());
-            hipLaunchKernelGGL(k_ing_text_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, (const uint16_t *)flags.get(),
-                               (const uint32_t *)tile_off.get(), symbols.get() + cols * unit, (uint32_t)std::min<uint64_t>(room - cols, 0xffffffffu), wide ? 1 : 0);
+            launch((const uint8_t *)st.dev[cur].get(), (uint32_t)cut, (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE));
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::IngestSummary), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(Total), hipMemcpyDeviceToHost, g.stream));
             HIP_TRY(hipEventRecord(st.done[cur], g.stream));
-            sent += cut;
-            ++slabs;
+            pass.sent += cut;
+            ++pass.slabs;
             return IMC_OK;
         },
         [&](int cur, size_t cut) -> int {
             const hipError_t waited = hipEventSynchronize(st.done[cur]);
             Relock held(lk);
-            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("ingest: ") + hipGetErrorString(waited));
-            const imc::IngestSummary all = verdict[cur];
-            const imc::IngestVerdict v = imc::ingest_verdict(all, (uint32_t)cut);
-            if (v.kind == imc::kIngestDeclined) return imc::kSlabDeclined;
-            if (v.kind == imc::kIngestBadByte) return fail(IMC_ERR_IO, std::string("unexpected character in ") + path);
-            if (v.kind == imc::kIngestSymbol) return fail(IMC_ERR_SYMBOL, imc::symbol_error_text(v.value, cols + v.column, v.at_end));
-            cols += all.count;
-            if (cols > room) return fail(IMC_ERR_HIP, "ingest: more tokens than the file can hold");
-            return IMC_OK;
+            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string(prefix) + hipGetErrorString(waited));
+            const imc::IoResult r = accept(verdict[cur], st.host[cur], cut);
+            return r.code == IMC_OK || r.code == imc::kSlabDeclined ? r.code : fail(r.code, r.msg);
         });
     lk.lock();
-    if (end == imc::kSlabDeclined) { *declined = true; return IMC_OK; }
-    if (end != imc::kSlabDone) return end;
+    *declined = end == imc::kSlabDeclined;
+    return *declined ? IMC_OK : end;
+}
+
+// Text file of file_bytes bytes, fp at its start.  *declined: the device parser does not take this file (a slab without
+// whitespace, a digit run beyond 16) - nothing was created, the host parser reads it from its start.  Errors are the host
+// parser's, in file order (imc::TextSession).
+int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, const char *path, int nsym, imc_obs **out, bool *declined)
+{
+    const bool wide = nsym > imc::kByteAlphabet;
+    const size_t unit = wide ? sizeof(imc::tok_t) : 1;
+    imc::TextSession ses(file_bytes);
+    IngestStage st;
+    DevBuf<uint8_t> symbols;
+    DevBuf<uint16_t> flags;
+    DevBuf<imc::IngestSummary> sums, total;
+    DevBuf<uint32_t> tile_off;
+    SlabPass pass;
+    const int passed = slab_pass(
+        lk, fp, file_bytes, "ingest: ", st, 0, total,
+        [&](size_t slab) -> int {
+            const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
+            HIP_TRY(symbols.alloc(ses.room * unit));
+            HIP_TRY(flags.alloc(tiles_max * TILE_THREADS * sizeof(uint16_t)));
+            HIP_TRY(sums.alloc(tiles_max * sizeof(imc::IngestSummary)));
+            HIP_TRY(total.alloc(sizeof(imc::IngestSummary)));
+            HIP_TRY(tile_off.alloc(tiles_max * sizeof(uint32_t)));
+            return IMC_OK;
+        },
+        no_first_slab_work, [&](const uint8_t *buf, size_t fill, bool last) { return ses.cut(buf, fill, last); },
+        [&](const uint8_t *d_slab, uint32_t n, uint32_t tiles) {
+            hipLaunchKernelGGL(k_ing_text_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, (uint32_t)nsym, flags.get(), sums.get());
+            hipLaunchKernelGGL(k_ing_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::IngestSummary *)sums.get(), tiles, tile_off.get(), total.get());
+            hipLaunchKernelGGL(k_ing_text_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, (const uint16_t *)flags.get(), (const uint32_t *)tile_off.get(),
+                               symbols.get() + ses.cols * unit, (uint32_t)std::min<uint64_t>(ses.room - ses.cols, 0xffffffffu), wide ? 1 : 0);
+        },
+        [&](const imc::IngestSummary &all, const uint8_t *, size_t cut) { return ses.accept(all, cut, path); }, pass, declined);
+    if (passed != IMC_OK || *declined) return passed;
+    const uint64_t cols = ses.cols;
     if (int rc = check_columns(cols)) return rc;
     HIP_TRY(hipSetDevice(g.device));
     ObsOwner o = obs_new((size_t)cols, nsym);
@@ -1237,7 +1272,7 @@ int ingest_text(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes,
     st.release();
     symbols.reset();
     if (rc == IMC_OK) rc = finish_device_chunk(lk, o.get());
-    if (rc == IMC_OK) note_ingest(1, sent, slabs, cols);
+    if (rc == IMC_OK) note_ingest(1, pass.sent, pass.slabs, cols);
     return obs_finish(rc, o, out);
 }
 
@@ -1288,15 +1323,41 @@ int ingest_cache(std::unique_lock<std::mutex> &lk, FILE *fp, const imc::CacheHea
     return obs_finish(rc, o, out);
 }
 
+// A file the device parsers read: open for the length of the object; only a regular file has a size and can be read a
+// second time by the host reader that takes what the device parser declines (a pipe cannot).
+struct InputFile {
+    FILE *fp = nullptr;
+    bool regular = false;
+    uint64_t bytes = 0;
+
+    InputFile() = default;
+    InputFile(const InputFile &) = delete;
+    InputFile &operator=(const InputFile &) = delete;
+    int open(const char *path)
+    {
+        fp = std::fopen(path, "rb");
+        if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+        struct stat sb;
+        regular = fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode);
+        bytes = regular ? (uint64_t)sb.st_size : 0;
+        return IMC_OK;
+    }
+    void close()
+    {
+        if (fp) std::fclose(fp);
+        fp = nullptr;
+    }
+    ~InputFile() { close(); }
+};
+
 // imc_obs_create_from_text on the device path (arguments checked).  Opening the file, its size, the magic and the cache
 // header are the host's business and need no device.
 int obs_from_file_device(const char *path, int nsym, imc_obs **out, bool *declined)
 {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
-    struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{fp};
-    struct stat sb;
-    if (fstat(fileno(fp), &sb) != 0 || !S_ISREG(sb.st_mode)) { *declined = true; return IMC_OK; }   // (a pipe cannot be read twice)
+    InputFile in;
+    if (int rc = in.open(path)) return rc;
+    if (!in.regular) { *declined = true; return IMC_OK; }
+    FILE *fp = in.fp;
     char head[8];
     const size_t nh = std::fread(head, 1, 8, fp);
     const bool cache = nh == 8 && std::memcmp(head, imc::kCacheMagic, 8) == 0;
@@ -1311,7 +1372,7 @@ int obs_from_file_device(const char *path, int nsym, imc_obs **out, bool *declin
     std::unique_lock<std::mutex> lk(g_mu);
     if (int rc = ensure_ctx()) return rc;
     HIP_TRY(hipSetDevice(g.device));
-    return cache ? ingest_cache(lk, fp, h, path, nsym, out) : ingest_text(lk, fp, (uint64_t)sb.st_size, path, nsym, out, declined);
+    return cache ? ingest_cache(lk, fp, h, path, nsym, out) : ingest_text(lk, fp, in.bytes, path, nsym, out, declined);
 }
 
 // imc_obs_create_pairwise (arguments checked): the rule of imc::encode_pairwise on the device, nsym = 3.
@@ -1362,87 +1423,54 @@ void aln_release(imc_aln *a)
 // a holds nothing then.
 int aln_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, imc_aln *a, bool *declined)
 {
-    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
-    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
     const uint64_t room = (file_bytes + 15) & ~(uint64_t)15;
+    imc::AlnSession ses;
     IngestStage st;
     DevBuf<uint8_t> bases;
     DevBuf<imc::AlnSummary> sums;
     DevBuf<AlnTileIn> tile_in;
     DevBuf<imc::AlnTotal> total;
     DevBuf<imc::AlnRecord> table;
-    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::AlnTotal) + imc::kMaxAlnRecords * sizeof(imc::AlnRecord))) return rc;
-    HIP_TRY(bases.alloc((size_t)room));
-    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::AlnSummary)));
-    HIP_TRY(tile_in.alloc(tiles_max * sizeof(AlnTileIn)));
-    HIP_TRY(total.alloc(sizeof(imc::AlnTotal)));
-    HIP_TRY(table.alloc(imc::kMaxAlnRecords * sizeof(imc::AlnRecord)));
-    imc::AlnTotal *verdict = static_cast<imc::AlnTotal *>(st.pinned);   // two totals, then the record table
-    imc::AlnRecord *recs = reinterpret_cast<imc::AlnRecord *>(verdict + 2);
-    uint64_t kept = 0, sent = 0, slabs = 0;
-    uint32_t state = imc::kAlnStart0, prev = '\n';
-    lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
-    const int end = imc::slab_stream(
-        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [&](const uint8_t *buf, size_t fill, bool last) { return imc::aln_slab_cut(buf, fill, last, state); },
-        [&](int cur, size_t cut) -> int {
-            Relock held(lk);
+    SlabPass pass;
+    // a slab's records come back into pinned memory behind the two totals: the host takes the names from the slab's bytes
+    auto fetch = [&](uint32_t have, uint32_t count, const imc::AlnRecord *&recs) {
+        imc::AlnRecord *pinned = reinterpret_cast<imc::AlnRecord *>(static_cast<imc::AlnTotal *>(st.pinned) + 2);
+        const int rc = [&]() -> int {
             HIP_TRY(hipSetDevice(g.device));
-            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE), have = (uint32_t)a->names.size();
-            HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
-            hipLaunchKernelGGL(k_aln_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, sums.get());
-            hipLaunchKernelGGL(k_aln_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::AlnSummary *)sums.get(), tiles, state, tile_in.get(), total.get());
-            hipLaunchKernelGGL(k_aln_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, (const uint8_t *)st.dev[cur].get(), n, prev, (const AlnTileIn *)tile_in.get(),
-                               bases.get(), kept, room, table.get(), have, imc::kMaxAlnRecords);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::AlnTotal), hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipEventRecord(st.done[cur], g.stream));
-            sent += cut;
-            ++slabs;
+            HIP_TRY(hipMemcpyAsync(pinned, table.get() + have, count * sizeof(imc::AlnRecord), hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            return IMC_OK;
+        }();
+        recs = pinned;
+        return rc == IMC_OK ? imc::IoResult() : imc::io_fail(rc, g_err);
+    };
+    const int passed = slab_pass(
+        lk, fp, file_bytes, "alignment: ", st, imc::kMaxAlnRecords * sizeof(imc::AlnRecord), total,
+        [&](size_t slab) -> int {
+            const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
+            HIP_TRY(bases.alloc((size_t)room));
+            HIP_TRY(sums.alloc(tiles_max * sizeof(imc::AlnSummary)));
+            HIP_TRY(tile_in.alloc(tiles_max * sizeof(AlnTileIn)));
+            HIP_TRY(total.alloc(sizeof(imc::AlnTotal)));
+            HIP_TRY(table.alloc(imc::kMaxAlnRecords * sizeof(imc::AlnRecord)));
             return IMC_OK;
         },
-        [&](int cur, size_t cut) -> int {
-            const hipError_t waited = hipEventSynchronize(st.done[cur]);
-            Relock held(lk);
-            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
-            const imc::AlnTotal t = verdict[cur];
-            const uint32_t have = (uint32_t)a->names.size();
-            if (t.decline || (uint64_t)have + t.hdr > imc::kMaxAlnRecords) return imc::kSlabDeclined;
-            if (kept + t.seq > room) return fail(IMC_ERR_HIP, "alignment: more bases than the file can hold");
-            if (t.hdr) {                                                // the names, from the slab's bytes in pinned memory
-                HIP_TRY(hipSetDevice(g.device));
-                HIP_TRY(hipMemcpyAsync(recs, table.get() + have, t.hdr * sizeof(imc::AlnRecord), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-                for (uint32_t k = 0; k < t.hdr; ++k) {
-                    const size_t at = (size_t)recs[k].slab_offset + 1;
-                    if (at > cut || recs[k].start > kept + t.seq) return fail(IMC_ERR_HIP, "alignment: a header outside its slab");
-                    std::string name = imc::aln_header_name(st.host[cur], cut, at - 1);
-                    if (name.empty()) return imc::kSlabDeclined;
-                    a->names.push_back(std::move(name));
-                    a->start.push_back(recs[k].start);
-                }
-            }
-            kept += t.seq;
-            state = t.exit;
-            prev = st.host[cur][cut - 1];
-            return IMC_OK;
-        });
-    lk.lock();
-    if (end == imc::kSlabDeclined) { *declined = true; return IMC_OK; }
-    if (end != imc::kSlabDone) return end;
-    std::set<std::string> seen(a->names.begin(), a->names.end());
-    if (seen.size() != a->names.size()) { *declined = true; return IMC_OK; }
-    for (size_t k = 0; k < a->start.size(); ++k) a->length.push_back((k + 1 < a->start.size() ? a->start[k + 1] : kept) - a->start[k]);
+        no_first_slab_work, [&](const uint8_t *buf, size_t fill, bool last) { return ses.cut(buf, fill, last); },
+        [&](const uint8_t *d_slab, uint32_t n, uint32_t tiles) {
+            hipLaunchKernelGGL(k_aln_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, ses.prev, sums.get());
+            hipLaunchKernelGGL(k_aln_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::AlnSummary *)sums.get(), tiles, ses.state, tile_in.get(), total.get());
+            hipLaunchKernelGGL(k_aln_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, ses.prev, (const AlnTileIn *)tile_in.get(), bases.get(), ses.kept, room,
+                               table.get(), (uint32_t)ses.names.size(), imc::kMaxAlnRecords);
+        },
+        [&](const imc::AlnTotal &t, const uint8_t *h_slab, size_t cut) { return ses.accept(t, fetch, h_slab, cut, room); }, pass, declined);
+    if (passed != IMC_OK || *declined) return passed;
+    if (ses.finish(a->length).code) { *declined = true; return IMC_OK; }
+    a->names = std::move(ses.names);
+    a->start = std::move(ses.start);
     a->d_bases = bases.release();                                       // the alignment owns the buffer now
-    a->info[0] = 1; a->info[1] = sent; a->info[2] = slabs; a->info[3] = a->names.size();
+    a->info[0] = 1; a->info[1] = pass.sent; a->info[2] = pass.slabs; a->info[3] = a->names.size();
     return IMC_OK;
 }
-
-}  // namespace
-
-// (the PHYLIP kernels, with phylip_tiles.hpp and phylip_io.hpp, in front of their only users)
-#include "kernels_phylip.hpp"
-
-namespace {
 
 // imc_aln_open_phylip: the same slabs and staging buffers, parsed by kernels_phylip.hpp (the rules: phylip_tiles.hpp).
 // PHYLIP file of file_bytes bytes, fp at its start, into a (empty).  The host parses the header line from the first slab's
@@ -1452,103 +1480,70 @@ namespace {
 // bytes must be the header's length.  *declined: the device parser does not take this file; a holds nothing then.
 int phy_parse_device(std::unique_lock<std::mutex> &lk, FILE *fp, uint64_t file_bytes, imc_aln *a, bool *declined)
 {
-    const size_t slab = (size_t)std::min<uint64_t>(ingest_slab_bytes(), std::max<uint64_t>(file_bytes, imc::kMinSlabBytes));
-    const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(imc::kPhyMaxLines, file_bytes / 2 + 2);   // (a counted line behind another takes two bytes)
-    const uint64_t lines_max = slab / 2 + 2;                              // lines that can start in one slab
+    imc::PhySession ses(file_bytes);
     IngestStage st;
     DevBuf<uint8_t> bases, names;
     DevBuf<imc::PhySummary> sums;
     DevBuf<imc::PhyCursor> tile_in;
     DevBuf<imc::PhyTotal> total;
     DevBuf<uint32_t> cnt, off, nlen, part;
-    if (int rc = st.alloc(slab, file_bytes > slab ? 2 : 1, 2 * sizeof(imc::PhyTotal))) return rc;
-    HIP_TRY(sums.alloc(tiles_max * sizeof(imc::PhySummary)));
-    HIP_TRY(tile_in.alloc(tiles_max * sizeof(imc::PhyCursor)));
-    HIP_TRY(total.alloc(sizeof(imc::PhyTotal)));
-    HIP_TRY(cnt.alloc((size_t)cap * sizeof(uint32_t)));
-    HIP_TRY(off.alloc((size_t)cap * sizeof(uint32_t)));
-    imc::PhyTotal *verdict = static_cast<imc::PhyTotal *>(st.pinned);
-    imc::PhylipHeader header;
-    imc::PhyCursor at{imc::kPhyCol0, 0u, 0u, 0u};
-    uint64_t sent = 0, slabs = 0;
-    uint32_t prev = '\n', nrec = 0, length = 0, rows = 0, pieces = 0;
+    imc::PhySizes sz{};
+    SlabPass pass;
     bool at_eof = false;
-    lk.unlock();                                                        // the file is read and the carry copied WITHOUT g_mu
-    const int end = imc::slab_stream(
-        st.host, slab, imc::FileSlabReader{fp, file_bytes}, [&](const uint8_t *, size_t fill, bool last) { at_eof = last; return fill; },
-        [&](int cur, size_t cut) -> int {
-            Relock held(lk);
-            HIP_TRY(hipSetDevice(g.device));
-            if (!slabs) {                                               // the header, and what is sized from it
-                if (!imc::phy_first_slab_header(st.host[cur], cut, at_eof, file_bytes, header)) return imc::kSlabDeclined;
-                nrec = (uint32_t)header.n;
-                length = (uint32_t)header.length;
-                rows = imc::phy_chain_rows(lines_max, nrec);
-                pieces = imc::phy_chain_pieces(lines_max, nrec, rows);
-                HIP_TRY(bases.alloc((size_t)std::max<uint64_t>(16, ((uint64_t)nrec * length + 15) & ~(uint64_t)15)));
-                HIP_TRY(names.alloc((size_t)nrec * imc::kPhyNameMax));
-                HIP_TRY(nlen.alloc((size_t)nrec * sizeof(uint32_t)));
-                HIP_TRY(part.alloc((size_t)pieces * nrec * sizeof(uint32_t)));
-                HIP_TRY(hipMemsetAsync(cnt.get(), 0, (size_t)cap * sizeof(uint32_t), g.stream));
-                HIP_TRY(hipMemsetAsync(nlen.get(), 0, (size_t)nrec * sizeof(uint32_t), g.stream));
-                HIP_TRY(hipMemsetAsync(names.get(), 0, (size_t)nrec * imc::kPhyNameMax, g.stream));
-                HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(imc::PhyTotal), g.stream));
-            }
-            const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + TILE_SIZE - 1) / TILE_SIZE);
-            const uint32_t units = (uint32_t)(((uint64_t)pieces * nrec + TILE_THREADS - 1) / TILE_THREADS);
-            const uint8_t *d_slab = st.dev[cur].get();
-            HIP_TRY(hipMemcpyAsync(st.dev[cur].get(), st.host[cur], cut, hipMemcpyHostToDevice, g.stream));
-            hipLaunchKernelGGL(k_phy_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, sums.get());
-            hipLaunchKernelGGL(k_phy_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::PhySummary *)sums.get(), tiles, at, tile_in.get(), total.get());
-            hipLaunchKernelGGL(k_phy_count, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, (const imc::PhyCursor *)tile_in.get(), nrec, cnt.get(), nlen.get(),
-                               cap);
-            hipLaunchKernelGGL(k_phy_partial, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), (const imc::PhyTotal *)total.get(), at.lines, cap,
-                               nrec, rows, pieces, part.get());
-            hipLaunchKernelGGL(k_phy_offsets, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), off.get(), (const uint32_t *)part.get(),
-                               (const imc::PhyTotal *)total.get(), at.lines, cap, nrec, rows, pieces);
-            hipLaunchKernelGGL(k_phy_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, prev, (const imc::PhyCursor *)tile_in.get(), nrec, length,
-                               (const uint32_t *)off.get(), cap, bases.get(), names.get(), total.get());
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&verdict[cur], total.get(), sizeof(imc::PhyTotal), hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipEventRecord(st.done[cur], g.stream));
-            sent += cut;
-            ++slabs;
+    const int passed = slab_pass(
+        lk, fp, file_bytes, "alignment: ", st, 0, total,
+        [&](size_t slab) -> int {
+            const size_t tiles_max = (slab + TILE_SIZE - 1) / TILE_SIZE;
+            HIP_TRY(sums.alloc(tiles_max * sizeof(imc::PhySummary)));
+            HIP_TRY(tile_in.alloc(tiles_max * sizeof(imc::PhyCursor)));
+            HIP_TRY(total.alloc(sizeof(imc::PhyTotal)));
+            HIP_TRY(cnt.alloc((size_t)ses.cap * sizeof(uint32_t)));
+            HIP_TRY(off.alloc((size_t)ses.cap * sizeof(uint32_t)));
             return IMC_OK;
         },
-        [&](int cur, size_t cut) -> int {
-            const hipError_t waited = hipEventSynchronize(st.done[cur]);
-            Relock held(lk);
-            if (waited != hipSuccess) return fail(IMC_ERR_HIP, std::string("alignment: ") + hipGetErrorString(waited));
-            const imc::PhyTotal t = verdict[cur];
-            // (an open line far beyond the header's length cannot belong to a record of that length: its counters stay 32-bit)
-            if (t.decline || t.flags || t.end.lines > cap || t.end.P > (uint64_t)length + imc::kPhyNameMax) return imc::kSlabDeclined;
-            at = t.end;
-            prev = st.host[cur][cut - 1];
+        [&](const uint8_t *h_slab, size_t cut) -> int {                 // the header, and what is sized from it
+            if (ses.begin(h_slab, cut, at_eof, st.slab, sz).code) return imc::kSlabDeclined;
+            HIP_TRY(bases.alloc(sz.bases));
+            HIP_TRY(names.alloc(sz.names));
+            HIP_TRY(nlen.alloc(sz.nlen));
+            HIP_TRY(part.alloc(sz.part));
+            HIP_TRY(hipMemsetAsync(cnt.get(), 0, (size_t)ses.cap * sizeof(uint32_t), g.stream));
+            HIP_TRY(hipMemsetAsync(nlen.get(), 0, sz.nlen, g.stream));
+            HIP_TRY(hipMemsetAsync(names.get(), 0, sz.names, g.stream));
+            HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(imc::PhyTotal), g.stream));
             return IMC_OK;
-        });
-    lk.lock();
-    if (end == imc::kSlabDeclined || (end == imc::kSlabDone && (!slabs || at.lines < (uint64_t)nrec + 1))) { *declined = true; return IMC_OK; }
-    if (end != imc::kSlabDone) return end;
+        },
+        [&](const uint8_t *, size_t fill, bool last) { at_eof = last; return fill; },
+        [&](const uint8_t *d_slab, uint32_t n, uint32_t tiles) {
+            const uint32_t cap = ses.cap, nrec = ses.nrec, units = (uint32_t)(((uint64_t)sz.pieces * nrec + TILE_THREADS - 1) / TILE_THREADS);
+            hipLaunchKernelGGL(k_phy_summary, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, ses.prev, sums.get());
+            hipLaunchKernelGGL(k_phy_scan, dim3(1), dim3(TILE_SCAN_THREADS), 0, g.stream, (const imc::PhySummary *)sums.get(), tiles, ses.at, tile_in.get(), total.get());
+            hipLaunchKernelGGL(k_phy_count, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, ses.prev, (const imc::PhyCursor *)tile_in.get(), nrec, cnt.get(),
+                               nlen.get(), cap);
+            hipLaunchKernelGGL(k_phy_partial, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), (const imc::PhyTotal *)total.get(), ses.at.lines, cap,
+                               nrec, sz.rows, sz.pieces, part.get());
+            hipLaunchKernelGGL(k_phy_offsets, dim3(units), dim3(TILE_THREADS), 0, g.stream, (const uint32_t *)cnt.get(), off.get(), (const uint32_t *)part.get(),
+                               (const imc::PhyTotal *)total.get(), ses.at.lines, cap, nrec, sz.rows, sz.pieces);
+            hipLaunchKernelGGL(k_phy_scatter, dim3(tiles), dim3(TILE_THREADS), 0, g.stream, d_slab, n, ses.prev, (const imc::PhyCursor *)tile_in.get(), nrec, ses.length,
+                               (const uint32_t *)off.get(), cap, bases.get(), names.get(), total.get());
+        },
+        [&](const imc::PhyTotal &t, const uint8_t *h_slab, size_t cut) { return ses.accept(t, h_slab[cut - 1]); }, pass, declined);
+    if (passed != IMC_OK || *declined) return passed;
     // the names and every record's kept bytes: the last n lines of the table hold one line of every record
+    uint32_t line = 0;
+    if (ses.tail(line).code) { *declined = true; return IMC_OK; }
+    const uint32_t nrec = ses.nrec;
     std::vector<uint32_t> name_len(nrec), tail_cnt(nrec), tail_off(nrec);
-    std::vector<char> name_bytes((size_t)nrec * imc::kPhyNameMax);
+    std::vector<char> name_bytes(sz.names);
     HIP_TRY(hipSetDevice(g.device));
     HIP_TRY(hipStreamSynchronize(g.stream));
     HIP_TRY(hipMemcpy(name_len.data(), nlen.get(), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(name_bytes.data(), names.get(), name_bytes.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tail_cnt.data(), cnt.get() + (at.lines - nrec), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tail_off.data(), off.get() + (at.lines - nrec), (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::set<std::string> seen;
-    for (uint32_t r = 0; r < nrec; ++r) {
-        if ((uint64_t)tail_off[r] + tail_cnt[r] != length || name_len[r] == 0 || name_len[r] >= imc::kPhyNameMax) { *declined = true; return IMC_OK; }
-        a->names.emplace_back(name_bytes.data() + (size_t)r * imc::kPhyNameMax, name_len[r]);
-        a->start.push_back((uint64_t)r * length);
-        a->length.push_back(length);
-        if (!seen.insert(a->names.back()).second) { *declined = true; return IMC_OK; }
-    }
+    HIP_TRY(hipMemcpy(tail_cnt.data(), cnt.get() + line, (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tail_off.data(), off.get() + line, (size_t)nrec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ses.finish(name_len.data(), name_bytes.data(), tail_cnt.data(), tail_off.data(), a->names, a->start, a->length).code) { *declined = true; return IMC_OK; }
     a->d_bases = bases.release();                                       // the alignment owns the buffer now
-    a->info[0] = 1; a->info[1] = sent; a->info[2] = slabs; a->info[3] = nrec;
+    a->info[0] = 1; a->info[1] = pass.sent; a->info[2] = pass.slabs; a->info[3] = nrec;
     return IMC_OK;
 }
 
@@ -1570,35 +1565,39 @@ int aln_upload_host(const imc::FastaRecords &r, imc_aln *a)
     return IMC_OK;
 }
 
-// imc_aln_open_fasta, imc_aln_open_phylip (arguments checked): the format says which device parser runs and which host
-// reader takes a file it declines.  Opening the file needs no device.
+// imc_aln_open_fasta, imc_aln_open_phylip: the format says which device parser runs and which host reader takes a file it
+// declines.  Opening the file needs no device.
 enum AlnFormat { kAlnFasta, kAlnPhylip };
+
+imc::IoResult aln_read_host(AlnFormat format, const char *path, imc::FastaRecords &records)
+{
+    return format == kAlnFasta ? imc::read_fasta(path, records) : imc::read_phylip(path, records);
+}
 
 int aln_open(const char *path, AlnFormat format, imc_aln **out)
 {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return fail(IMC_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
-    struct stat sb;
-    const bool regular = fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode);   // (a pipe cannot be read twice)
+    if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
+    InputFile in;
+    if (int rc = in.open(path)) return rc;
     std::unique_ptr<imc_aln> a(new (std::nothrow) imc_aln());
-    if (!a) { std::fclose(fp); return fail(IMC_ERR_OOM, kHostAllocFailed); }
-    bool declined = !regular;
+    if (!a) return fail(IMC_ERR_OOM, kHostAllocFailed);
+    bool declined = !in.regular;
     {
-        struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{fp};
         std::unique_lock<std::mutex> lk(g_mu);
         if (int rc = ensure_ctx()) return rc;
         HIP_TRY(hipSetDevice(g.device));
         a->pid = g.pid;
         a->device = g.device;
-        if (regular) {
-            const int rc = (format == kAlnFasta ? aln_parse_device : phy_parse_device)(lk, fp, (uint64_t)sb.st_size, a.get(), &declined);
+        if (in.regular) {
+            const int rc = (format == kAlnFasta ? aln_parse_device : phy_parse_device)(lk, in.fp, in.bytes, a.get(), &declined);
             if (rc != IMC_OK) { (void)hipStreamSynchronize(g.stream); return rc; }
         }
     }
+    in.close();
     if (declined) {                                     // the host reader, from the start of the file, without g_mu
         a->names.clear(); a->start.clear(); a->length.clear();
         imc::FastaRecords records;
-        const imc::IoResult r = format == kAlnFasta ? imc::read_fasta(path, records) : imc::read_phylip(path, records);
+        const imc::IoResult r = aln_read_host(format, path, records);
         if (r.code) return fail(r.code, r.msg);
         std::unique_lock<std::mutex> lk(g_mu);
         if (int rc = aln_upload_host(records, a.get())) {
@@ -3609,8 +3608,12 @@ int imc_encode_triplet(const char *seq1, const char *seq2, const char *seq3, siz
 }
 
 // imc_read_fasta, imc_read_phylip: record `index` of what the host reader gave, into the caller's buffers.
-static int copy_record(const imc::FastaRecords &r, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
+static int read_records(AlnFormat format, const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
 {
+    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
+    imc::FastaRecords r;
+    const imc::IoResult io = aln_read_host(format, path, r);
+    if (io.code) return fail(io.code, io.msg);
     *count = (int)r.names.size();
     if (index < 0 || (size_t)index >= r.names.size()) {
         if (length) *length = 0;
@@ -3625,33 +3628,17 @@ static int copy_record(const imc::FastaRecords &r, int index, char *name_out, si
 
 int imc_read_fasta(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
 {
-    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
-    imc::FastaRecords r;
-    const imc::IoResult io = imc::read_fasta(path, r);
-    if (io.code) return fail(io.code, io.msg);
-    return copy_record(r, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
+    return read_records(kAlnFasta, path, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
 }
 
 int imc_read_phylip(const char *path, int index, char *name_out, size_t name_capacity, char *seq_out, size_t seq_capacity, size_t *length, int *count)
 {
-    if (!path || !count) return fail(IMC_ERR_ARG, "null argument");
-    imc::FastaRecords r;
-    const imc::IoResult io = imc::read_phylip(path, r);
-    if (io.code) return fail(io.code, io.msg);
-    return copy_record(r, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
+    return read_records(kAlnPhylip, path, index, name_out, name_capacity, seq_out, seq_capacity, length, count);
 }
 
-int imc_aln_open_fasta(const char *path, imc_aln **out)
-{
-    if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
-    return aln_open(path, kAlnFasta, out);
-}
+int imc_aln_open_fasta(const char *path, imc_aln **out) { return aln_open(path, kAlnFasta, out); }
 
-int imc_aln_open_phylip(const char *path, imc_aln **out)
-{
-    if (!out || !path) return fail(IMC_ERR_ARG, "null argument");
-    return aln_open(path, kAlnPhylip, out);
-}
+int imc_aln_open_phylip(const char *path, imc_aln **out) { return aln_open(path, kAlnPhylip, out); }
 
 int imc_aln_count(const imc_aln *aln) { return aln ? (int)aln->names.size() : 0; }
 

@@ -23,6 +23,9 @@
 #include <cstdlib>
 #include <string>
 
+#include "obs_io.hpp"
+#include "slab_stream.hpp"
+
 #if defined(__HIPCC__)
 #define IMC_ING_HD __host__ __device__
 #else
@@ -162,6 +165,36 @@ inline size_t slab_bytes_setting(const char *text, size_t deflt)
 
 // Upper bound of the tokens in `bytes` bytes of text (every token needs a separator but the last).
 inline uint64_t max_tokens_in(uint64_t bytes) { return (bytes + 1) / 2; }
+
+// ---- what the host decides ------------------------------------------------------------------------------------
+// A rule's answer about a slab or a file is an IoResult: code 0 goes on, kSlabDeclined hands the file to the host parser
+// (no text), every other code is an error of include/imcoal_fwd.h with its text.  The engine (imcoal_fwd.hip: slab_pass)
+// and the CPU checks call the same rules with the same arguments.
+constexpr int kRuleSymbol = -2, kRuleHip = -3, kRuleIo = -5;   // IMC_ERR_SYMBOL, IMC_ERR_HIP, IMC_ERR_IO
+
+inline IoResult rule_declines() { return io_fail(kSlabDeclined, std::string()); }
+
+// A text file's pass: what the host carries from slab to slab, and every rule that looks at it.
+struct TextSession {
+    uint64_t room;           // tokens the symbol buffer holds: the upper bound for the file's bytes
+    uint64_t cols = 0;       // tokens of the slabs accepted so far
+
+    explicit TextSession(uint64_t file_bytes) : room(max_tokens_in(file_bytes)) {}
+
+    size_t cut(const uint8_t *buf, size_t fill, bool last) const { return slab_cut(buf, fill, last); }
+
+    // all: the summary of the whole slab of n bytes behind the accepted ones.  Errors are the host parser's, in file order.
+    IoResult accept(const IngestSummary &all, size_t n, const char *path)
+    {
+        const IngestVerdict v = ingest_verdict(all, (uint32_t)n);
+        if (v.kind == kIngestDeclined) return rule_declines();
+        if (v.kind == kIngestBadByte) return io_fail(kRuleIo, std::string("unexpected character in ") + path);
+        if (v.kind == kIngestSymbol) return io_fail(kRuleSymbol, symbol_error_text(v.value, cols + v.column, v.at_end));
+        cols += all.count;
+        if (cols > room) return io_fail(kRuleHip, "ingest: more tokens than the file can hold");
+        return IoResult();
+    }
+};
 
 // ---- 2-bit cache and pairwise rule ---------------------------------------------------------------------
 IMC_ING_HD inline uint32_t unpack2(const uint8_t *pk, uint32_t t) { return (pk[t >> 2] >> (2 * (t & 3))) & 3u; }

@@ -37,6 +37,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <set>
+#include <string>
+#include <vector>
 
 #include "align_tiles.hpp"
 #include "phylip_io.hpp"
@@ -268,5 +271,89 @@ inline bool phy_first_slab_header(const uint8_t *buf, size_t n, bool at_eof, uin
     }
     return false;
 }
+
+// The limits of the device parser (the CPU check runs with smaller ones).
+struct PhyLimits {
+    uint32_t cap_lines = kPhyMaxLines;
+    uint32_t name_max = kPhyNameMax;
+};
+
+// What is sized from the header: the shape of the offsets' pieces, and the bytes of the four buffers.
+struct PhySizes {
+    uint32_t rows, pieces;
+    size_t bases, names, nlen, part;
+};
+
+// A PHYLIP file's pass: what the host carries from slab to slab, and every rule that looks at it (answers: ingest_tiles.hpp).
+struct PhySession {
+    const PhyLimits lim;
+    const uint64_t file_bytes;
+    const uint32_t cap;              // lines the line table holds (a counted line behind another takes two bytes)
+    PhyCursor at{kPhyCol0, 0u, 0u, 0u};   // the next slab is entered at it
+    uint32_t prev = '\n';            // the byte in front of the next slab
+    uint32_t nrec = 0, length = 0;   // the header's
+    bool begun = false;
+
+    explicit PhySession(uint64_t bytes, const PhyLimits &limits = PhyLimits())
+        : lim(limits), file_bytes(bytes), cap((uint32_t)(bytes / 2 + 2 < limits.cap_lines ? bytes / 2 + 2 : limits.cap_lines))
+    {
+    }
+
+    // The first slab (its `cut` bytes at `first`, of slabs of at most `slab` bytes): the header, and what is sized from it
+    // (record r at r * length).
+    IoResult begin(const uint8_t *first, size_t cut, bool at_eof, size_t slab, PhySizes &sz)
+    {
+        const uint64_t lines_max = slab / 2 + 2;                          // lines that can start in one slab
+        PhylipHeader header;
+        if (!phy_first_slab_header(first, cut, at_eof, file_bytes, header)) return rule_declines();
+        begun = true;
+        nrec = (uint32_t)header.n;
+        length = (uint32_t)header.length;
+        sz.rows = phy_chain_rows(lines_max, nrec);
+        sz.pieces = phy_chain_pieces(lines_max, nrec, sz.rows);
+        const uint64_t all = ((uint64_t)nrec * length + 15) & ~(uint64_t)15;
+        sz.bases = (size_t)(all < 16 ? 16 : all);
+        sz.names = (size_t)nrec * lim.name_max;
+        sz.nlen = (size_t)nrec * sizeof(uint32_t);
+        sz.part = (size_t)sz.pieces * nrec * sizeof(uint32_t);
+        return IoResult();
+    }
+
+    // t: the total of the slab behind the accepted ones, whose last byte is last_byte.
+    IoResult accept(const PhyTotal &t, uint8_t last_byte)
+    {
+        // (an open line far beyond the header's length cannot belong to a record of that length: its counters stay 32-bit)
+        if (t.decline || t.flags || t.end.lines > cap || t.end.P > (uint64_t)length + lim.name_max) return rule_declines();
+        at = t.end;
+        prev = last_byte;
+        return IoResult();
+    }
+
+    // Behind the last slab: a file without a slab or with fewer than n name lines declines; else `line` is the first of the
+    // last n lines of the line table, which hold one line of every record.
+    IoResult tail(uint32_t &line) const
+    {
+        if (!begun || at.lines < (uint64_t)nrec + 1) return rule_declines();
+        line = at.lines - nrec;
+        return IoResult();
+    }
+
+    // name_len[r], the lim.name_max bytes at name_bytes + r * lim.name_max: record r's name as the device wrote it;
+    // tail_cnt, tail_off: cnt[] and off[] of the n lines from tail()'s line on.  Every record's kept bytes must be the
+    // header's length, every name must fit its row and stand once.
+    IoResult finish(const uint32_t *name_len, const char *name_bytes, const uint32_t *tail_cnt, const uint32_t *tail_off, std::vector<std::string> &names,
+                    std::vector<uint64_t> &start, std::vector<uint64_t> &lengths) const
+    {
+        std::set<std::string> seen;
+        for (uint32_t r = 0; r < nrec; ++r) {
+            if ((uint64_t)tail_off[r] + tail_cnt[r] != length || name_len[r] == 0 || name_len[r] >= lim.name_max) return rule_declines();
+            names.emplace_back(name_bytes + (size_t)r * lim.name_max, name_len[r]);
+            start.push_back((uint64_t)r * length);
+            lengths.push_back(length);
+            if (!seen.insert(names.back()).second) return rule_declines();
+        }
+        return IoResult();
+    }
+};
 
 }  // namespace imc

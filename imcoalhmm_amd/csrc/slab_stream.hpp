@@ -1,8 +1,10 @@
 // slab_stream.hpp - the two pieces of host-side scaffolding the tiled device pipelines share, host-only (no HIP include):
 // the loop that pumps a file through two slab buffers and carries what lies behind the cut into the next slab, and the
 // split of n scan elements among the threads of a one-workgroup scan (tile_scan.hpp).  The product (imcoal_fwd.hip:
-// ingest_text, aln_parse_device) and the CPU checks (tests/ingest_tiles_check.cpp, tests/align_tiles_check.cpp) call the
-// same functions, so the checks' comparisons cover the product's loop.
+// slab_pass, the one driver of ingest_text, aln_parse_device and phy_parse_device) and the CPU checks
+// (tests/ingest_tiles_check.cpp, tests/align_tiles_check.cpp, tests/phylip_tiles_check.cpp) call the same functions, so
+// the checks' comparisons cover the product's loop; the rules inside its callbacks are the session records of
+// ingest_tiles.hpp, align_tiles.hpp and phylip_tiles.hpp, which both call as well.
 #pragma once
 
 #include <cstddef>

@@ -59,7 +59,7 @@ typedef std::vector<uint8_t> Bytes;
 struct Parsed {
     bool declined = false, slab_declined = false;    // slab_declined: a header line longer than the slab
     std::vector<std::string> names;
-    std::vector<uint64_t> start;
+    std::vector<uint64_t> start, length;
     Bytes bases;
 };
 
@@ -98,17 +98,18 @@ static std::vector<uint32_t> t_state, t_seq, t_hdr;
 static bool g_scatter_declined = false;                     // run the scatter of a slab that declines as well (the device does)
 
 // first_slab: bytes the first read delivers (0: the whole file in one slab); the second read delivers the rest.  The loop
-// is the product's (imc::slab_stream) over two buffers of the file's size, with the three launches as its "queue" and the
-// verdict and the names as its "judge".
+// is the product's (imc::slab_stream) over two buffers of the file's size, with the three launches as its "queue"; the cut,
+// the "judge" and what follows the last slab are the product's too (imc::AlnSession: cut, accept, finish).
 static void tiled_parse(const Bytes &data, size_t first_slab, size_t tile, Parsed &out)
 {
     out.declined = out.slab_declined = false;
     out.names.clear();
     out.start.clear();
+    out.length.clear();
     out.bases.assign(data.size(), 0xee);
-    uint32_t state = imc::kAlnStart0;
-    uint8_t prev = '\n';
-    uint64_t kept = 0;
+    imc::AlnSession ses;                                     // the product's rules, with the arguments the engine passes
+    const uint32_t &state = ses.state, &prev = ses.prev;
+    const uint64_t &kept = ses.kept, room = (data.size() + 15) & ~(uint64_t)15;
     static Bytes slabs[2];                                   // scratch, kept between calls
     static std::vector<imc::AlnRecord> table;
     const size_t slab = std::max<size_t>(data.size(), 1);
@@ -126,7 +127,7 @@ static void tiled_parse(const Bytes &data, size_t first_slab, size_t tile, Parse
             if (pos == data.size()) eof = true;
             return take;
         },
-        [&](const uint8_t *buf, size_t fill, bool last) { return imc::aln_slab_cut(buf, fill, last, state); },
+        [&](const uint8_t *buf, size_t fill, bool last) { return ses.cut(buf, fill, last); },
         [&](int cur, size_t cut) -> int {
             const uint8_t *buf = host[cur];
             const uint32_t n = (uint32_t)cut, tiles = (uint32_t)((cut + tile - 1) / tile);
@@ -185,22 +186,19 @@ static void tiled_parse(const Bytes &data, size_t first_slab, size_t tile, Parse
         },
         [&](int cur, size_t cut) -> int {
             between_slabs = false;
-            if (total.decline || out.names.size() + total.hdr > imc::kMaxAlnRecords) return imc::kSlabDeclined;
-            for (const imc::AlnRecord &r : table) {
-                const std::string name = imc::aln_header_name(host[cur], cut, r.slab_offset);
-                if (name.empty()) return imc::kSlabDeclined;
-                out.names.push_back(name);
-                out.start.push_back(r.start);
-            }
-            kept += total.seq;
-            state = total.exit;
-            prev = host[cur][cut - 1];
+            const imc::IoResult r = ses.accept(
+                total, [&](uint32_t, uint32_t count, const imc::AlnRecord *&recs) { CHECK(count == table.size()); recs = table.data(); return imc::IoResult(); }, host[cur],
+                cut, room);
+            CHECK(r.code == 0 || r.code == imc::kSlabDeclined);   // the device path has no error of its own to report
+            if (r.code) return r.code;
             base += cut;
             between_slabs = true;
             return 0;
         });
     if (end == imc::kSlabDeclined) { out.declined = true; out.slab_declined = between_slabs; return; }
-    if (std::set<std::string>(out.names.begin(), out.names.end()).size() != out.names.size()) { out.declined = true; return; }
+    if (ses.finish(out.length).code) { out.declined = true; return; }
+    out.names = ses.names;
+    out.start = ses.start;
     out.bases.resize(kept);
 }
 
@@ -216,9 +214,9 @@ static void compare(const Bytes &data, size_t first_slab, size_t tile, const imc
     }
     CHECK(host_rc.code == 0);                                 // every error is the host reader's: the tile scan declines
     CHECK(got.names == host.names);
+    CHECK(got.length.size() == host.names.size());
     for (size_t k = 0; k < host.names.size(); ++k) {
-        const uint64_t end = k + 1 < got.start.size() ? got.start[k + 1] : got.bases.size();
-        CHECK(end - got.start[k] == host.seqs[k].size());
+        CHECK(got.length[k] == host.seqs[k].size() && got.start[k] + got.length[k] <= got.bases.size());
         CHECK(std::memcmp(got.bases.data() + got.start[k], host.seqs[k].data(), host.seqs[k].size()) == 0);
     }
     CHECK(host.names.empty() ? got.bases.empty() : got.start[0] == 0);
@@ -270,6 +268,33 @@ static Bytes random_conforming(Rng &rng)
     }
     if (!d.empty() && rng.below(3) == 0) d.resize(d.size() - eol.size());        // no final line break
     return d;
+}
+
+// ---- the record cap by hand -----------------------------------------------------------------------------------
+// Exactly kMaxAlnRecords records are taken and one more is declined, in one slab and with the last header alone in a
+// second slab (the first slab then holds kMaxAlnRecords headers, and the cap is met by the names of an earlier slab).
+static void check_record_cap()
+{
+    for (uint32_t records : {imc::kMaxAlnRecords, imc::kMaxAlnRecords + 1}) {
+        Bytes d;
+        size_t last_header = 0;
+        for (uint32_t r = 0; r < records; ++r) {
+            const std::string rec = ">r" + std::to_string(r) + "\nAC\n";
+            last_header = d.size();
+            d.insert(d.end(), rec.begin(), rec.end());
+        }
+        static imc::FastaRecords host;
+        const imc::IoResult rc = imc::read_fasta_bytes(d.data(), d.size(), "f", host);
+        const bool takes = conforms(d);
+        CHECK(rc.code == 0 && host.names.size() == records && takes == (records <= imc::kMaxAlnRecords));
+        g_position.resize(d.size());
+        for (size_t i = 0; i < d.size(); ++i) g_position[i] = imc::aln_range(d.data() + i, i ? d[i - 1] : (uint8_t)'\n', 1);
+        for (size_t first : {(size_t)0, last_header, d.size() / 2}) {
+            const long declined = g_declined;
+            compare(d, first, 64, rc, host, takes);
+            CHECK((g_declined > declined) == !takes);
+        }
+    }
 }
 
 // ---- (c) column rules ----------------------------------------------------------------------------------------
@@ -420,6 +445,9 @@ int main()
     CHECK(imc::aln_slab_cut(two, 10, true, imc::kAlnStart0) == 10);
     check_column_rules();
     check_scan_shares();
-    std::printf("align_tiles ok: %ld parses compared, %ld declined, %ld conforming files\n", g_compared, g_declined, g_conforming);
+    const long compared = g_compared, declined = g_declined;     // (the totals name the seeded inputs alone)
+    check_record_cap();
+    std::printf("record cap: %ld parses compared, %ld declined\n", g_compared - compared, g_declined - declined);
+    std::printf("align_tiles ok: %ld parses compared, %ld declined, %ld conforming files\n", compared, declined, g_conforming);
     return 0;
 }

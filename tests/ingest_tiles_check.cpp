@@ -68,7 +68,7 @@ static std::vector<imc::IngestSummary> t_sums;
 static std::vector<uint32_t> t_off;
 
 // The product's loop (imc::slab_stream) over two buffers of the slab size, with the three launches as its "queue" and the
-// verdict as its "judge".
+// product's rules (imc::TextSession: cut, accept) as its cut and its "judge".
 static void tiled_parse(const std::vector<uint8_t> &data, size_t slab, size_t tile, uint32_t nsym, Parsed &out)
 {
     out.code = 0;
@@ -77,7 +77,8 @@ static void tiled_parse(const std::vector<uint8_t> &data, size_t slab, size_t ti
     for (auto &b : t_buf) b.assign(slab, 0);
     uint8_t *const host[2] = {t_buf[0].data(), t_buf[1].data()};
     size_t pos = 0;
-    uint64_t cols = 0;
+    imc::TextSession ses(data.size());                         // the product's rules, with the arguments the engine passes
+    const uint64_t &cols = ses.cols;
     imc::IngestSummary all = imc::ingest_identity();
     out.code = imc::slab_stream(
         host, slab,
@@ -88,7 +89,7 @@ static void tiled_parse(const std::vector<uint8_t> &data, size_t slab, size_t ti
             if (pos == data.size()) eof = true;
             return take;
         },
-        [](const uint8_t *buf, size_t fill, bool last) { return imc::slab_cut(buf, fill, last); },      // 0 before the end: a slab without whitespace
+        [&](const uint8_t *buf, size_t fill, bool last) { return ses.cut(buf, fill, last); },           // 0 before the end: a slab without whitespace
         [&](int cur, size_t cut) -> int {
             const uint32_t n = (uint32_t)cut;
             const uint8_t *b = host[cur];
@@ -124,12 +125,9 @@ static void tiled_parse(const std::vector<uint8_t> &data, size_t slab, size_t ti
             return 0;
         },
         [&](int, size_t cut) -> int {
-            const imc::IngestVerdict v = imc::ingest_verdict(all, (uint32_t)cut);
-            if (v.kind == imc::kIngestDeclined) return imc::kSlabDeclined;
-            if (v.kind == imc::kIngestBadByte) { out.msg = std::string("unexpected character in ") + kPath; return -5; }
-            if (v.kind == imc::kIngestSymbol) { out.msg = imc::symbol_error_text(v.value, cols + v.column, v.at_end); return -2; }
-            cols += all.count;
-            return 0;
+            const imc::IoResult r = ses.accept(all, cut, kPath);
+            out.msg = r.msg;
+            return r.code;
         });
 }
 
@@ -251,6 +249,18 @@ static void other_rules()
     CHECK(imc::slab_bytes_setting("4097", 1 << 20) == 4097);
     CHECK(imc::slab_bytes_setting("99999999999999", 1 << 20) == imc::kMaxSlabBytes);
     CHECK(imc::max_tokens_in(0) == 0 && imc::max_tokens_in(1) == 1 && imc::max_tokens_in(2) == 1 && imc::max_tokens_in(3) == 2);
+    // the room rule: "1 1 1" and "0 0 0 0" (both among the exhaustive strings, taken at every slab and tile size) hold exactly
+    // max_tokens_in(file bytes) tokens; no file holds more, so the error behind the bound is asked for directly
+    for (uint32_t tokens : {3u, 4u}) {
+        imc::TextSession ses(2 * tokens - 1);
+        imc::IngestSummary s = imc::ingest_identity();
+        s.count = tokens - 1;
+        CHECK(ses.room == tokens && ses.accept(s, 2 * tokens - 2, kPath).code == 0 && ses.cols == tokens - 1);
+        s.count = 1;
+        CHECK(ses.accept(s, 1, kPath).code == 0 && ses.cols == ses.room);                   // exactly the room: taken
+        const imc::IoResult over = ses.accept(s, 1, kPath);                                 // one more: the engine's error
+        CHECK(over.code == imc::kRuleHip && over.msg == "ingest: more tokens than the file can hold");
+    }
 }
 
 int main()

@@ -1,7 +1,8 @@
 // phylip_tiles_check.cpp - the parallel form of reading a PHYLIP alignment (csrc/phylip_tiles.hpp) against the host reader
 // imc::read_phylip (csrc/phylip_io.hpp), on the CPU.  The functions the PHYLIP kernels call are driven here sequentially,
-// the way the device path runs them: the file goes through the product's own loop (imc::slab_stream, cut anywhere), the
-// header comes from the first slab (phy_first_slab_header), and per slab the six launches - a summary per tile, folded
+// the way the device path runs them: the file goes through the product's own loop (imc::slab_stream, cut anywhere) under
+// the product's own rules (imc::PhySession: the header and the sizes from the first slab, the verdict on every slab's
+// total, the last n lines and the names behind the last slab), and per slab the six launches - a summary per tile, folded
 // from single positions with phy_combine (and equal to phy_range over the tile); one scan that gives every tile its cursor
 // from the cursor the slab is entered at; the line counts; the stride-n offsets in pieces of a few rows (phy_chain_partial,
 // phy_chain_walk); then every tile (in reverse order here: they are independent) walks its bytes from its own cursor
@@ -69,19 +70,20 @@ static bool same_summary(const imc::PhySummary &a, const imc::PhySummary &b)
 
 // ---- the device path, sequentially ------------------------------------------------------------------------------
 struct Device {
-    uint32_t tile, cap, name_max;
-    imc::PhylipHeader header;
-    uint32_t n = 0, length = 0;
+    uint32_t tile;
+    const imc::PhySession *ses;      // the product's session: what the launches get as arguments comes from it
+    imc::PhySizes sz;                // ... and from what its begin() sized
     Bytes bases, names;
     std::vector<uint32_t> cnt, off, nlen;
-    imc::PhyCursor at{imc::kPhyCol0, 0u, 0u, 0u};
     uint32_t flags = 0;
-    uint8_t prev = '\n';
-    bool have_header = false;
+    imc::PhyTotal total;             // what the slab reports
 
-    // one slab; false: it declines
-    bool slab(const uint8_t *buf, uint32_t len)
+    // one slab
+    void slab(const uint8_t *buf, uint32_t len)
     {
+        const imc::PhyCursor at = ses->at;
+        const uint8_t prev = (uint8_t)ses->prev;
+        const uint32_t n = ses->nrec, length = ses->length, cap = ses->cap, name_max = ses->lim.name_max;
         const uint32_t tiles = (len + tile - 1) / tile;
         auto byte_before = [&](uint32_t i) { return i ? buf[i - 1] : prev; };
         // summary
@@ -118,8 +120,9 @@ struct Device {
         const uint32_t j0 = at.lines, j1 = std::min(end.lines, cap), m = j1 > j0 ? j1 - j0 : 0u;
         const uint32_t m_max = len / 2 + 2;
         CHECK(m <= m_max);
-        const uint32_t rows = imc::phy_chain_rows(m_max, n), pieces = imc::phy_chain_pieces(m_max, n, rows);
-        std::vector<uint32_t> part((size_t)pieces * n);
+        const uint32_t rows = sz.rows, pieces = sz.pieces;
+        CHECK((uint64_t)rows * pieces * n >= m_max);
+        std::vector<uint32_t> part(sz.part / sizeof(uint32_t));
         for (uint32_t q = 0; q < pieces; ++q)
             for (uint32_t c = 0; c < n; ++c) part[(size_t)q * n + c] = imc::phy_chain_partial(cnt.data(), j0, m, n, rows, q, c);
         for (uint32_t q = pieces; q-- > 0;)
@@ -161,20 +164,17 @@ struct Device {
                 for (uint32_t b = 0; b < seg_cnt[s]; ++b) bases.at((size_t)(dest0 + b)) = stage[seg_start[s] + b];
             }
         }
-        if (decline || flags || end.lines > cap || end.P > (uint64_t)length + name_max) return false;
-        at = end;
-        prev = buf[len - 1];
-        return true;
+        total = imc::PhyTotal{end, decline ? 1u : 0u, flags, {0u, 0u}};
     }
 };
 
 static Parsed device_parse(const Bytes &d, size_t slab_bytes, uint32_t tile, uint32_t cap_lines = 1u << 20, uint32_t name_max = imc::kPhyNameMax)
 {
     Parsed out;
+    imc::PhySession ses(d.size(), imc::PhyLimits{cap_lines, name_max});    // the product's rules, with the arguments the engine passes
     Device dev;
     dev.tile = tile;
-    dev.name_max = name_max;
-    dev.cap = (uint32_t)std::min<uint64_t>(cap_lines, d.size() / 2 + 2);
+    dev.ses = &ses;
     Bytes h0(slab_bytes), h1(slab_bytes);
     uint8_t *const host[2] = {h0.data(), h1.data()};
     size_t pos = 0;
@@ -192,32 +192,28 @@ static Parsed device_parse(const Bytes &d, size_t slab_bytes, uint32_t tile, uin
         [&](const uint8_t *, size_t fill, bool last) { at_eof = last; return fill; },
         [&](int cur, size_t cut) -> int {
             if (!slabs) {
-                if (!imc::phy_first_slab_header(host[cur], cut, at_eof, d.size(), dev.header)) return imc::kSlabDeclined;
-                dev.n = (uint32_t)dev.header.n;
-                dev.length = (uint32_t)dev.header.length;
-                dev.bases.assign((size_t)dev.n * dev.length, 0);          // exactly n * length: any write outside is caught
-                dev.names.assign((size_t)dev.n * name_max, 0);
-                dev.nlen.assign(dev.n, 0);
-                dev.cnt.assign(dev.cap, 0);
-                dev.off.assign(dev.cap, 0xdeadbeefu);
+                if (ses.begin(host[cur], cut, at_eof, slab_bytes, dev.sz).code) return imc::kSlabDeclined;
+                CHECK(dev.sz.bases >= (size_t)ses.nrec * ses.length && dev.sz.bases % 16 == 0);
+                dev.bases.assign((size_t)ses.nrec * ses.length, 0);       // exactly n * length: any write outside is caught
+                dev.names.assign(dev.sz.names, 0);
+                dev.nlen.assign(dev.sz.nlen / sizeof(uint32_t), 0);
+                dev.cnt.assign(ses.cap, 0);
+                dev.off.assign(ses.cap, 0xdeadbeefu);
             }
             ++slabs;
-            return dev.slab(host[cur], (uint32_t)cut) ? imc::kSlabDone : imc::kSlabDeclined;
+            dev.slab(host[cur], (uint32_t)cut);
+            return imc::kSlabDone;
         },
-        [&](int, size_t) -> int { return imc::kSlabDone; });
-    if (end == imc::kSlabDeclined || !slabs || dev.at.lines < (uint64_t)dev.n + 1) { out.declined = true; return out; }
-    std::set<std::string> seen;
-    for (uint32_t r = 0; r < dev.n; ++r) {
-        const uint32_t j = dev.at.lines - dev.n + r, rec = (j - 1) % dev.n;
-        if ((uint64_t)dev.off[j] + dev.cnt[j] != dev.length) { out.declined = true; return out; }
-        (void)rec;
+        [&](int cur, size_t cut) -> int { return ses.accept(dev.total, host[cur][cut - 1]).code; });
+    uint32_t line = 0;
+    if (end == imc::kSlabDeclined || ses.tail(line).code) { out.declined = true; return out; }
+    CHECK(end == imc::kSlabDone && slabs > 0);
+    std::vector<uint64_t> start, length;
+    if (ses.finish(dev.nlen.data(), reinterpret_cast<const char *>(dev.names.data()), dev.cnt.data() + line, dev.off.data() + line, out.names, start, length).code) {
+        out.declined = true;
+        return out;
     }
-    for (uint32_t r = 0; r < dev.n; ++r) {
-        if (dev.nlen[r] == 0 || dev.nlen[r] >= name_max) { out.declined = true; return out; }
-        out.names.emplace_back(reinterpret_cast<const char *>(dev.names.data()) + (size_t)r * name_max, dev.nlen[r]);
-        out.seqs.emplace_back(reinterpret_cast<const char *>(dev.bases.data()) + (size_t)r * dev.length, dev.length);
-        if (!seen.insert(out.names.back()).second) { out.declined = true; return out; }
-    }
+    for (uint32_t r = 0; r < ses.nrec; ++r) out.seqs.emplace_back(reinterpret_cast<const char *>(dev.bases.data()) + start[r], length[r]);
     return out;
 }
 
@@ -428,7 +424,7 @@ static void hand_written()
         const Bytes far = bytes_of("      2 1\na A\nb C\n");
         CHECK(!compare(far, 8, 3) && compare(far, 10, 3));
     }
-    // a name of name_max bytes or more; the line cap
+    // a name of name_max - 1 bytes is taken, one of name_max bytes or more is not; the line cap
     {
         const Bytes d = bytes_of("2 2\nabcdefg AC\nhi GT\n");
         CHECK(compare(d, 5, 3, 1u << 20, 8) && !compare(d, 5, 3, 1u << 20, 7) && !compare(d, d.size(), 3, 1u << 20, 4));
@@ -437,12 +433,27 @@ static void hand_written()
     }
 }
 
+// The edges of the rules behind the last slab, beside those hand_written() stands on already: "3 0" with its three name
+// lines (exactly n name lines and no base: taken), "b ACG" (a last record one base short on its name line), "abcdefg" at
+// name_max 8 and 7 (a name of name_max - 1 bytes is taken, one of name_max bytes is not).
+static void session_edges()
+{
+    all_geometries("3 0\na\nb\n", false);                                 // one name line fewer than n, no base
+    all_geometries("2 4\na AC\nb AC\nGT\nG\n", false);                     // a last record one base short in the last block
+    all_geometries("2 4\na AC\nb AC\nGT\nGT\n", true, 4);                  // ... and whole
+    const Bytes d = bytes_of("2 2\nabcdefg AC\nhi GT\n");                   // the name limit with the whole file in one slab and one tile
+    CHECK(compare(d, d.size(), 64, 1u << 20, 8) && !compare(d, d.size(), 64, 1u << 20, 7));
+}
+
 int main()
 {
     all_short_strings();
     generated_files();
     hand_written();
     CHECK(g_taken > 1000 && g_declined > 1000);
-    std::printf("compared %ld (taken %ld, declined %ld)\nphylip_tiles ok\n", g_compared, g_taken, g_declined);
+    const long compared = g_compared, taken = g_taken, declined = g_declined;      // (the totals name the seeded inputs alone)
+    session_edges();
+    std::printf("session edges: compared %ld (taken %ld, declined %ld)\n", g_compared - compared, g_taken - taken, g_declined - declined);
+    std::printf("compared %ld (taken %ld, declined %ld)\nphylip_tiles ok\n", compared, taken, declined);
     return 0;
 }
