@@ -21,8 +21,13 @@
 // and the owner of a chunk under construction, the level loop install_levels with its host and device sources, the device
 // trainer, dictionary_for, obs_upload / obs_from_device, device ingestion of files and sequence pairs, resident alignments; the
 // training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's, the parses ingest_tiles.hpp's and align_tiles.hpp's);
-// the kernel table, the launch plan (Group / Level / Plan own their device buffers), the plan list with recompress_alphabet
-// behind it, the plan builder, one enqueue function per kernel family, the model layer, the sampler, the C ABI.
+// the kernel table, the launch plan (Group / Level / Plan own their device buffers; a Group holds its imc::GroupDecision and its
+// part of the geometry), the plan list with recompress_alphabet behind it, the plan builder, one enqueue function per kernel
+// family, the model layer, the sampler, the C ABI.  A plan is made by host-only functions - imc::decide_groups
+// (planner_host.hpp), then imc::plan_geometry and imc::group_schedules (plan_host.hpp: segments, stitch units, vectors, block
+// lists, fused-tail records, the stitch hierarchy; workgroup lists, table schedules, hot set, phase table) - and build_plan adds
+// the one step that needs the chunk handles, a segment's device pointer; PlanBuilder::upload() then only evicts, allocates,
+// copies and registers the plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1723,7 +1728,7 @@ KernelChoice make_kc()
             k.zip4_max_hot = &Zip4Geom<NP / 4>::max_hot;
         }
     }
-    if constexpr (NP == 28 || NP == 32) {   // streamed scan only, four wavefronts per workgroup (PlanBuilder::wide)
+    if constexpr (NP == 28 || NP == 32) {   // streamed scan only, four wavefronts per workgroup (build_plan: wide)
         k.tok_doubles = Zip3Geom<NP / 4>::TOK;
         k.zip4s = k_zpropagate4<NP / 4, false, false>;
         k.zip4sw = k_zpropagate4<NP / 4, true, false>;
@@ -1785,74 +1790,44 @@ KernelChoice *choose_kernel(int N, bool prefer_gemm)
 // ---- launch plan ----------------------------------------------------------------------------------
 
 struct Group {             // one propagate launch
-    // Which kernel family runs the group: decided by imc::decide_groups (planner_host.hpp); everything after that reads
-    // `kind` or one of the predicates below.
+    // What imc::decide_groups decided (planner_host.hpp): the kernel family (`kind`, which everything reads directly or
+    // through the predicates below), the stream (raw columns or a token level of the dictionary) and its alphabet, the
+    // chunks, the segment length, the rank-one hand-off's checkpoints, the planner's estimates.
     using Kind = imc::GroupKind;
-    Kind kind = Kind::ColumnVector;
-    bool is_chain() const { return kind == Kind::GemmChain || kind == Kind::MatVecChain; }
-    bool is_blocked() const { return kind == Kind::BlockedLds || kind == Kind::BlockedGlobal; }
-    bool global_table() const { return kind == Kind::BlockedGlobal; }
-
-    // ---- what every family uses ----
-    bool tokens = false;   // the group's stream is a token level of its dictionary, not the raw columns (a raw stream can
-                           // run the blocked scan and the chains too)
-    int level = -1, A = 0;
+    imc::GroupDecision dec;
+    imc::GroupGeometry geo;    // its vectors, chain segments, blocks and fused-tail records (imc::plan_geometry)
+    imc::GroupSchedules sch;   // its workgroup lists, table-build schedules, hot set and phase table (imc::group_schedules)
+    bool is_chain() const { return imc::is_chain(dec.kind); }
+    bool is_blocked() const { return imc::is_blocked(dec.kind); }
+    bool global_table() const { return dec.kind == Kind::BlockedGlobal; }
     std::shared_ptr<DictDev> dict;
-    std::vector<int> chunks;
-    uint32_t vec_begin = 0, n_vecs = 0;
-    size_t seglen = 0;
-    double model_us = 0.0, model_tab_us = 0.0;   // the planner's estimate for this group's launches and the table's part of it (dictionary groups; compared by build_plan)
-    uint64_t vsteps = 0;   // executed vector-steps per parameter set (columns or tokens)
-    uint64_t stream_len = 0;
+
     // operator table in global memory and its exponents: the chain families and the global-table scan
     DevBuf<double> d_Ctab;
     DevBuf<int> d_cex;
 
     struct Chain {         // ---- GemmChain / MatVecChain ----
-        std::vector<uint32_t> seg_ids, seg_out;   // segment ids and their level-0 vector index
-        std::vector<BigBlock> big_blocks;         // one entry per (segment, column slab) workgroup
         DevBuf<BigBlock> d_big_blocks;
-        std::vector<std::pair<int, int>> table_runs;   // (first, count) in the dictionary's depth order per k_big_table_level launch
         DevBuf<double> d_Cpack;                   // groups that run the mat-vec chain: packed copy of the table ([B][A][N][TS])
         // rank-one hand-off (GEMM chain only): operator segments run on the GEMM chain in rounds that end at the
         // checkpoints (token counts); after each round k_rank1_check tests the segments still on the chain, and those
         // that collapsed to u alpha^T finish on the mat-vec chain from that checkpoint.  The schedule is fixed per plan,
         // the decision per segment comes from the data of the evaluation: nothing is carried from call to call.
-        bool rank1 = false;
-        std::vector<int> checkpoints;
-        std::vector<BigBlock> tail_blocks;        // one entry per segment (operator tails and first segments)
-        std::vector<std::pair<uint32_t, uint32_t>> r1_segs;   // (plan-wide id, length) of the operator segments
         DevBuf<BigBlock> d_tail_blocks;
         DevBuf<int> d_r1flag, d_r1at;
         DevBuf<double> d_r1u, d_r1alpha;
     } chain;
 
     struct Blocked {       // ---- BlockedLds / BlockedGlobal ----
-        std::vector<Z2Block> blocks;              // one entry per workgroup
         DevBuf<Z2Block> d_blocks;
         DevBuf<uint16_t> d_tab_order;             // merged tokens of the alphabet by dictionary depth
         DevBuf<int> d_tab_lvl;
-        std::vector<int> tab_lvl;                 // host copy of the depth offsets
-        int tab_nlvl = 0;
-        // global table: its build's descriptor lists with their launch lists (first entry, entries)
-        DevBuf<int4> d_tab_desc;                  // {token, left, right, 0} per entry of the depth order
-        DevBuf<int4> d_tab_desc2;                 // two int4 per entry of the two-depths-per-launch schedule (k_z4_level2)
-        std::vector<std::pair<int, int>> tab2;
-        DevBuf<int4> d_tab_desc3;                 // three int4 per token of the three-depths-per-launch schedule (k_z4_level3): {token, leaves 0-2}, {leaves 3-6}, {leaf 7}
-        std::vector<std::pair<int, int>> tab3;
-        bool wide_tokens = false;                 // the token stream holds 16-bit ids (set when the group is created, for every
-                                                  // group; only the global-table scan reads it)
-        bool stream_table = false;                // nothing cached in LDS: the launch's tables are small enough to stay cache resident
-        int n_hot = 0;                            // hybrid table: operators cached in LDS
-        std::vector<uint16_t> hot;
+        DevBuf<int4> d_tab_desc, d_tab_desc2, d_tab_desc3;   // global table: the descriptor lists of its build (GroupSchedules)
         DevBuf<uint16_t> d_hot;
-        imc::PhaseTable phases;                   // the XCD-affine grid of the scan (used when B > 1)
-        // fused tail (zip3_tail): per workgroup {chunk, unit, units of the chunk}; published operators, exponents, arrival counters
-        std::vector<Z2Tail> tails;
+        // fused tail (zip3_tail): the records; published operators, exponents, arrival counters
         DevBuf<Z2Tail> d_tails;
         DevBuf<double> d_tailX;
         DevBuf<int> d_tailE, d_tail_arrive;
-        int tail_stride = 0;
     } blk;
 };
 
@@ -1883,7 +1858,7 @@ struct PlanKey {
 struct Plan {
     const PlanKey key;               // (key.opt: what the builder and every launch of this plan read their options from)
     KernelChoice *kc = nullptr;
-    bool wide = false;               // 25-32 states on the blocked scan (PlanBuilder::wide)
+    bool wide = false;               // 25-32 states on the blocked scan (build_plan: wide)
     const int &N = key.N, &S = key.S, &B = key.B;   // the key holds the call's shape: one copy (a Plan is neither copied nor moved)
     const int n_chunks = (int)key.chunk_ids.size();
     uint32_t n_segs = 0, n_vecs = 0;
@@ -2093,193 +2068,13 @@ struct DevUpload {
     }
 };
 
-// Builds the launch descriptors of one plan from the planner's decision (build_plan fills p->groups and chunk_group from
-// imc::decide_groups), in phases; every phase reads what the earlier ones left in the members.
+// What is left of building a plan once the host-only functions have run (build_plan: imc::decide_groups,
+// imc::plan_geometry, imc::group_schedules): the plan with its groups filled, the geometry, and the segment cuts resolved
+// against the chunks' device streams.  upload() computes nothing: it evicts, allocates, copies and registers the plan.
 struct PlanBuilder {
-    const imc_obs *const *chunks = nullptr;
-    int n_chunks = 0, N = 0, S = 0, B = 0;
-    bool op_mode = false;               // imc_forward_state(as_operator): no segment is a chunk's "first"
-    KernelChoice *kc = nullptr;
-    // 25-32 states: kc is the vector kernels' entry and every dictionary's chunks run its streamed blocked scan
-    // (k_zpropagate4<7 | 8>); chunks without tokens stay on the vector kernels.
-    bool wide = false;
-    bool mfma() const { return kc->use3(opt().blocked_variant) || wide; }      // the blocked kernels of this plan are the fp64-MFMA ones
     std::unique_ptr<Plan> p;
-    const imc::PlanOptions &opt() const { return p->key.opt; }   // the options the decision was taken under: the plan's
-    std::vector<int> chunk_group;       // chunk -> index into p->groups
+    imc::PlanGeometry geo;
     std::vector<SegDesc> segs;          // all segments, chunk order
-    std::vector<uint8_t> seg_first;
-    std::vector<uint32_t> chunk_seg;    // chunk -> first segment (n_chunks + 1 entries)
-    std::vector<VecDesc> vecs;          // level-0 vectors
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> chunk_units;
-    std::vector<uint32_t> chunk_unit, unit_vec0;
-    std::vector<uint8_t> unit_first;
-    struct HostLevel { std::vector<uint32_t> chunk_seg, vec0; std::vector<uint8_t> first; std::vector<ChainDesc> chains; uint32_t n_vecs; };
-    std::vector<HostLevel> hl;          // stitch hierarchy, level 0 = propagate output
-    std::vector<int32_t> final_vec;     // chunk -> its single remaining unit at the last level (-1: empty chunk)
-
-    void cut_segments()
-    {
-        // ---- segments in chunk order ----
-        chunk_seg.assign(n_chunks + 1, 0);
-        for (int f = 0; f < n_chunks; ++f) {
-            chunk_seg[f] = (uint32_t)segs.size();
-            const Group &gr = p->groups[chunk_group[f]];
-            const size_t L = gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L;
-            const uint8_t *base = gr.tokens ? chunks[f]->d_tok[gr.level] : chunks[f]->d_sym;
-            if (!L) continue;
-            const size_t K0 = (L + gr.seglen - 1) / gr.seglen;
-            const size_t sl = round_up((L + K0 - 1) / K0, gr.is_blocked() ? Z2GRAN : 16);   // equalised; a multiple of 16 (16-byte aligned
-                                                                                   // loads) except for the blocked kernels
-            for (size_t off = 0, k = 0; off < L; off += sl, ++k) {
-                const bool wide = gr.tokens ? chunks[f]->wide[gr.level] : chunks[f]->wide_raw;
-                const bool fst = k == 0 && !op_mode;   // operator mode: the chunk's own first segment is an operator too
-                segs.push_back(SegDesc{base + off * (wide ? 2 : 1), (uint32_t)std::min(sl, L - off),
-                                       (fst ? SEG_FIRST : 0u) | (wide ? SEG_WIDE : 0u)});
-                seg_first.push_back(fst);
-            }
-        }
-        chunk_seg[n_chunks] = (uint32_t)segs.size();
-    }
-
-    int make_units()
-    {
-        // ---- stitch units and their vectors, contiguous per group ----
-        // A unit is what the stitch hierarchy sees at level 0: a segment, or (blocked kernel) a workgroup's
-        // run of up to 32 consecutive segments of one chunk, already folded inside the kernel.
-        chunk_units.assign(n_chunks, {});   // per chunk: (seg0, nsegs)
-        for (int f = 0; f < n_chunks; ++f) {
-            const Group &gr = p->groups[chunk_group[f]];
-            const uint32_t step = gr.is_blocked() ? (uint32_t)kc->z4_slots() : 1u;
-            for (uint32_t sid = chunk_seg[f]; sid < chunk_seg[f + 1]; sid += step)
-                chunk_units[f].push_back({sid, std::min(step, chunk_seg[f + 1] - sid)});
-        }
-        chunk_unit.assign(n_chunks + 1, 0);
-        for (int f = 0; f < n_chunks; ++f) chunk_unit[f + 1] = chunk_unit[f] + (uint32_t)chunk_units[f].size();
-        unit_vec0.assign(chunk_unit[n_chunks], 0);
-        unit_first.assign(chunk_unit[n_chunks], 0);
-        for (Group &gr : p->groups) {
-            gr.vec_begin = (uint32_t)vecs.size();
-            for (int f : gr.chunks) {
-                gr.stream_len += gr.tokens ? chunks[f]->ntok[gr.level] : chunks[f]->L;
-                for (size_t u = 0; u < chunk_units[f].size(); ++u) {
-                    const uint32_t sid = chunk_units[f][u].first, ns = chunk_units[f][u].second;
-                    const uint32_t uid = chunk_unit[f] + (uint32_t)u;
-                    const bool fst = seg_first[sid] != 0;
-                    unit_first[uid] = fst;
-                    unit_vec0[uid] = (uint32_t)vecs.size();
-                    const int nv = fst ? 1 : N;
-                    for (int c = 0; c < nv; ++c) vecs.push_back(VecDesc{sid, (uint32_t)c});
-                    if (gr.is_chain()) { gr.chain.seg_ids.push_back(sid); gr.chain.seg_out.push_back(unit_vec0[uid]); }
-                    if (gr.is_blocked()) {
-                        std::vector<Z2Block> &blocks = gr.blk.blocks;
-                        // A chunk that is ONE segment needs no fold: up to 32 consecutive such chunks share a workgroup, each
-                        // in a slot of its own (Z2Block::first == 2).  One workgroup per chunk left 31 of 32 rows idle when
-                        // the chunks are short (10000 chunks of 1e4 columns, 20 states: 39 rounds of workgroups, 1.97 ms).
-                        const bool whole = mfma() && fst && ns == 1 && chunk_units[f].size() == 1;
-                        if (whole && !blocks.empty() && blocks.back().first == 2 && blocks.back().n < (uint32_t)kc->z4_slots() &&
-                            blocks.back().seg0 + blocks.back().n == sid && blocks.back().out_vec0 + blocks.back().n == unit_vec0[uid])
-                            ++blocks.back().n;
-                        else
-                            blocks.push_back(Z2Block{sid, ns, unit_vec0[uid], whole ? 2u : fst ? 1u : 0u});
-                    }
-                    for (uint32_t q2 = 0; q2 < ns; ++q2)
-                        gr.vsteps += (uint64_t)((seg_first[sid + q2] && !gr.is_blocked()) ? 1 : N) * segs[sid + q2].len;
-                }
-            }
-            gr.n_vecs = (uint32_t)vecs.size() - gr.vec_begin;
-        }
-        // fused tail: one blocked-MFMA group holds every chunk, no chunk is empty or longer than a workgroup has slots
-        if (p->groups.size() == 1 && p->groups[0].is_blocked() && mfma() && !op_mode && n_chunks > 0) {
-            Group::Blocked &bl = p->groups[0].blk;
-            bool ok = true;
-            size_t most = 0;
-            for (int f = 0; f < n_chunks; ++f) {
-                ok = ok && !chunk_units[f].empty() && chunk_units[f].size() <= (size_t)kc->z4_slots();
-                most = std::max(most, chunk_units[f].size());
-            }
-            if (ok) {
-                for (int f : p->groups[0].chunks)
-                    for (size_t u = 0; u < chunk_units[f].size(); ++u)
-                        bl.tails.push_back(Z2Tail{(uint32_t)f, (uint32_t)u, (uint32_t)chunk_units[f].size(), 0u});
-                bl.tail_stride = (int)most;
-                if (bl.tails.size() != bl.blocks.size()) bl.tails.clear();      // packed blocks: several chunks share a workgroup
-                else
-                    for (Z2Block &bk : bl.blocks)                               // (a packed block of ONE chunk is an ordinary first block,
-                        if (bk.first == 2) bk.first = 1;                        //  and the fused tail writes that chunk's result)
-            }
-        }
-        if (vecs.size() >= (size_t)UINT32_MAX / 2) return fail(IMC_ERR_ARG, "too many vectors in one call");
-        p->n_segs = (uint32_t)segs.size();
-        p->n_vecs = (uint32_t)vecs.size();
-        p->pstride = round_up((size_t)kc->NP + (size_t)kc->NP * kc->NP + (size_t)S * kc->NP, 2);
-
-        return IMC_OK;
-    }
-
-    void make_hierarchy()
-    {
-        // ---- stitch hierarchy: fold runs of g ~ sqrt(K) consecutive segments until one vector per chunk ----
-        hl.assign(1, HostLevel());
-        hl[0].chunk_seg = chunk_unit; hl[0].vec0 = unit_vec0; hl[0].first = unit_first; hl[0].n_vecs = p->n_vecs;
-        for (;;) {
-            const HostLevel &cur = hl.back();
-            uint32_t kmax = 0;
-            for (int f = 0; f < n_chunks; ++f) kmax = std::max(kmax, cur.chunk_seg[f + 1] - cur.chunk_seg[f]);
-            // a level whose chunks all hold one first-vector is final; level 0 operators always need one pass
-            if (kmax <= 1 && hl.size() > 1) break;
-            if (kmax == 0) break;
-            // ~3 levels: per level a chain costs g serial steps (0.38 us each at 20 states, profiles/mb_chain_step.txt) plus
-            // one launch (~3 us up to its second step)
-            const uint32_t gsz = kmax <= 16 ? kmax : std::max<uint32_t>(12, (uint32_t)std::ceil(std::cbrt((double)kmax)));
-            p->chain_steps += gsz;
-            HostLevel nx;
-            nx.chunk_seg.assign(n_chunks + 1, 0);
-            nx.n_vecs = 0;
-            for (int f = 0; f < n_chunks; ++f) {
-                nx.chunk_seg[f] = (uint32_t)nx.vec0.size();
-                const uint32_t s0 = cur.chunk_seg[f], s1 = cur.chunk_seg[f + 1];
-                for (uint32_t rb = s0; rb < s1; rb += gsz) {
-                    const uint32_t re = std::min(rb + gsz, s1);
-                    const bool fst = rb == s0 && !op_mode;
-                    nx.vec0.push_back(nx.n_vecs);
-                    nx.first.push_back(fst);
-                    const int nvv = fst ? 1 : N;
-                    // the start vector and the first operator's vectors: known here, so no chain looks them up on the device
-                    const uint32_t op0 = rb + (fst ? 1u : 0u);
-                    const uint32_t vec_first = fst ? cur.vec0[rb] : 0u, vbase = op0 < re ? cur.vec0[op0] : 0u;
-                    for (int c = 0; c < nvv; ++c)
-                        nx.chains.push_back(ChainDesc{rb, re, (uint32_t)c, nx.n_vecs + c, fst ? 1u : 0u, 0u, vec_first, vbase});
-                    nx.n_vecs += nvv;
-                }
-            }
-            nx.chunk_seg[n_chunks] = (uint32_t)nx.vec0.size();
-            const bool done = kmax <= gsz;
-            hl.push_back(std::move(nx));
-            if (done) break;
-        }
-        final_vec.assign(std::max(n_chunks, 1), -1);
-        bool all_from_chains = hl.size() > 1 && !op_mode && n_chunks > 0;
-        for (int f = 0; f < n_chunks; ++f) {
-            const HostLevel &last = hl.back();
-            if (last.chunk_seg[f + 1] > last.chunk_seg[f]) final_vec[f] = (int32_t)last.vec0[last.chunk_seg[f]];
-            else all_from_chains = false;               // an empty chunk: k_finish writes its 0.0
-        }
-        // every chunk's final vector comes out of a chain of the last level: those chains write the log-likelihoods
-        // themselves and k_finish is not launched
-        p->finish_fused = false;
-        if (all_from_chains) {
-            HostLevel &last = hl.back();
-            std::vector<char> seen((size_t)n_chunks, 0);
-            for (ChainDesc &cd : last.chains)
-                for (int f = 0; f < n_chunks; ++f)
-                    if (cd.first && final_vec[f] == (int32_t)cd.out_vec) { cd.chunk1 = (uint32_t)f + 1; seen[f] = 1; }
-            p->finish_fused = std::all_of(seen.begin(), seen.end(), [](char c) { return c != 0; });
-            if (!p->finish_fused)
-                for (ChainDesc &cd : last.chains) cd.chunk1 = 0;
-        }
-
-    }
 
     int upload(Plan **out)
     {
@@ -2292,10 +2087,13 @@ struct PlanBuilder {
         }
 
         Plan *q = p.get();
+        const KernelChoice *kc = q->kc;
+        const int N = q->N, B = q->B, n_chunks = q->n_chunks;
+        const std::vector<imc::HostLevel> &hl = geo.levels;
         DevUpload u;
         u.put(q->d_segs, segs);
-        u.put(q->d_vecs, vecs);
-        u.put(q->d_final_vec, final_vec);
+        u.put(q->d_vecs, geo.vecs);
+        u.put(q->d_final_vec, geo.final_vec);
         q->levels.resize(hl.size());
         for (size_t l = 0; l < hl.size(); ++l) {
             Level &lv = q->levels[l];
@@ -2313,63 +2111,40 @@ struct PlanBuilder {
         for (Group &gr : q->groups) {
             Group::Blocked &bl = gr.blk;
             Group::Chain &ch = gr.chain;
-            if (gr.is_blocked()) u.put(bl.d_blocks, bl.blocks);
-            if (!bl.tails.empty()) {
-                const size_t slots = (size_t)B * n_chunks * bl.tail_stride;
-                u.put(bl.d_tails, bl.tails);
+            const imc::GroupSchedules &sch = gr.sch;
+            const int A = gr.dec.A;
+            if (gr.is_blocked()) u.put(bl.d_blocks, gr.geo.blocks);
+            if (!gr.geo.tails.empty()) {
+                const size_t slots = (size_t)B * n_chunks * gr.geo.tail_stride;
+                u.put(bl.d_tails, gr.geo.tails);
                 u.alloc(bl.d_tailX, slots * kc->tok_doubles * 8);
                 u.alloc(bl.d_tailE, slots * 128);
                 u.zeroed(bl.d_tail_arrive, (size_t)B * n_chunks * 4);
             }
             if (gr.global_table()) {
-                // hot set: the most frequent tokens of this group's chunks, as many as LDS holds beside the identity
-                std::vector<uint64_t> cnt((size_t)gr.A, 0);
-                for (int f : gr.chunks)
-                    for (size_t z = 0; z < chunks[f]->tok_count[gr.level].size() && z < cnt.size(); ++z) cnt[z] += chunks[f]->tok_count[gr.level][z];
-                const std::vector<uint16_t> ids = imc::hot_order(cnt);
-                const double tables = (double)B * (gr.A + 1) * kc->tok_doubles * 8.0;
-                bl.stream_table = wide || imc::z4_streamed(opt(), tables, B);
-                bl.n_hot = bl.stream_table ? 0 : std::min(gr.A, kc->zip4_max_hot(gr.A, LDS_BUDGET));
-                bl.hot.assign(ids.begin(), ids.begin() + bl.n_hot);
-                bl.phases = imc::xcd_phases(B, (int)bl.blocks.size());
-                u.put(bl.d_hot, bl.hot);
-                u.alloc(gr.d_Ctab, (size_t)B * (gr.A + 1) * kc->tok_doubles * 8);
-                u.alloc(gr.d_cex, (size_t)B * (gr.A + 1) * 4 + 16);
+                u.put(bl.d_hot, sch.hot);
+                u.alloc(gr.d_Ctab, (size_t)B * (A + 1) * kc->tok_doubles * 8);
+                u.alloc(gr.d_cex, (size_t)B * (A + 1) * 4 + 16);
             }
-            if (gr.is_blocked() && gr.tokens) {
-                // merged tokens of this level's alphabet (ids S .. A-1) grouped by dictionary depth, for the table build
-                const DictDev &dd = *gr.dict;
-                const imc::DepthOrder o = imc::depth_order_below(dd.order, dd.depth, gr.A);
-                bl.tab_nlvl = o.nlvl;
-                bl.tab_lvl = o.lvl;
-                u.put(bl.d_tab_order, o.order);
-                u.put(bl.d_tab_lvl, o.lvl);
+            if (gr.is_blocked() && gr.dec.tokens) {
+                u.put(bl.d_tab_order, sch.tab.order);
+                u.put(bl.d_tab_lvl, sch.tab.lvl);
                 if (gr.global_table()) {
-                    const std::vector<imc::Desc4> desc = imc::level_descriptors(dd.dict, o);
-                    const imc::TableSchedule s2 = imc::pairs_schedule(dd.dict, dd.depth, o, S);
-                    const imc::TableSchedule s3 = imc::triples_schedule(dd.dict, dd.depth, o, S, gr.A);
-                    bl.tab2 = s2.launches;
-                    bl.tab3 = s3.launches;
-                    u.put(bl.d_tab_desc, desc);
-                    if (!s2.desc.empty()) u.put(bl.d_tab_desc2, s2.desc);
-                    if (!s3.desc.empty()) u.put(bl.d_tab_desc3, s3.desc);
+                    u.put(bl.d_tab_desc, sch.tab_desc);
+                    if (!sch.tab2.desc.empty()) u.put(bl.d_tab_desc2, sch.tab2.desc);
+                    if (!sch.tab3.desc.empty()) u.put(bl.d_tab_desc3, sch.tab3.desc);
                 }
             }
             if (!gr.is_chain()) continue;
             const size_t np2 = (size_t)kc->NP * kc->NP;
-            if (gr.tokens) ch.table_runs = imc::depth_runs_below(gr.dict->order, gr.dict->depth, gr.A);
-            ch.big_blocks = imc::deal_slabs<BigBlock>(ch.seg_ids, ch.seg_out, seg_first, kc->big_nslab);
-            u.put(ch.d_big_blocks, ch.big_blocks);
-            u.alloc(gr.d_Ctab, (size_t)B * gr.A * np2 * 8);
-            if ((gr.kind == Group::Kind::MatVecChain || ch.rank1) && N < kc->NP && opt().pack_table)   // the mat-vec chain reads a packed copy
-                u.alloc(ch.d_Cpack, (size_t)B * gr.A * N * (size_t)(N + (N & 1)) * 8);
-            u.alloc(gr.d_cex, (size_t)B * gr.A * 4 + 16);
-            if (ch.rank1) {
-                ch.tail_blocks = imc::tail_list<BigBlock>(ch.seg_ids, ch.seg_out);
-                for (uint32_t id : ch.seg_ids)
-                    if (!seg_first[id]) ch.r1_segs.push_back({id, segs[id].len});
+            u.put(ch.d_big_blocks, sch.big_blocks);
+            u.alloc(gr.d_Ctab, (size_t)B * A * np2 * 8);
+            if ((gr.dec.kind == Group::Kind::MatVecChain || gr.dec.rank1) && N < kc->NP && q->key.opt.pack_table)   // the mat-vec chain reads a packed copy
+                u.alloc(ch.d_Cpack, (size_t)B * A * N * (size_t)(N + (N & 1)) * 8);
+            u.alloc(gr.d_cex, (size_t)B * A * 4 + 16);
+            if (gr.dec.rank1) {
                 const size_t nrec = (size_t)B * segs.size();
-                u.put(ch.d_tail_blocks, ch.tail_blocks);
+                u.put(ch.d_tail_blocks, sch.tail_blocks);
                 u.zeroed(ch.d_r1flag, nrec * 4);
                 u.zeroed(ch.d_r1at, nrec * 4);
                 u.alloc(ch.d_r1u, nrec * kc->NP * 8);
@@ -2456,24 +2231,32 @@ int build_plan(const imc_obs *const *chunks, int n_chunks, int N, int S, int B, 
             wide = true;
         }
     }
+    // ---- geometry and schedules (host-only, plan_host.hpp), then the one step that needs the chunk handles ----
     PlanBuilder pb;
-    pb.chunks = chunks; pb.n_chunks = n_chunks; pb.N = N; pb.S = S; pb.B = B; pb.op_mode = op_mode; pb.kc = kc; pb.wide = wide;
     pb.p = std::make_unique<Plan>(std::move(key));
-    pb.p->kc = kc; pb.p->wide = wide;
-    pb.chunk_group = std::move(dec.chunk_group);
-    for (imc::GroupDecision &gd : dec.groups) {
-        Group gr;
-        gr.kind = gd.kind; gr.tokens = gd.tokens; gr.level = gd.level; gr.A = gd.A;
-        if (gd.dict >= 0) gr.dict = dict_of[gd.dict];
-        gr.chunks = std::move(gd.chunks);
-        gr.seglen = gd.seglen; gr.model_us = gd.model_us; gr.model_tab_us = gd.model_tab_us;
-        gr.blk.wide_tokens = gd.wide_tokens;
-        gr.chain.rank1 = gd.rank1; gr.chain.checkpoints = std::move(gd.checkpoints);
-        pb.p->groups.push_back(std::move(gr));
+    Plan *p = pb.p.get();
+    p->kc = kc; p->wide = wide;
+    const bool mfma = kc->use3(p->key.opt.blocked_variant) || wide;     // the blocked kernels of this plan are the fp64-MFMA ones
+    imc::PlanGeometry &geo = pb.geo = imc::plan_geometry(dec, cf, *kc, N, S, op_mode, mfma);
+    if (geo.too_many_vectors) return fail(IMC_ERR_ARG, "too many vectors in one call");
+    p->n_segs = (uint32_t)geo.segs.size();
+    p->n_vecs = (uint32_t)geo.vecs.size();
+    p->pstride = geo.pstride;
+    p->chain_steps = geo.chain_steps;
+    p->finish_fused = geo.finish_fused;
+    for (const imc::SegCut &cut : geo.segs) {
+        const imc::GroupDecision &gd = dec.groups[dec.chunk_group[cut.chunk]];
+        const uint8_t *base = gd.tokens ? chunks[cut.chunk]->d_tok[gd.level] : chunks[cut.chunk]->d_sym;
+        pb.segs.push_back(SegDesc{base + cut.offset * ((cut.flags & SEG_WIDE) ? 2 : 1), cut.len, cut.flags});
     }
-    pb.cut_segments();
-    if (int rc = pb.make_units()) return rc;
-    pb.make_hierarchy();
+    for (size_t q = 0; q < dec.groups.size(); ++q) {
+        Group gr;
+        gr.dec = std::move(dec.groups[q]);
+        gr.geo = std::move(geo.groups[q]);
+        if (gr.dec.dict >= 0) gr.dict = dict_of[gr.dec.dict];
+        gr.sch = imc::group_schedules(p->key.opt, *kc, wide, gr.dec, geo, gr.geo, cf, gr.dict.get(), S, B);
+        p->groups.push_back(std::move(gr));
+    }
     return pb.upload(out);
 }
 
@@ -2547,8 +2330,8 @@ struct Launch {
     void account(const Group &gr) const
     {
         uint64_t *lp = p->lp;
-        if (gr.tokens) { lp[4] = gr.seglen; lp[5] += gr.vsteps * (uint64_t)B; lp[6] += gr.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.A); }
-        else { lp[2] = gr.seglen; lp[3] += gr.vsteps * (uint64_t)B; }
+        if (gr.dec.tokens) { lp[4] = gr.dec.seglen; lp[5] += gr.geo.vsteps * (uint64_t)B; lp[6] += gr.geo.stream_len; lp[7] = std::max(lp[7], (uint64_t)gr.dec.A); }
+        else { lp[2] = gr.dec.seglen; lp[3] += gr.geo.vsteps * (uint64_t)B; }
     }
     int fetch_params();
     BigArgs blocked_args(const Group &gr);
@@ -2563,7 +2346,7 @@ struct Launch {
     int stitch() const;
 };
 
-const char *stream_tag(const Group &gr) { return gr.tokens ? "[tokens]" : "[columns]"; }
+const char *stream_tag(const Group &gr) { return gr.dec.tokens ? "[tokens]" : "[columns]"; }
 
 // Opt a kernel in to LDS_BUDGET bytes of dynamic LDS: one hipFuncSetAttribute per function and device (g.lds_opted).
 template <class Fn>
@@ -2587,15 +2370,15 @@ int Launch::fetch_params()
     int active = 0;
     const Group *only = nullptr;
     for (const Group &gr : p->groups)
-        if (gr.n_vecs) { ++active; only = &gr; }
+        if (gr.geo.n_vecs) { ++active; only = &gr; }
     const size_t head_lds = p->pstride * 8;
-    fuse_head = opt.fuse_head && active == 1 && only->global_table() && opt.table_pairs && only->blk.d_tab_desc2 && !only->blk.tab2.empty() &&
+    fuse_head = opt.fuse_head && active == 1 && only->global_table() && opt.table_pairs && only->blk.d_tab_desc2 && !only->sch.tab2.launches.empty() &&
                 kc->zip4_level2_first && pbytes <= STAGE_KERNEL_MAX_BYTES && head_lds <= 16 * 1024;
     // ... and a SMALL launch of the LDS-table MFMA kernel (the reference's own data sizes: one alignment of 1e5..1e6
     // columns): each of its few workgroups fetches the parameter set itself
-    direct_params = opt.fuse_head && active == 1 && only->kind == Group::Kind::BlockedLds && kc->use3(opt.blocked_variant) && pbytes <= STAGE_KERNEL_MAX_BYTES &&
-                    only->blk.blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
-                    ((kc->blocked_lds(only->A, opt.blocked_variant) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
+    direct_params = opt.fuse_head && active == 1 && only->dec.kind == Group::Kind::BlockedLds && kc->use3(opt.blocked_variant) && pbytes <= STAGE_KERNEL_MAX_BYTES &&
+                    only->geo.blocks.size() * (size_t)B <= 32 && p->pstride * 8 <= 8192 &&
+                    ((kc->blocked_lds(only->dec.A, opt.blocked_variant) + 15) & ~(size_t)15) + p->pstride * 8 <= LDS_BUDGET;
     if (fuse_head || direct_params) {
         // (nothing to enqueue here)
     } else if (pbytes <= STAGE_KERNEL_MAX_BYTES) {
@@ -2612,10 +2395,10 @@ int Launch::fetch_params()
 PropArgs prop_args(const Plan *p, const Group &gr)
 {
     PropArgs a;
-    a.segs = p->d_segs.get(); a.vecs = p->d_vecs.get() + gr.vec_begin; a.n_vecs = gr.n_vecs; a.vec_base = gr.vec_begin;
+    a.segs = p->d_segs.get(); a.vecs = p->d_vecs.get() + gr.geo.vec_begin; a.n_vecs = gr.geo.n_vecs; a.vec_base = gr.geo.vec_begin;
     a.n_vecs_total = p->n_vecs; a.N = p->N; a.S = p->S;
     a.params = p->d_params.get(); a.pstride = p->pstride; a.P = p->levels[0].d_P.get(); a.EX = p->levels[0].d_EX.get();
-    a.A = gr.A; a.tok_left = gr.tokens ? gr.dict->d_left : nullptr; a.tok_right = gr.tokens ? gr.dict->d_right : nullptr;
+    a.A = gr.dec.A; a.tok_left = gr.dec.tokens ? gr.dict->d_left : nullptr; a.tok_right = gr.dec.tokens ? gr.dict->d_right : nullptr;
     return a;
 }
 
@@ -2626,8 +2409,8 @@ BigArgs common_args(const Plan *p, const Group &gr)
     BigArgs ba{};
     ba.segs = p->d_segs.get();
     ba.n_vecs_total = p->n_vecs; ba.n_segs = p->n_segs; ba.n_chunks = p->n_chunks;
-    ba.N = p->N; ba.S = p->S; ba.A = gr.A; ba.params = p->d_params.get(); ba.pstride = p->pstride; ba.PP = p->kc->NP;
-    ba.tok_left = gr.tokens ? gr.dict->d_left : nullptr; ba.tok_right = gr.tokens ? gr.dict->d_right : nullptr;
+    ba.N = p->N; ba.S = p->S; ba.A = gr.dec.A; ba.params = p->d_params.get(); ba.pstride = p->pstride; ba.PP = p->kc->NP;
+    ba.tok_left = gr.dec.tokens ? gr.dict->d_left : nullptr; ba.tok_right = gr.dec.tokens ? gr.dict->d_right : nullptr;
     ba.Ctab = gr.d_Ctab.get(); ba.cex = gr.d_cex.get();
     ba.P = p->levels[0].d_P.get(); ba.EX = p->levels[0].d_EX.get();
     ba.t_to = INT_MAX;
@@ -2639,9 +2422,9 @@ BigArgs common_args(const Plan *p, const Group &gr)
 BigArgs big_args(const Plan *p, const Group &gr)
 {
     BigArgs ba = common_args(p, gr);
-    ba.n_group_segs = (uint32_t)gr.chain.seg_ids.size();
+    ba.n_group_segs = (uint32_t)gr.geo.seg_ids.size();
     ba.Cpack = gr.chain.d_Cpack.get(); ba.TS = p->N + (p->N & 1);
-    ba.phase = gr.chain.rank1 ? 1 : 0; ba.t_to = gr.chain.rank1 ? gr.chain.checkpoints[0] : INT_MAX;
+    ba.phase = gr.dec.rank1 ? 1 : 0; ba.t_to = gr.dec.rank1 ? gr.dec.checkpoints[0] : INT_MAX;
     ba.r1flag = gr.chain.d_r1flag.get(); ba.r1at = gr.chain.d_r1at.get(); ba.r1u = gr.chain.d_r1u.get(); ba.r1alpha = gr.chain.d_r1alpha.get();
     return ba;
 }
@@ -2649,10 +2432,10 @@ BigArgs big_args(const Plan *p, const Group &gr)
 // Raw symbols, then the merged tokens: one launch per run of one dictionary depth (tokens of a depth are independent)
 int Launch::big_table(const Group &gr, const BigArgs &ba) const
 {
-    if (gr.chain.rank1) HIP_TRY(hipMemsetAsync(gr.chain.d_r1flag.get(), 0, (size_t)p->B * p->n_segs * 4, stream));   // nothing certified yet
+    if (gr.dec.rank1) HIP_TRY(hipMemsetAsync(gr.chain.d_r1flag.get(), 0, (size_t)p->B * p->n_segs * 4, stream));   // nothing certified yet
     hipLaunchKernelGGL(kc->big_table_raw, dim3((unsigned)p->S, (unsigned)p->B), dim3(kc->G * 64), 0, stream, ba);
     HIP_TRY(hipGetLastError());
-    for (const auto &run : gr.chain.table_runs) {
+    for (const auto &run : gr.sch.table_runs) {
         hipLaunchKernelGGL(kc->big_table_level, dim3((unsigned)run.second, (unsigned)p->B), dim3(kc->G * 64), 0,
                            stream, ba, (const uint16_t *)gr.dict->d_order, run.first);
         HIP_TRY(hipGetLastError());
@@ -2665,10 +2448,10 @@ int Launch::matvec_chain(const Group &gr)
 {
     const BigArgs ba = big_args(p, gr);
     if (int rc = big_table(gr, ba)) return rc;
-    const unsigned grid = B >= 8 ? 8u * (unsigned)gr.chain.big_blocks.size() * (unsigned)((B + 7) / 8)
-                                 : (unsigned)gr.chain.big_blocks.size() * (unsigned)B;
+    const unsigned grid = B >= 8 ? 8u * (unsigned)gr.sch.big_blocks.size() * (unsigned)((B + 7) / 8)
+                                 : (unsigned)gr.sch.big_blocks.size() * (unsigned)B;
     hipLaunchKernelGGL(kc->big_vec, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                       (const BigBlock *)gr.chain.d_big_blocks.get(), (int)gr.chain.big_blocks.size(), B);
+                       (const BigBlock *)gr.chain.d_big_blocks.get(), (int)gr.sch.big_blocks.size(), B);
     note("k_big_vector<" + std::to_string(kc->G) + ">" + stream_tag(gr));
     account(gr);
     HIP_TRY(hipGetLastError());
@@ -2681,27 +2464,27 @@ int Launch::gemm_chain(const Group &gr)
     BigArgs ba = big_args(p, gr);
     if (int rc = big_table(gr, ba)) return rc;
     if (int rc = allow_lds_budget(kc->big_prop)) return rc;
-    const dim3 prop_grid((unsigned)gr.chain.big_blocks.size(), (unsigned)B), prop_block(kc->big_prop_waves * 64);
+    const dim3 prop_grid((unsigned)gr.sch.big_blocks.size(), (unsigned)B), prop_block(kc->big_prop_waves * 64);
     hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.chain.d_big_blocks.get());
     note(std::string(kc->big_prop_waves != kc->G ? "k_big_propagate_s<" : "k_big_propagate<") + std::to_string(kc->G) + ">" + stream_tag(gr));
-    if (gr.chain.rank1 && !gr.chain.tail_blocks.empty()) {
+    if (gr.dec.rank1 && !gr.sch.tail_blocks.empty()) {
         // The first round of heads is done.  Per checkpoint: certify which of the operators still on the GEMM
         // chain collapsed to rank one, then run the others up to the next checkpoint; after the last one the
         // certified segments finish on the mat-vec chain and the rest on the GEMM chain.  Every launch covers
         // all segments and a workgroup with nothing to do exits at once, so there is no host round trip.
-        for (size_t r = 0; r < gr.chain.checkpoints.size(); ++r) {
+        for (size_t r = 0; r < gr.dec.checkpoints.size(); ++r) {
             HIP_TRY(hipGetLastError());
-            ba.t_to = gr.chain.checkpoints[r];
-            hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.chain.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
+            ba.t_to = gr.dec.checkpoints[r];
+            hipLaunchKernelGGL(k_rank1_check, dim3((unsigned)gr.sch.tail_blocks.size(), (unsigned)B), dim3(1024), 0, stream, ba,
                                (const BigBlock *)gr.chain.d_tail_blocks.get(), kc->NP);
             HIP_TRY(hipGetLastError());
-            ba.t_from = gr.chain.checkpoints[r];
-            ba.t_to = r + 1 < gr.chain.checkpoints.size() ? gr.chain.checkpoints[r + 1] : INT_MAX;
-            if (r + 1 == gr.chain.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
-                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.chain.tail_blocks.size() * (unsigned)((B + 7) / 8)
-                                             : (unsigned)gr.chain.tail_blocks.size() * (unsigned)B;
+            ba.t_from = gr.dec.checkpoints[r];
+            ba.t_to = r + 1 < gr.dec.checkpoints.size() ? gr.dec.checkpoints[r + 1] : INT_MAX;
+            if (r + 1 == gr.dec.checkpoints.size()) {   // the mat-vec tails first: they are the long launch
+                const unsigned grid = B >= 8 ? 8u * (unsigned)gr.sch.tail_blocks.size() * (unsigned)((B + 7) / 8)
+                                             : (unsigned)gr.sch.tail_blocks.size() * (unsigned)B;
                 hipLaunchKernelGGL(kc->big_vec_tail, dim3(grid), dim3(kc->big_vec_waves * 64), 0, stream, ba,
-                                   (const BigBlock *)gr.chain.d_tail_blocks.get(), (int)gr.chain.tail_blocks.size(), B);
+                                   (const BigBlock *)gr.chain.d_tail_blocks.get(), (int)gr.sch.tail_blocks.size(), B);
                 HIP_TRY(hipGetLastError());
             }
             hipLaunchKernelGGL(kc->big_prop, prop_grid, prop_block, kc->big_lds, stream, ba, (const BigBlock *)gr.chain.d_big_blocks.get());
@@ -2719,12 +2502,12 @@ BigArgs Launch::blocked_args(const Group &gr)
 {
     BigArgs ba = common_args(p, gr);
     ba.blocks = gr.blk.d_blocks.get();
-    ba.n_group_segs = (uint32_t)gr.blk.blocks.size();
-    ba.tab_order = gr.blk.d_tab_order.get(); ba.tab_lvl = gr.blk.d_tab_lvl.get(); ba.tab_nlvl = gr.blk.tab_nlvl;
-    ba.hot = gr.blk.d_hot.get(); ba.n_hot = gr.blk.n_hot; ba.tab_desc = gr.blk.d_tab_desc.get();
-    if (gr.blk.d_tails && (opt.fuse_tail == 2 || (opt.fuse_tail == 1 && gr.blk.tail_stride <= 4)) && allow_tail && (kc->use3(opt.blocked_variant) || p->wide)) {
+    ba.n_group_segs = (uint32_t)gr.geo.blocks.size();
+    ba.tab_order = gr.blk.d_tab_order.get(); ba.tab_lvl = gr.blk.d_tab_lvl.get(); ba.tab_nlvl = gr.sch.tab.nlvl;
+    ba.hot = gr.blk.d_hot.get(); ba.n_hot = gr.sch.n_hot; ba.tab_desc = gr.blk.d_tab_desc.get();
+    if (gr.blk.d_tails && (opt.fuse_tail == 2 || (opt.fuse_tail == 1 && gr.geo.tail_stride <= 4)) && allow_tail && (kc->use3(opt.blocked_variant) || p->wide)) {
         ba.tail = gr.blk.d_tails.get(); ba.tailX = gr.blk.d_tailX.get(); ba.tailE = gr.blk.d_tailE.get(); ba.tail_arrive = gr.blk.d_tail_arrive.get();
-        ba.tail_out = out; ba.tail_stride = gr.blk.tail_stride;
+        ba.tail_out = out; ba.tail_stride = gr.geo.tail_stride;
         tail_used = true;
     }
     return ba;
@@ -2743,7 +2526,7 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
     if (opt.table_pairs && (opt.table_triples == 1 || (opt.table_triples < 0 && kc->NP <= 12)) && gr.blk.d_tab_desc3 && kc->zip4_level3) {
         if (int rc = allow_lds_budget(kc->zip4_level3)) return rc;
         if (int rc = allow_lds_budget(kc->zip4_level3_first)) return rc;
-        for (const auto &lc : gr.blk.tab3) {          // three dictionary depths per launch, one wavefront per token
+        for (const auto &lc : gr.sch.tab3.launches) {          // three dictionary depths per launch, one wavefront per token
             const dim3 grid((unsigned)(lc.second + Z4L3_WAVES - 1) / Z4L3_WAVES, (unsigned)B);
             if (head)
                 hipLaunchKernelGGL(kc->zip4_level3_first, grid, dim3(Z4L3_WAVES * 64), kc->zip4_level3_lds(p->pstride), stream, ba,
@@ -2756,7 +2539,7 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
         }
     } else if (opt.table_pairs && gr.blk.d_tab_desc2 && kc->zip4_level2) {
         const size_t split_max = opt.table_split_max >= 0 ? (size_t)opt.table_split_max : (size_t)4 * opt.cus;
-        for (const auto &lc : gr.blk.tab2) {          // two dictionary depths per launch
+        for (const auto &lc : gr.sch.tab2.launches) {          // two dictionary depths per launch
             if (opt.table_split && (size_t)lc.second * B <= split_max) {     // a latency launch: one token per wavefront
                 if (head)
                     hipLaunchKernelGGL(kc->zip4_level2_split_first, dim3((unsigned)(lc.second + Z4_SPLIT_WAVES_FIRST - 1) / Z4_SPLIT_WAVES_FIRST, (unsigned)B),
@@ -2778,8 +2561,8 @@ int Launch::z4_table(const Group &gr, const BigArgs &ba)
             HIP_TRY(hipGetLastError());
         }
     } else
-        for (int d = 0; d < gr.blk.tab_nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
-            const int first = gr.blk.tab_lvl[d], count = gr.blk.tab_lvl[d + 1] - first;
+        for (int d = 0; d < gr.sch.tab.nlvl; ++d) {   // one launch per dictionary depth: kernel boundaries order the depths
+            const int first = gr.sch.tab.lvl[d], count = gr.sch.tab.lvl[d + 1] - first;
             hipLaunchKernelGGL(kc->zip4_level, dim3((unsigned)(count + 3) / 4, (unsigned)B), dim3(64), 0, stream, ba, first, count);
             HIP_TRY(hipGetLastError());
         }
@@ -2791,20 +2574,20 @@ int Launch::zip4(const Group &gr)
 {
     BigArgs ba = blocked_args(gr);
     if (int rc = z4_table(gr, ba)) return rc;
-    void (*scan)(BigArgs) = gr.blk.stream_table ? (gr.blk.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.blk.wide_tokens ? kc->zip4w : kc->zip4);
+    void (*scan)(BigArgs) = gr.sch.stream_table ? (gr.dec.wide_tokens ? kc->zip4sw : kc->zip4s) : (gr.dec.wide_tokens ? kc->zip4w : kc->zip4);
     if (int rc = allow_lds_budget(scan)) return rc;
     if (int rc = mark_a()) return rc;
     // XCD-affine grid (BigArgs::n_phases): with the two-dimensional grid every XCD's L2 sees the tables of all
     // B parameter sets
     dim3 scan_grid(ba.n_group_segs, (unsigned)B);
     if (opt.xcd_affine && B > 1) {
-        const imc::PhaseTable &t = gr.blk.phases;
+        const imc::PhaseTable &t = gr.sch.phases;
         ba.n_phases = t.n_phases;
         for (int k = 0; k < t.n_phases; ++k) { ba.ph_begin[k] = t.ph_begin[k]; ba.ph_first[k] = t.ph_first[k]; ba.ph_sets[k] = t.ph_sets[k]; }
         scan_grid = dim3((unsigned)t.grid);
     }
-    hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.A, gr.blk.n_hot), stream, ba);
-    note(std::string("k_zpropagate4<") + std::to_string(kc->NP / 4) + (gr.blk.wide_tokens ? ",16" : "") + (gr.blk.stream_table ? ",streamed>" : ">") + stream_tag(gr));
+    hipLaunchKernelGGL(scan, scan_grid, dim3(kc->z4_waves * 64), kc->zip4_lds(gr.dec.A, gr.sch.n_hot), stream, ba);
+    note(std::string("k_zpropagate4<") + std::to_string(kc->NP / 4) + (gr.dec.wide_tokens ? ",16" : "") + (gr.sch.stream_table ? ",streamed>" : ">") + stream_tag(gr));
     account(gr);
     HIP_TRY(hipGetLastError());
     return IMC_OK;
@@ -2817,7 +2600,7 @@ int Launch::zip32(const Group &gr)
     const bool v3 = kc->use3(opt.blocked_variant);
     void (*scan)(BigArgs) = v3 ? kc->zip3 : kc->zip2;
     if (int rc = allow_lds_budget(scan)) return rc;
-    size_t lds3 = kc->blocked_lds(gr.A, opt.blocked_variant);
+    size_t lds3 = kc->blocked_lds(gr.dec.A, opt.blocked_variant);
     if (direct_params) { ba.params_src = p->h_params_dev[p->slot]; lds3 = ((lds3 + 15) & ~(size_t)15) + p->pstride * 8; }
     hipLaunchKernelGGL(scan, dim3(ba.n_group_segs, (unsigned)p->B), dim3(Z2WAVES * 64), lds3, stream, ba);
     note(std::string(v3 ? "k_zpropagate3<" : "k_zpropagate2<") + std::to_string(kc->NP / 4) + ">" + stream_tag(gr));
@@ -2830,10 +2613,10 @@ int Launch::zip32(const Group &gr)
 
 int Launch::zpropagate(const Group &gr)
 {
-    const size_t lds = kc->zip_lds(gr.A);
+    const size_t lds = kc->zip_lds(gr.dec.A);
     if (int rc = allow_lds_budget(kc->zip)) return rc;
     const uint32_t vpb = (uint32_t)(ZWAVES * kc->VPW);
-    dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
+    dim3 grid((gr.geo.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
     hipLaunchKernelGGL(kc->zip, grid, dim3(ZWAVES * 64), lds, stream, prop_args(p, gr));
     note("k_zpropagate<" + std::to_string(kc->R) + "," + std::to_string(kc->G) + ">" + stream_tag(gr));
     account(gr);
@@ -2844,7 +2627,7 @@ int Launch::zpropagate(const Group &gr)
 int Launch::propagate(const Group &gr)
 {
     const uint32_t vpb = (uint32_t)(WPB * kc->VPW);
-    dim3 grid((gr.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
+    dim3 grid((gr.geo.n_vecs + vpb - 1) / vpb, (unsigned)p->B);
     const size_t lds = ((size_t)WPB * kc->VPW * kc->NP + (size_t)p->S * kc->NP) * 8;
     if (lds > LDS_BUDGET) return fail(IMC_ERR_ARG, "emission table (S x N) too large for LDS");
     if (lds > 48 * 1024)                  // large alphabets: opt in to > 64 KB of dynamic LDS
@@ -2903,11 +2686,11 @@ int enqueue(Plan *p, hipStream_t stream, double *out, bool allow_tail = true)
     if (L.prof) { HIP_TRY(hipEventCreate(&L.ev.a)); HIP_TRY(hipEventCreate(&L.ev.b)); HIP_TRY(hipEventCreate(&L.ev.c)); }
     p->kernels.clear();
     for (const Group &gr : p->groups) {
-        if (!gr.n_vecs) continue;
+        if (!gr.geo.n_vecs) continue;
         if (!gr.global_table())
             if (int rc = L.mark_a()) return rc;
         int rc = IMC_OK;
-        switch (gr.kind) {
+        switch (gr.dec.kind) {
         case Group::Kind::ColumnVector: rc = L.propagate(gr); break;
         case Group::Kind::TokenVector: rc = L.zpropagate(gr); break;
         case Group::Kind::BlockedLds: rc = L.zip32(gr); break;
@@ -2946,12 +2729,12 @@ void collect_rank1_stats(Plan *p)
 {
     g.r1_checked = g.r1_collapsed = 0;
     for (Group &gr : p->groups) {
-        if (!gr.chain.rank1 || gr.chain.r1_segs.empty() || gr.chain.checkpoints.empty()) continue;
+        if (!gr.dec.rank1 || gr.sch.r1_segs.empty() || gr.dec.checkpoints.empty()) continue;
         std::vector<int> flags((size_t)p->B * p->n_segs);
         if (hipMemcpy(flags.data(), gr.chain.d_r1flag.get(), flags.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
         for (int b = 0; b < p->B; ++b)
-            for (const auto &sl : gr.chain.r1_segs) {
-                if ((int)sl.second <= gr.chain.checkpoints[0]) continue;
+            for (const auto &sl : gr.sch.r1_segs) {
+                if ((int)sl.second <= gr.dec.checkpoints[0]) continue;
                 ++g.r1_checked;
                 g.r1_collapsed += flags[(size_t)b * p->n_segs + sl.first] ? 1 : 0;
             }
@@ -2959,9 +2742,9 @@ void collect_rank1_stats(Plan *p)
             std::vector<int> at((size_t)p->B * p->n_segs);
             if (hipMemcpy(at.data(), gr.chain.d_r1at.get(), at.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
             std::map<int, int> hist;
-            for (const auto &sl : gr.chain.r1_segs) hist[flags[sl.first] ? at[sl.first] : -1]++;
-            fprintf(stderr, "[imc] rank-one hand-off: segment length %zu tokens, checkpoints", (size_t)gr.seglen);
-            for (int c : gr.chain.checkpoints) fprintf(stderr, " %d", c);
+            for (const auto &sl : gr.sch.r1_segs) hist[flags[sl.first] ? at[sl.first] : -1]++;
+            fprintf(stderr, "[imc] rank-one hand-off: segment length %zu tokens, checkpoints", (size_t)gr.dec.seglen);
+            for (int c : gr.dec.checkpoints) fprintf(stderr, " %d", c);
             fprintf(stderr, "\n[imc]   certified at (tokens: segments)");
             for (auto &kv : hist) fprintf(stderr, " %d:%d", kv.first, kv.second);
             fprintf(stderr, "\n");

@@ -19,14 +19,7 @@
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-struct Z2Block {                  // one workgroup of k_zpropagate2: up to Z2SLOTS consecutive segments of one chunk
-    uint32_t seg0, n;             // first segment id, number of segments
-    uint32_t out_vec0;            // where the block's combined result goes (level-0 vector index)
-    uint32_t first;               // 1: seg0 is its chunk's first segment -> the result is a vector; 2 (MFMA forms): a PACKED block -
-                                  // every one of the n segments is a whole chunk, slot s writes its vector to out_vec0 + s, no fold
-};
-
-struct Z2Tail { uint32_t chunk, unit, n_units, pad; };
+// (Z2Block, Z2Tail, BigBlock - the workgroup lists of the blocked scan, its fused tail and the chains: launch_desc.hpp)
 
 struct BigArgs {
     const SegDesc *segs;          // all segments of the plan
@@ -332,13 +325,7 @@ __global__ __launch_bounds__(NT * 64) void k_big_table_level(BigArgs a, const ui
 // is written back into it after each step): P never touches global memory, and the only streamed operand
 // is the token operator's 16-deep A panels (double-buffered through LDS).  Wavefront w owns tile-row w:
 // NT/NSLAB accumulator tiles.  Slabs of one segment are given block ids 8 apart so that they land on the
-// same XCD and share the operator rows in its L2.
-struct BigBlock {
-    uint32_t seg;        // segment id
-    uint32_t slab;       // column slab index
-    uint32_t out_vec0;   // level-0 vector index of the segment's result
-    uint32_t pad;
-};
+// same XCD and share the operator rows in its L2 (BigBlock, imc::deal_slabs).
 
 template <int NT, int NSLAB>
 struct BigSlab {

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "launch_desc.hpp"
+
 // =====================================================================================================
 // Device side
 // =====================================================================================================
@@ -32,18 +34,13 @@ struct SegDesc {          // one segment of one chunk
     uint32_t len;         // columns in this segment
     uint32_t first;       // bit 0: first segment of its chunk (single vector, starts from pi); bit 1: 16-bit tokens
 };
-static constexpr uint32_t SEG_FIRST = 1u, SEG_WIDE = 2u;
+// (SEG_FIRST, SEG_WIDE: launch_desc.hpp)
 
 // token t of a segment: bytes, or 16-bit ids on the wide dictionary levels (large-N kernels only)
 __device__ __forceinline__ int seg_token(const uint8_t *p, bool wide, int t)
 {
     return wide ? (int)reinterpret_cast<const uint16_t *>(p)[t] : (int)p[t];
 }
-
-struct VecDesc {          // one propagated vector
-    uint32_t seg;         // segment id
-    uint32_t c;           // basis index (0 for a first segment)
-};
 
 struct PropArgs {
     const SegDesc *segs;   // all segments of the plan

@@ -11,15 +11,7 @@
 #include "kernels_plain.hpp"
 #include <utility>
 
-struct ChainDesc {
-    uint32_t seg_begin, seg_end;   // input segments [begin, end) of the previous level
-    uint32_t c;                    // basis index when the run does not start its chunk
-    uint32_t out_vec;              // output vector index in the next level
-    uint32_t first;                // 1: the run starts with its chunk's first segment (a vector)
-    uint32_t chunk1;               // last level only: 1 + the chunk whose final vector this chain produces (0: none)
-    uint32_t vec_first;            // first == 1: that vector's index in the previous level
-    uint32_t vbase;                // first vector of the run's first operator (operator t starts at vbase + t*N); 0: no operator
-};
+// (ChainDesc, one chain of a level: launch_desc.hpp)
 
 // How a step of k_chain<NP, D > 0> hands the rescaled vector (entry m in lane m) to every lane.
 //   CHAIN_LDS   through LDS: one write, a fence, NP/2 broadcast 16-byte reads

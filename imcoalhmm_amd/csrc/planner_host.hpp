@@ -1,9 +1,9 @@
 // planner_host.hpp - host-only decisions of the launch planner: which dictionary level a dictionary's chunks run on, the
 // launch groups and the kernel family of each, the segment length, the rank-one checkpoints, and the comparisons between
 // kernel entries that build_plan makes.  Everything here is a pure function of plain facts (PlanOptions, KernelFacts,
-// ChunkFacts, DictFacts): no HIP and no device pointers.  imcoal_fwd.hip gathers the facts from its chunk handles
-// and turns a PlanDecision into launch descriptors; tests/planner_host_check.cpp asks the same functions on the CPU
-// under ASan/UBSan.
+// ChunkFacts, DictFacts): no HIP and no device pointers.  imcoal_fwd.hip gathers the facts from its chunk handles,
+// plan_host.hpp turns a PlanDecision into launch descriptors; tests/planner_host_check.cpp asks the same functions on
+// the CPU under ASan/UBSan.
 #pragma once
 
 #include <algorithm>
@@ -19,7 +19,6 @@
 
 #include "options_host.hpp"
 #include "pair_dict.hpp"
-#include "plan_host.hpp"
 
 namespace imc {
 
@@ -55,6 +54,8 @@ enum class GroupKind {
     GemmChain,       // large-N GEMM chain (one workgroup per segment and column slab): k_big_propagate
     MatVecChain,     // ... every chunk is one segment: mat-vec chain (k_big_vector), no operators
 };
+inline bool is_chain(GroupKind k) { return k == GroupKind::GemmChain || k == GroupKind::MatVecChain; }
+inline bool is_blocked(GroupKind k) { return k == GroupKind::BlockedLds || k == GroupKind::BlockedGlobal; }
 
 // What the planner reads: the options record (options_host.hpp; the planner's own fields are its first group), the
 // device's size and the per-call variables; build_plan fills one per call and the plan keeps it.
@@ -533,7 +534,7 @@ struct GroupDecider {
                     size_t seg_blk = 16;
                     double slots = 0.0, cost_blk = 1e300;
                     // a workgroup takes 32 consecutive segments of ONE chunk: rows are allocated per chunk in 32s
-                    // (... except chunks that are ONE segment: those are packed, a row each - make_units)
+                    // (... except chunks that are ONE segment: those are packed, a row each - plan_geometry)
                     const bool can_pack = mfma() && !op_mode;
                     auto rows_used = [&](size_t sg) {
                         double r = 0.0, singles = 0.0;

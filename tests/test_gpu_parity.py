@@ -754,7 +754,7 @@ def test_every_number_of_parameter_sets_reaches_every_workgroup(oracle, hmm_para
 
 @pytest.mark.parametrize("n", [10, 20])
 def test_many_short_chunks_share_workgroups(oracle, hmm_params, n):
-    """Packed blocks (Z2Block::first == 2, csrc/imcoal_fwd.hip make_units): chunks that are a single segment take a slot each
+    """Packed blocks (Z2Block::first == 2, csrc/plan_host.hpp plan_geometry): chunks that are a single segment take a slot each
     of a shared workgroup instead of a workgroup each.  Hundreds of short chunks of every length around the 16-token block
     size - runs of them broken by long chunks (which are cut and folded as before) and by empty ones - on the LDS-table and
     the global-table kernel, two parameter sets: every chunk against the oracle."""

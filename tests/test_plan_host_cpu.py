@@ -1,7 +1,13 @@
 """Host-only launch geometry (csrc/plan_host.hpp) under AddressSanitizer + UBSan on the CPU: tests/plan_host_check.cpp
 trains dictionaries on sticky random streams and checks the depth order, the two- and three-depths-per-launch table
 schedules, the depth runs of the GEMM chain's table, the hot-set order, the workgroup dealing of the GEMM chain and the
-XCD-affine phase table against what the kernels that run from them need.
+XCD-affine phase table against what the kernels that run from them need.  The same program checks the geometry of a
+plan, imc::plan_geometry: over states of every table family (28 and 32 with the wide scan too), 1 / 3 / 9 parameter
+sets, both operator modes, the compression modes, forced segment lengths and chunk sets with an empty chunk, chunks
+shorter than a segment, many one-segment chunks and one long chunk beside many short ones, it asserts what the kernels
+need of the segments, stitch units, vectors, block lists, fused-tail records, stitch hierarchy and finish_fused, and
+fails if its sweep never met a packed block, a fused tail, one withdrawn for packed blocks, either finish_fused, an
+empty chunk, the operator mode, a hierarchy of three levels or one of the group kinds.
 
 The planner's decisions (csrc/planner_host.hpp) the same way: tests/planner_host_check.cpp gathers chunk facts from such
 dictionaries, puts small stand-ins behind the kernel table's LDS size functions and sweeps states, parameter sets, chunk
