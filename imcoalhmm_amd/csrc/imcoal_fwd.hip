@@ -16,14 +16,14 @@
 // (imc::GroupKind) by the host-only planner in planner_host.hpp; the kernel families themselves are described in
 // DESIGN.md section 5.
 //
-// Host side, in the order of this file (every function stands behind what it calls; the run-time options are
-// options_host.hpp's record): context and device memory (dev_alloc, DevBuf); chunks and dictionaries (padded buffers, obs_new
+// Host side, in the order of this file and of the engine_*.hpp it includes (every function stands behind what it calls; the
+// run-time options are options_host.hpp's record): context and device memory (dev_alloc, DevBuf: engine_core.hpp); chunks and dictionaries (padded buffers, obs_new
 // and the owner of a chunk under construction, the level loop install_levels with its host and device sources, the device
 // trainer, dictionary_for, obs_upload / obs_from_device, device ingestion of files and sequence pairs, resident alignments; the
 // training policy is pair_dict.hpp's, the level rule encode_tiles.hpp's, the parses ingest_tiles.hpp's and align_tiles.hpp's);
 // the kernel table, the launch plan (Group / Level / Plan own their device buffers; a Group holds its imc::GroupDecision and its
 // part of the geometry), the plan list with recompress_alphabet behind it, the plan builder, one enqueue function per kernel
-// family, the model layer, the sampler, the C ABI.  A plan is made by host-only functions - imc::decide_groups
+// family, the model layer (engine_model.hpp), the sampler (engine_sample.hpp), the C ABI.  A plan is made by host-only functions - imc::decide_groups
 // (planner_host.hpp), then imc::plan_geometry and imc::group_schedules (plan_host.hpp: segments, stitch units, vectors, block
 // lists, fused-tail records, the stitch hierarchy; workgroup lists, table schedules, hot set, phase table) - and build_plan adds
 // the one step that needs the chunk handles, a segment's device pointer; PlanBuilder::upload() then only evicts, allocates,
@@ -79,248 +79,7 @@
 #include "obs_io.hpp"
 #include "fasta_io.hpp"
 
-static_assert(sizeof(imc::Desc4) == sizeof(int4) && alignof(imc::Desc4) == alignof(int4), "descriptor entries are uploaded as int4");
-
-namespace {
-
-thread_local std::string g_err;
-std::mutex g_mu;
-std::condition_variable g_cv;   // signalled when a plan stops being busy (see Plan::busy)
-
-int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return fail(_e == hipErrorOutOfMemory ? IMC_ERR_OOM : IMC_ERR_HIP,                          \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                             \
-    } while (0)
-
-// the planner's constants and helpers that the rest of this file uses too (planner_host.hpp)
-using imc::HYBRID_MAX_ALPHABET;
-using imc::LDS_BUDGET;
-using imc::Z2GRAN;
-using imc::round_up;
-
-constexpr size_t STAGE_KERNEL_MAX_BYTES = 1u << 20;   // parameter sets up to this size are fetched by k_stage_params (enqueue)
-
-// ---- device memory -----------------------------------------------------------------------------------
-// Every device buffer of the library comes from here.  Normal mode: hipMalloc / hipFree.  Guard mode (IMC_GUARD=1, a
-// test facility): each buffer is its own virtual-memory reservation with NO mapping behind its last 16-byte unit, so
-// a kernel that reads or writes even one vector load past a buffer's declared size faults deterministically instead of
-// silently touching whatever the allocator happened to place next (tests/test_gpu_guard.py runs the create / free /
-// compression-flip / create sequence of round 1's unexplained fault this way).  dev_free stands here, in front of DictDev, whose
-// destructor calls it; dev_alloc reads the context and follows ensure_ctx().
-struct GuardRec { hipDeviceptr_t va; size_t va_size; hipMemGenericAllocationHandle_t handle; hipDeviceptr_t map; size_t map_size; };
-// (never destroyed: the context `g` - whose dictionaries free device buffers in their destructors - outlives every
-// other static at process exit, and dev_free must still find the guard records then; a plain static map is destroyed
-// first and the lookup walked freed nodes: "malloc_consolidate(): invalid chunk size" at exit under IMC_GUARD=1)
-std::map<void *, GuardRec> &g_guard = *new std::map<void *, GuardRec>();
-
-void dev_free(void *p)
-{
-    if (!p) return;
-    auto it = g_guard.find(p);
-    if (it == g_guard.end()) { (void)hipFree(p); return; }
-    (void)hipDeviceSynchronize();
-    (void)hipMemUnmap(it->second.map, it->second.map_size);
-    (void)hipMemRelease(it->second.handle);
-    // The address range is NOT given back (hipMemAddressFree): a freed guard buffer stays unmapped for the rest of the
-    // process, so a use after free faults too - and no later buffer can be mapped at an address some CU may still hold a
-    // translation for.  (Round 3: with the ranges recycled, a Forwarder created right after another had been freed
-    // sometimes evaluated to a wrong value in every plan - 3 of 4 processes, under IMC_GUARD=1 only, never with hipMalloc -
-    // and a later launch faulted at an address nobody had computed; with the ranges kept, neither was seen again.)
-    g_guard.erase(it);
-}
-
-struct DictDev : imc::TrainedDict {                // one trained dictionary (dict, depth, order: pair_dict.hpp) + its device copy
-    uint16_t *d_left = nullptr, *d_right = nullptr;
-    uint16_t *d_order = nullptr;                   // device copy of order
-    uint64_t trained_on = 0;                       // columns of the chunk(s) the training sample was drawn from
-    pid_t pid = 0;
-    DictDev(imc::TrainedDict t, uint64_t columns) : imc::TrainedDict(std::move(t)), trained_on(columns) {}
-    ~DictDev()
-    {
-        if (pid == getpid()) { dev_free(d_left); dev_free(d_right); dev_free(d_order); }
-    }
-};
-
-struct Ev3 { hipEvent_t a, b, c; };   // a: before propagate, b: after propagate, c: after stitch
-
-struct Ctx {
-    pid_t pid = 0;
-    int device = -1;          // -1: use the thread's current device at first use
-    bool ready = false;
-    hipStream_t stream = nullptr;
-    int cus = 256;
-    uint64_t next_obs_id = 1, next_dict_id = 1;
-    imc::Options opt;         // the knobs (options_host.hpp): set by the ABI's setters and by the table of variables
-    bool profile = false;
-    std::vector<Ev3> events;
-    std::map<int, std::shared_ptr<DictDev>> dicts;   // by raw alphabet size
-    uint64_t last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t last_ingest[4] = {0, 0, 0, 0};      // imc_last_ingest: path, bytes sent to the device, slabs, columns
-    uint64_t last_training[4] = {0, 0, 0, 0};    // imc_last_training: path, symbols in the sample, byte-phase attempts, 16-bit rounds
-    uint64_t r1_checked = 0, r1_collapsed = 0;   // last call: operator segments tested / certified rank one
-    std::string last_kernels;   // propagate kernels of the last enqueue, e.g. "k_zpropagate2<5>[tokens]"
-    std::vector<const void *> lds_opted;   // kernels of this device that may use LDS_BUDGET bytes of dynamic LDS (allow_lds_budget)
-} g;
-
-int ensure_ctx()
-{
-    const pid_t me = getpid();
-    if (g.ready && g.pid == me) return IMC_OK;
-    if (g.ready && g.pid != me)
-        // A forked child of a process that had already used the GPU: the parent's HIP state (context, streams, every
-        // device pointer held by cached plans and dictionaries) is not usable here and HIP cannot be re-initialised
-        // after fork().  Refuse instead of guessing; nothing of the parent's is freed or touched.  Children that
-        // build their own Forwarders (mcmc.py:112-121) must be forked BEFORE the parent's first library call.
-        return fail(IMC_ERR_HIP, "libimcoal_fwd was initialised in the parent process before fork(): fork the chain "
-                                 "processes before the first imc_* call of the parent, or use the spawn start method");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(IMC_ERR_NODEVICE, "no HIP device available (libimcoal_fwd has no CPU fallback)");
-    if (g.device < 0) {
-        int cur = 0;
-        if (hipGetDevice(&cur) != hipSuccess) cur = 0;
-        g.device = cur;
-    }
-    if (g.device >= n) return fail(IMC_ERR_NODEVICE, "requested device index out of range");
-    HIP_TRY(hipSetDevice(g.device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, g.device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(IMC_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    g.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    imc::read_options(g.opt, imc::ReadAt::Context, imc::process_env);
-    g.pid = me;
-    g.ready = true;
-    return IMC_OK;
-}
-
-// A device switch of the record (device_encode, device_ingest, device_train; g_mu held, no device needed): its variable
-// decides until the API has set it.
-int device_mode(int imc::Options::*field) { return imc::device_switch(g.opt, field, imc::process_env); }
-
-// ... and its setter (imc_set_device_encoding / _ingest / _training; takes g_mu): 0 or 1, anything else is `refusal`.
-int set_device_mode(int imc::Options::*field, int mode, const char *refusal)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (mode != 0 && mode != 1) return fail(IMC_ERR_ARG, refusal);
-    g.opt.*field = mode;
-    return IMC_OK;
-}
-
-// (device memory, continued)
-hipError_t dev_alloc(void **p, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 16);
-    if (!g.opt.guard) return hipMalloc(p, bytes);
-    hipMemAllocationProp prop{};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = g.device;
-    size_t gran = 0;
-    hipError_t e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum);
-    if (e != hipSuccess || gran == 0) return e != hipSuccess ? e : hipErrorUnknown;
-    GuardRec r{};
-    r.map_size = (bytes + gran - 1) / gran * gran;
-    r.va_size = r.map_size + 2 * gran;              // one unmapped granule before, one after
-    e = hipMemAddressReserve(&r.va, r.va_size, gran, nullptr, 0);
-    if (e != hipSuccess) return e;
-    e = hipMemCreate(&r.handle, r.map_size, &prop, 0);
-    if (e != hipSuccess) { (void)hipMemAddressFree(r.va, r.va_size); return e; }
-    r.map = (hipDeviceptr_t)((char *)r.va + gran);
-    e = hipMemMap(r.map, r.map_size, 0, r.handle, 0);
-    if (e == hipSuccess) {
-        hipMemAccessDesc ad{};
-        ad.location = prop.location;
-        ad.flags = hipMemAccessFlagsProtReadWrite;
-        e = hipMemSetAccess(r.map, r.map_size, &ad, 1);
-        if (e != hipSuccess) (void)hipMemUnmap(r.map, r.map_size);
-    }
-    if (e != hipSuccess) { (void)hipMemRelease(r.handle); (void)hipMemAddressFree(r.va, r.va_size); return e; }
-    void *user = (char *)r.map + (r.map_size - (bytes + 15) / 16 * 16);   // the buffer's end is the mapping's end
-    g_guard[user] = r;
-    *p = user;
-    return hipSuccess;
-}
-
-// One device buffer and its owner: allocated by dev_alloc (so guard mode applies), freed by dev_free when the owner
-// is destroyed, re-assigned or reset().  Every device pointer of Plan, Level and Group is one of these, so erasing a
-// plan releases it.  NOT used for imc_obs (its token levels alias each other, and it checks the process id before it
-// frees), DictDev (its destructor runs at exit behind the same process-id check) and g_model (a static whose buffers
-// are released explicitly): those keep raw pointers.
-template <class T>
-class DevBuf {
-    T *p_ = nullptr;
-
-public:
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    hipError_t alloc(size_t bytes)
-    {
-        reset();
-        return dev_alloc((void **)&p_, bytes);
-    }
-    void reset()
-    {
-        dev_free(p_);
-        p_ = nullptr;
-    }
-    T *get() const { return p_; }
-    T *release()                  // the caller owns the buffer from now on (dev_free)
-    {
-        T *p = p_;
-        p_ = nullptr;
-        return p;
-    }
-    explicit operator bool() const { return p_ != nullptr; }
-};
-
-}  // namespace
-
-struct imc_obs {
-    uint64_t id = 0;
-    pid_t pid = 0;
-    int device = 0;
-    int nsym = 0;
-    size_t L = 0;
-    uint8_t *d_sym = nullptr;              // L raw symbols + zero padding (bytes, or 16-bit values when wide_raw)
-    bool wide_raw = false;                 // raw alphabet beyond 256 symbols
-    std::shared_ptr<DictDev> dict;         // null: not compressed
-    uint8_t *d_tok[imc::kNumLevels] = {};  // token streams per level (aliases allowed), null if none
-    bool owns[imc::kNumLevels] = {};       // ... in a buffer of the level's own: release_tokens() frees exactly these
-    bool wide[imc::kNumLevels] = {};       // ... holding 16-bit ids (alphabets beyond 256)
-    size_t ntok[imc::kNumLevels] = {};
-    int alphabet[imc::kNumLevels] = {};
-    std::vector<uint32_t> tok_count[imc::kNumLevels];   // byte levels: occurrences of every token id (hot-set choice of the hybrid table)
-};
-
-// An alignment whose sequences are resident on the device: all records' bases back to back in one buffer (not word
-// aligned), names and the record table on the host.
-struct imc_aln {
-    pid_t pid = 0;
-    int device = 0;
-    std::vector<std::string> names;
-    std::vector<uint64_t> start, length;   // of every record, in bytes of d_bases
-    uint8_t *d_bases = nullptr;            // the file's size rounded up to 16 (device parser) / the bases' (host reader)
-    uint64_t info[4] = {0, 0, 0, 0};       // imc_aln_info
-};
+#include "engine_core.hpp"
 
 namespace {
 
@@ -2886,351 +2645,8 @@ int run_state(const imc_obs *const *chunks, int n_chunks, bool op_mode, int B, i
 
 }  // namespace
 
-// =====================================================================================================
-// (pi, T) of a population on the device: host side of csrc/kernels_model.hpp (include/imcoal_model.h)
-// =====================================================================================================
-namespace {
-
-constexpr size_t MODEL_WORK_CAP = (size_t)256 << 20;   // bytes of work matrices per launch: larger populations go in rounds
-constexpr int MODEL_LDS_ORDER = 96;                    // the solve's M and R both fit LDS up to this padded order (2 x 72 KiB)
-
-// The three device buffers of the model path (uploads, work matrices, results): kept between calls, only ever grown.
-// Under IMC_GUARD=1 a buffer is re-made at exactly the size a launch needs, so that its end is the guard range's start.
-struct ModelBuf { void *p = nullptr; size_t cap = 0; };
-struct ModelDev { ModelBuf in, work, out; bool attr_set = false; } g_model;
-
-hipError_t model_reserve(ModelBuf &b, size_t bytes)
-{
-    bytes = round_up(std::max<size_t>(bytes, 16), 16);
-    if (g.opt.guard ? b.cap == bytes : b.cap >= bytes) return hipSuccess;
-    dev_free(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const hipError_t e = dev_alloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    return e;
-}
-
-struct ModelBlob {                                     // one upload: sections at 16-byte boundaries
-    std::vector<char> bytes;
-    template <class V> size_t put(const V *src, size_t count)
-    {
-        const size_t off = round_up(bytes.size(), 16);
-        bytes.resize(off + count * sizeof(V));
-        if (count) std::memcpy(bytes.data() + off, src, count * sizeof(V));
-        return off;
-    }
-};
-
-// Pade degree and squarings of one slot from the 1-norm of Q dt - the numbers imc_model::expm would see
-void model_plan_slot(ModelSlot &sl, const double *Qm)
-{
-    const int n = sl.n;
-    double best = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s += std::fabs(Qm[(size_t)i * n + j] * sl.dt);
-        best = std::max(best, s);
-    }
-    imc_model::expm_plan(best, sl.m, sl.s);
-    sl.scale = std::ldexp(1.0, -sl.s);
-}
-
-int model_launch_expm(const ModelSlot *d_slots, int n_slots, const double *d_Q, double *d_work, int *d_flags, int lds_np)
-{
-    if (!g_model.attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_model_expm, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    2 * MODEL_LDS_ORDER * MODEL_LDS_ORDER * 8));
-        g_model.attr_set = true;
-    }
-    const int lds_doubles = 2 * lds_np * lds_np;
-    hipLaunchKernelGGL(k_model_expm, dim3((unsigned)n_slots), dim3(MODEL_EXPM_THREADS), (size_t)lds_doubles * 8, g.stream, d_slots, d_Q,
-                       d_work, d_flags, lds_doubles);
-    HIP_TRY(hipGetLastError());
-    return IMC_OK;
-}
-
-// The argument checks of imc_model_transitions and imc_model_transitions_device (`fn` prefixes the messages): null
-// pointers, counts, piece and class indices; fills the offsets of the rate matrices inside one system's Q block.
-int model_check_args(const char *fn, int n_systems, int n_intervals, const int32_t *space_size, const int32_t *cls_off,
-                     const int32_t *cls_idx, const int32_t *piece_q, const int32_t *piece_proj, int n_q, const int32_t *q_size, int n_proj,
-                     const int32_t *proj_off, const double *proj, const double *Q, const double *dt, const double *start,
-                     const double *pi, const double *T, std::vector<int32_t> &q_off, int &stride)
-{
-    const std::string who = std::string(fn) + ": ";
-    if (n_systems < 0 || n_intervals < 1 || n_q < 1 || !space_size || !cls_off || !cls_idx || !q_size || !Q || !start || !pi || !T ||
-        (n_intervals > 1 && (!piece_q || !piece_proj || !dt)))
-        return fail(IMC_ERR_ARG, who + "bad arguments");
-    q_off.assign((size_t)n_q, 0);
-    stride = 0;
-    for (int k = 0; k < n_q; ++k) {
-        if (q_size[k] < 1) return fail(IMC_ERR_ARG, who + "rate matrix of order < 1");
-        q_off[k] = stride;
-        stride += q_size[k] * q_size[k];
-    }
-    for (int i = 0; i + 1 < n_intervals; ++i) {
-        if (piece_q[i] < 0 || piece_q[i] >= n_q || piece_proj[i] >= n_proj || (piece_proj[i] >= 0 && (!proj || !proj_off)))
-            return fail(IMC_ERR_ARG, who + "piece index out of range");
-    }
-    if (cls_off[0] < 0) return fail(IMC_ERR_ARG, who + "class offsets must not decrease");
-    for (int i = 0; i < n_intervals; ++i) {
-        for (int k = 0; k < 3; ++k)
-            if (cls_off[3 * i + k + 1] < cls_off[3 * i + k]) return fail(IMC_ERR_ARG, who + "class offsets must not decrease");
-        for (int k = cls_off[3 * i]; k < cls_off[3 * i + 3]; ++k)
-            if (cls_idx[k] < 0 || cls_idx[k] >= space_size[i]) return fail(IMC_ERR_ARG, who + "class index outside its state space");
-    }
-    return IMC_OK;
-}
-
-// On top of model_check_args: the limits of the device kernels, and the per-system checks that
-// imc_model::transitions_one makes on the way (same messages) - all of it before the first HIP call.
-int model_check_device_args(int n_systems, int n_intervals, const int32_t *space_size, const int32_t *cls_off, const int32_t *cls_idx,
-                            const int32_t *piece_q, const int32_t *piece_proj, int n_q, const int32_t *q_size, int n_proj,
-                            const int32_t *proj_off, const double *proj, const double *Q, const double *dt, const double *start,
-                            const double *pi, const double *T, std::vector<int32_t> &q_off, int &stride)
-{
-    const std::string who = "imc_model_transitions_device: ";
-    if (int rc = model_check_args("imc_model_transitions_device", n_systems, n_intervals, space_size, cls_off, cls_idx, piece_q, piece_proj,
-                                  n_q, q_size, n_proj, proj_off, proj, Q, dt, start, pi, T, q_off, stride))
-        return rc;
-    if (n_intervals > MODEL_MAX_INTERVALS) return fail(IMC_ERR_ARG, who + "more than " + std::to_string(MODEL_MAX_INTERVALS) + " intervals");
-    for (int k = 0; k < n_q; ++k)
-        if (q_size[k] > MODEL_MAX_ORDER)
-            return fail(IMC_ERR_ARG, who + "rate matrix of order " + std::to_string(q_size[k]) + " exceeds " + std::to_string(MODEL_MAX_ORDER));
-    for (int i = 0; i < n_intervals; ++i)
-        if (space_size[i] < 1 || space_size[i] > MODEL_MAX_ORDER)
-            return fail(IMC_ERR_ARG, who + "state space of order " + std::to_string(space_size[i]) + " outside [1," + std::to_string(MODEL_MAX_ORDER) + "]");
-    for (int i = 0; i + 1 < n_intervals; ++i)
-        if (piece_proj[i] >= 0 && proj_off[piece_proj[i]] < 0) return fail(IMC_ERR_ARG, who + "negative projection offset");
-    for (int k = 0; k < 3 * n_intervals; ++k)
-        if (cls_off[k + 1] - cls_off[k] > MODEL_MAX_ORDER) return fail(IMC_ERR_ARG, who + "a class lists more than " + std::to_string(MODEL_MAX_ORDER) + " states");
-    for (int i = 0; i + 1 < n_intervals; ++i) {
-        if (q_size[piece_q[i]] != space_size[i]) return fail(IMC_ERR_ARG, "a rate matrix does not match its interval's state space");
-        if (piece_proj[i] < 0 && space_size[i + 1] != space_size[i]) return fail(IMC_ERR_ARG, "state space changes without a projection");
-    }
-    if (n_intervals > 1)
-        for (int k = cls_off[2]; k < cls_off[3]; ++k)
-            if (cls_idx[k] >= space_size[1]) return fail(IMC_ERR_ARG, "an end-state index exceeds the next interval's state space");
-    const int s0 = space_size[0];
-    std::vector<char> inB((size_t)s0, 0);
-    for (int k = cls_off[0]; k < cls_off[1]; ++k) inB[cls_idx[k]] = 1;
-    for (int b = 0; b < n_systems; ++b)
-        for (int k = 0; k < s0; ++k)
-            if (!inB[k] && start[(size_t)b * s0 + k] != 0.0) return fail(IMC_ERR_ARG, "the start distribution must be supported on the B class");
-    return IMC_OK;
-}
-
-struct ModelSysPlan {                 // one system: its slots (distinct (rate matrix, dt)) and projected through matrices
-    std::vector<ModelSlot> slots;     // q_off: inside the system's Q block; w_off / r_off: set per round
-    std::vector<int> slot_q;          // which rate matrix
-    std::vector<std::pair<int, int>> jobs;   // (slot, projection)
-    std::vector<int> piece_slot, piece_job;  // per interval but the last; piece_job -1: the exponential itself
-    size_t work_doubles = 0;
-};
-
-int model_transitions_device(int n_systems, int n, const int32_t *space_size, const int32_t *cls_off, const int32_t *cls_idx,
-                             const int32_t *piece_q, const int32_t *piece_proj, const int32_t *q_size, const std::vector<int32_t> &q_off,
-                             int stride, const int32_t *proj_off, const double *proj, const double *Q, const double *dt,
-                             const double *start, double *pi, double *T)
-{
-    const int np1 = n - 1, s0 = space_size[0];
-    int max_l = 1;
-    for (int i = 0; i < n; ++i) max_l = std::max(max_l, (int)(cls_off[3 * i + 2] - cls_off[3 * i + 1]));
-    size_t proj_doubles = 0;
-    for (int i = 0; i < np1; ++i)
-        if (piece_proj[i] >= 0) proj_doubles = std::max(proj_doubles, (size_t)proj_off[piece_proj[i]] + (size_t)space_size[i] * space_size[i + 1]);
-    // ---- plan every system: slots de-duplicated on (rate matrix, dt) as transitions_one does, degree and squarings per slot ----
-    std::vector<ModelSysPlan> plans((size_t)n_systems);
-    for (int b = 0; b < n_systems; ++b) {
-        ModelSysPlan &sp = plans[b];
-        const double *dtb = dt + (size_t)b * np1;
-        sp.piece_slot.assign((size_t)np1, -1);
-        sp.piece_job.assign((size_t)np1, -1);
-        for (int i = 0; i < np1; ++i) {
-            int k = -1;
-            for (size_t c = 0; c < sp.slots.size() && k < 0; ++c)
-                if (sp.slot_q[c] == piece_q[i] && sp.slots[c].dt == dtb[i]) k = (int)c;
-            if (k < 0) {
-                ModelSlot sl{};
-                sl.n = q_size[piece_q[i]];
-                sl.np = (sl.n + 15) / 16 * 16;
-                sl.dt = dtb[i];
-                sl.q_off = q_off[piece_q[i]];
-                model_plan_slot(sl, Q + (size_t)b * stride + q_off[piece_q[i]]);
-                k = (int)sp.slots.size();
-                sp.slots.push_back(sl);
-                sp.slot_q.push_back(piece_q[i]);
-                sp.work_doubles += (size_t)MODEL_MATS * sl.np * sl.np;
-            }
-            sp.piece_slot[i] = k;
-            if (piece_proj[i] >= 0) {
-                int j = -1;
-                for (size_t c = 0; c < sp.jobs.size() && j < 0; ++c)
-                    if (sp.jobs[c].first == k && sp.jobs[c].second == piece_proj[i]) j = (int)c;
-                if (j < 0) {
-                    j = (int)sp.jobs.size();
-                    sp.jobs.emplace_back(k, piece_proj[i]);
-                    sp.work_doubles += (size_t)space_size[i] * space_size[i + 1];
-                }
-                sp.piece_job[i] = j;
-            }
-        }
-        sp.work_doubles += (size_t)2 * np1 * max_l;
-    }
-    HIP_TRY(hipSetDevice(g.device));
-    for (int b0 = 0; b0 < n_systems;) {
-        // ---- one round: as many systems as the work cap takes (at least one) ----
-        int b1 = b0;
-        size_t work_doubles = 0;
-        while (b1 < n_systems && (b1 == b0 || (work_doubles + plans[b1].work_doubles) * 8 <= MODEL_WORK_CAP)) work_doubles += plans[b1++].work_doubles;
-        const int ns = b1 - b0;
-        std::vector<ModelSlot> slots;
-        std::vector<ModelProjJob> jobs;
-        std::vector<int> job_off((size_t)ns + 1, 0), thr_ld((size_t)ns * np1 + 1, 0);
-        std::vector<long long> thr_off((size_t)ns * np1 + 1, 0);
-        long long off = 0;
-        int lds_np = 0;
-        for (int b = b0; b < b1; ++b) {
-            const ModelSysPlan &sp = plans[b];
-            const size_t first_slot = slots.size(), first_job = jobs.size();
-            for (ModelSlot sl : sp.slots) {
-                sl.q_off += (long long)(b - b0) * stride;
-                sl.w_off = off;
-                sl.r_off = off + (long long)((sl.s & 1) ? MODEL_MAT_TM : MODEL_MAT_OUT) * sl.np * sl.np;
-                off += (long long)MODEL_MATS * sl.np * sl.np;
-                if (sl.np <= MODEL_LDS_ORDER) lds_np = std::max(lds_np, sl.np);
-                slots.push_back(sl);
-            }
-            std::vector<int> job_cols(sp.jobs.size(), 0);
-            for (int i = 0; i < np1; ++i) {
-                const ModelSlot &sl = slots[first_slot + sp.piece_slot[i]];
-                const int j = sp.piece_job[i];
-                if (j >= 0 && first_job + j >= jobs.size()) {       // (jobs were numbered in order of first use)
-                    ModelProjJob jd{};
-                    jd.src_off = sl.r_off;
-                    jd.src_ld = sl.np;
-                    jd.rows = space_size[i];
-                    jd.cols = space_size[i + 1];
-                    jd.proj_off = proj_off[piece_proj[i]];
-                    jd.dst_off = off;
-                    off += (long long)jd.rows * jd.cols;
-                    jobs.push_back(jd);
-                }
-                thr_off[(size_t)(b - b0) * np1 + i] = j < 0 ? sl.r_off : jobs[first_job + j].dst_off;
-                thr_ld[(size_t)(b - b0) * np1 + i] = j < 0 ? sl.np : jobs[first_job + j].cols;
-            }
-            job_off[(size_t)(b - b0) + 1] = (int)jobs.size();
-        }
-        const long long v_off = off;
-        off += (long long)ns * 2 * np1 * max_l;
-        const int n_slots = (int)slots.size();
-        // ---- upload ----
-        ModelBlob blob;
-        const size_t o_space = blob.put(space_size, (size_t)n), o_coff = blob.put(cls_off, (size_t)3 * n + 1),
-                     o_cidx = blob.put(cls_idx, (size_t)cls_off[3 * n]), o_proj = blob.put(proj, proj_doubles),
-                     o_start = blob.put(start + (size_t)b0 * s0, (size_t)ns * s0), o_slots = blob.put(slots.data(), slots.size()),
-                     o_toff = blob.put(thr_off.data(), thr_off.size()), o_tld = blob.put(thr_ld.data(), thr_ld.size()),
-                     o_jobs = blob.put(jobs.data(), jobs.size()), o_joff = blob.put(job_off.data(), job_off.size());
-        const size_t o_Q = round_up(blob.bytes.size(), 16), q_bytes = (size_t)ns * stride * 8;
-        const size_t o_pi = round_up((size_t)ns * n * n * 8, 16), o_total = round_up(o_pi + (size_t)ns * n * 8, 16),
-                     o_flags = round_up(o_total + (size_t)ns * 8, 16), out_bytes = o_flags + (size_t)std::max(n_slots, 1) * 4;
-        HIP_TRY(model_reserve(g_model.in, o_Q + q_bytes));
-        HIP_TRY(model_reserve(g_model.work, (size_t)std::max<long long>(off, 2) * 8));
-        HIP_TRY(model_reserve(g_model.out, out_bytes));
-        char *d_in = (char *)g_model.in.p, *d_out = (char *)g_model.out.p;
-        double *d_work = (double *)g_model.work.p;
-        HIP_TRY(hipMemcpyAsync(d_in, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync(d_in + o_Q, Q + (size_t)b0 * stride, q_bytes, hipMemcpyHostToDevice, g.stream));
-        // ---- exponentials (one workgroup per slot), then projection + recursion (one workgroup per system) ----
-        if (n_slots > 0)
-            if (int rc = model_launch_expm((const ModelSlot *)(d_in + o_slots), n_slots, (const double *)(d_in + o_Q), d_work,
-                                           (int *)(d_out + o_flags), lds_np))
-                return rc;
-        ModelJointArgs ja{};
-        ja.n = n; ja.s0 = s0; ja.max_l = max_l;
-        ja.space_size = (const int *)(d_in + o_space); ja.cls_off = (const int *)(d_in + o_coff); ja.cls_idx = (const int *)(d_in + o_cidx);
-        ja.proj = (const double *)(d_in + o_proj); ja.start = (const double *)(d_in + o_start);
-        ja.thr_off = (const long long *)(d_in + o_toff); ja.thr_ld = (const int *)(d_in + o_tld);
-        ja.jobs = (const ModelProjJob *)(d_in + o_jobs); ja.job_off = (const int *)(d_in + o_joff);
-        ja.work = d_work; ja.v_off = v_off;
-        ja.T = (double *)d_out; ja.pi = (double *)(d_out + o_pi); ja.total = (double *)(d_out + o_total);
-        hipLaunchKernelGGL(k_model_joint, dim3((unsigned)ns), dim3(MODEL_JOINT_THREADS), 0, g.stream, ja);
-        HIP_TRY(hipGetLastError());
-        // ---- results ----
-        std::vector<double> totals((size_t)ns);
-        std::vector<int> flags((size_t)std::max(n_slots, 1), 0);
-        HIP_TRY(hipMemcpyAsync(T + (size_t)b0 * n * n, d_out, (size_t)ns * n * n * 8, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(pi + (size_t)b0 * n, d_out + o_pi, (size_t)ns * n * 8, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(totals.data(), d_out + o_total, (size_t)ns * 8, hipMemcpyDeviceToHost, g.stream));
-        if (n_slots > 0) HIP_TRY(hipMemcpyAsync(flags.data(), d_out + o_flags, (size_t)n_slots * 4, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        for (int f : flags)
-            if (f) return fail(IMC_ERR_ARG, "expm: singular Pade denominator");
-        for (int b = 0; b < ns; ++b)
-            if (!(std::fabs(totals[b] - 1.0) < 1.5e-7))            // transitions.py:237, as imc_model::transitions_one
-                return fail(IMC_ERR_ARG, "joint probabilities sum to " + std::to_string(totals[b]) + ", not 1 (system " + std::to_string(b0 + b) + ")");
-        b0 = b1;
-    }
-    return IMC_OK;
-}
-
-int model_expm_batch_device(int n, int count, const double *A, double *out)
-{
-    const int np = (n + 15) / 16 * 16;
-    const size_t nn = (size_t)n * n, slot_doubles = (size_t)MODEL_MATS * np * np;
-    const int per_round = (int)std::max<size_t>(1, MODEL_WORK_CAP / 8 / slot_doubles);
-    HIP_TRY(hipSetDevice(g.device));
-    for (int r0 = 0; r0 < count; r0 += per_round) {
-        const int nr = std::min(per_round, count - r0);
-        std::vector<ModelSlot> slots((size_t)nr);
-        for (int k = 0; k < nr; ++k) {
-            ModelSlot &sl = slots[k];
-            sl = ModelSlot{};
-            sl.n = n;
-            sl.np = np;
-            sl.dt = 1.0;
-            sl.q_off = (long long)k * nn;
-            model_plan_slot(sl, A + (size_t)(r0 + k) * nn);
-            sl.w_off = (long long)k * slot_doubles;
-            sl.r_off = sl.w_off + (long long)((sl.s & 1) ? MODEL_MAT_TM : MODEL_MAT_OUT) * np * np;
-        }
-        ModelBlob blob;
-        const size_t o_slots = blob.put(slots.data(), slots.size());
-        const size_t o_Q = round_up(blob.bytes.size(), 16), q_bytes = (size_t)nr * nn * 8;
-        const size_t o_flags = round_up(q_bytes, 16), out_bytes = o_flags + (size_t)nr * 4;
-        HIP_TRY(model_reserve(g_model.in, o_Q + q_bytes));
-        HIP_TRY(model_reserve(g_model.work, (size_t)nr * slot_doubles * 8));
-        HIP_TRY(model_reserve(g_model.out, out_bytes));
-        char *d_in = (char *)g_model.in.p, *d_out = (char *)g_model.out.p;
-        HIP_TRY(hipMemcpyAsync(d_in, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync(d_in + o_Q, A + (size_t)r0 * nn, q_bytes, hipMemcpyHostToDevice, g.stream));
-        if (int rc = model_launch_expm((const ModelSlot *)(d_in + o_slots), nr, (const double *)(d_in + o_Q), (double *)g_model.work.p,
-                                       (int *)(d_out + o_flags), np <= MODEL_LDS_ORDER ? np : 0))
-            return rc;
-        hipLaunchKernelGGL(k_model_unpad, dim3((unsigned)nr), dim3(256), 0, g.stream, (const ModelSlot *)(d_in + o_slots),
-                           (const double *)g_model.work.p, (double *)d_out);
-        HIP_TRY(hipGetLastError());
-        std::vector<int> flags((size_t)nr, 0);
-        HIP_TRY(hipMemcpyAsync(out + (size_t)r0 * nn, d_out, q_bytes, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(flags.data(), d_out + o_flags, (size_t)nr * 4, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        for (int k = 0; k < nr; ++k)
-            if (flags[k]) return fail(IMC_ERR_ARG, "imc_model_expm_batch_device: singular Pade denominator (matrix " + std::to_string(r0 + k) + ")");
-    }
-    return IMC_OK;
-}
-
-void model_release()
-{
-    for (ModelBuf *b : {&g_model.in, &g_model.work, &g_model.out}) {
-        dev_free(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    g_model.attr_set = false;
-}
-
-}  // namespace
+#include "engine_model.hpp"
+#include "engine_sample.hpp"
 
 // =====================================================================================================
 // C ABI
@@ -3848,121 +3264,6 @@ int imc_model_expm_batch_device(int n, int count, const double *A, double *out)
 }
 
 }  // extern "C"
-
-// ---- sampling from an HMM (include/imcoal_sample.h; csrc/sample_tiles.hpp is the specification) -------------------------
-namespace {
-
-uint64_t g_last_sampling[4] = {0, 0, 0, 0};   // imc_last_sampling: path, tiles, tile length, columns (g_mu held)
-
-constexpr int SAMPLE_TILE_DEFAULT = 512;      // (profiles/device_sampling_ab.txt: the sweep over 64 .. 4096)
-
-// every check both entry points share, before any HIP call; builds the threshold tables
-int sample_check(const char *who, int N, int S, int emit, const double *pi, const double *T, const double *E, int R, size_t L,
-                 const void *sym_out, int sym_bytes, imc::SampleTables *tb)
-{
-    const std::string w = std::string(who) + ": ";
-    if (N < 1 || N > imc::kSampleMaxStates) return fail(IMC_ERR_ARG, w + "N must be in [1," + std::to_string(imc::kSampleMaxStates) + "]");
-    if (S < 1 || S > imc::kSampleMaxSymbols) return fail(IMC_ERR_ARG, w + "S must be in [1," + std::to_string(imc::kSampleMaxSymbols) + "]");
-    if (emit < 1 || emit > S) return fail(IMC_ERR_ARG, w + "emit_symbols must be in [1,S]");
-    if (sym_bytes != 1 && sym_bytes != 2) return fail(IMC_ERR_ARG, w + "sym_bytes must be 1 or 2");
-    if (sym_bytes == 1 && emit > 256) return fail(IMC_ERR_ARG, w + "byte symbols cannot carry more than 256 symbols");
-    if (L < 1 || L >= (size_t)1 << 31) return fail(IMC_ERR_ARG, w + "L must be in [1,2^31)");
-    if (R < 1 || R > imc::kSampleMaxReplicates) return fail(IMC_ERR_ARG, w + "n_replicates must be in [1," + std::to_string(imc::kSampleMaxReplicates) + "]");
-    if (!pi || !T || !E) return fail(IMC_ERR_ARG, w + "pi, T or E is null");
-    if (!sym_out) return fail(IMC_ERR_ARG, w + "the symbol output is null");
-    if (sym_bytes == 2 && (reinterpret_cast<uintptr_t>(sym_out) & 1)) return fail(IMC_ERR_ARG, w + "16-bit symbol output is not 2-byte aligned");
-    std::string err;
-    if (!imc::build_tables(N, S, emit, pi, T, E, tb, &err)) return fail(IMC_ERR_ARG, w + err);
-    return IMC_OK;
-}
-
-// `what` must be device memory of the library's device, `bytes` long: an error, never a fault (g_mu held, context ready)
-int check_device_output(const void *p, size_t bytes, const char *what)
-{
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(IMC_ERR_ARG, std::string(what) + " is not device memory (hipPointerGetAttributes)");
-    }
-    if (at.type != hipMemoryTypeDevice) return fail(IMC_ERR_ARG, std::string(what) + " is not device memory");
-    if (at.device != g.device) return fail(IMC_ERR_ARG, std::string(what) + " is memory of device " + std::to_string(at.device) + ", the library runs on device " + std::to_string(g.device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
-        if ((const char *)p + bytes > (const char *)base + size) return fail(IMC_ERR_ARG, std::string(what) + ": the allocation ends before n_replicates x L elements");
-    } else (void)hipGetLastError();
-    return IMC_OK;
-}
-
-// The three launches on `st` (g_mu held, context ready, outputs checked); returns after synchronising st.
-int sample_on_device(const imc::SampleTables &tb, uint64_t seed, uint32_t tag, uint64_t L, uint64_t total, uint32_t tile, uint32_t ntiles,
-                     void *d_sym, int sym_bytes, uint8_t *d_states, hipStream_t st)
-{
-    const int N = tb.N, emit = tb.emit;
-    const char *lds_env = std::getenv("IMC_SAMPLE_LDS");            // 0: every table read from global memory (A/B measurements)
-    const bool lds_allowed = !(lds_env && std::atoi(lds_env) == 0);
-    const size_t trans_bytes = tb.transition_doubles() * sizeof(double), all_bytes = tb.cdf.size() * sizeof(double);
-    const bool summary_lds = lds_allowed && trans_bytes <= LDS_BUDGET;
-    const bool emit_lds = lds_allowed && all_bytes <= SMP_EMIT_TABLE_LDS;
-
-    DevBuf<double> d_tab;
-    DevBuf<uint8_t> d_summ, d_enter;
-    HIP_TRY(d_tab.alloc(all_bytes));
-    HIP_TRY(d_summ.alloc((size_t)ntiles * N));
-    HIP_TRY(d_enter.alloc(ntiles));
-    HIP_TRY(hipMemcpyAsync(d_tab.get(), tb.cdf.data(), all_bytes, hipMemcpyHostToDevice, st));
-    const SmpArgs a{d_tab.get(), N, emit, seed, tag, L, total, tile, ntiles};
-
-    const bool timed = PhaseTimer::enabled();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto stamp = [&](int k) { if (timed && ev[k]) (void)hipEventRecord(ev[k], st); };
-    if (timed)
-        for (auto &e : ev) (void)hipEventCreate(&e);
-
-    // summary: floor(64 / N) tiles per wavefront up to 64 states, ceil(N / 64) wavefronts per tile beyond
-    const int sum_threads = summary_lds && trans_bytes >= SMP_SUMMARY_WIDE_FROM ? SMP_SUMMARY_WIDE_THREADS : SMP_THREADS;
-    const uint64_t waves = N <= 64 ? ((uint64_t)ntiles + 64 / N - 1) / (64 / N) : (uint64_t)ntiles * ((N + 63) / 64);
-    const uint64_t sum_blocks = (waves + sum_threads / 64 - 1) / (sum_threads / 64);
-    if (sum_blocks >= (uint64_t)1 << 31) return fail(IMC_ERR_ARG, "imc_sample_device: too many tiles for one launch");
-    stamp(0);
-    if (summary_lds) {
-        if (trans_bytes > 48 * 1024)
-            if (int rc = allow_lds_budget(k_smp_summary<true>)) return rc;
-        hipLaunchKernelGGL(k_smp_summary<true>, dim3((uint32_t)sum_blocks), dim3(sum_threads), trans_bytes, st, a, d_summ.get());
-    } else
-        hipLaunchKernelGGL(k_smp_summary<false>, dim3((uint32_t)sum_blocks), dim3(sum_threads), 0, st, a, d_summ.get());
-    HIP_TRY(hipGetLastError());
-    stamp(1);
-    const int scan_threads = smp_scan_threads(N);
-    hipLaunchKernelGGL(k_smp_scan, dim3(1), dim3(scan_threads), (size_t)2 * scan_threads * N, st, d_summ.get(), ntiles, N, d_enter.get());
-    HIP_TRY(hipGetLastError());
-    stamp(2);
-    const dim3 emit_grid((ntiles + SMP_THREADS - 1) / SMP_THREADS);
-    const size_t emit_lds_bytes = (emit_lds ? (all_bytes + 15) & ~(size_t)15 : 0) + smp_emit_stage_bytes(sym_bytes);
-    if (sym_bytes == 1) {
-        if (emit_lds) hipLaunchKernelGGL((k_smp_emit<true, uint8_t>), emit_grid, dim3(SMP_THREADS), emit_lds_bytes, st, a, d_enter.get(), (uint8_t *)d_sym, d_states);
-        else hipLaunchKernelGGL((k_smp_emit<false, uint8_t>), emit_grid, dim3(SMP_THREADS), emit_lds_bytes, st, a, d_enter.get(), (uint8_t *)d_sym, d_states);
-    } else {
-        if (emit_lds) hipLaunchKernelGGL((k_smp_emit<true, uint16_t>), emit_grid, dim3(SMP_THREADS), emit_lds_bytes, st, a, d_enter.get(), (uint16_t *)d_sym, d_states);
-        else hipLaunchKernelGGL((k_smp_emit<false, uint16_t>), emit_grid, dim3(SMP_THREADS), emit_lds_bytes, st, a, d_enter.get(), (uint16_t *)d_sym, d_states);
-    }
-    HIP_TRY(hipGetLastError());
-    stamp(3);
-    HIP_TRY(hipStreamSynchronize(st));     // the temporaries are freed on return
-    if (timed) {
-        float ms[3] = {0.f, 0.f, 0.f};
-        for (int k = 0; k < 3; ++k)
-            if (ev[k] && ev[k + 1]) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-        std::fprintf(stderr, "[imc sample] %llu columns, %d states, tile %u (%u tiles): summary %.3f ms (%s table), scan %.3f ms, emit %.3f ms (%s tables)\n",
-                     (unsigned long long)total, N, tile, ntiles, ms[0], summary_lds ? "LDS" : "global", ms[1], ms[2], emit_lds ? "LDS" : "global");
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    return IMC_OK;
-}
-
-}  // namespace
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 // options_host.hpp - the engine's run-time options in one place: the record (imc::Options, every knob with its
 // default), the table of environment variables (imc::kOptionVars: name, field, how the text becomes a value, when it is
 // read) and the one comparison that says whether a cached plan may be replayed (imc::same_plan_options).  Host only, no
-// HIP: planner_host.hpp derives PlanOptions from the record, imcoal_fwd.hip keeps the live record in its context, a Plan
+// HIP: planner_host.hpp derives PlanOptions from the record, engine_core.hpp keeps the live record in its context, a Plan
 // keeps the one it was built under, and tests/options_host_check.cpp checks all of it on the CPU under ASan/UBSan.
 // Needs no other header of the engine.
 #pragma once

@@ -8,8 +8,6 @@ in tests/test_gpu_alignment.py."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -17,6 +15,7 @@ import pytest
 import imcoalhmm_amd
 from imcoalhmm_amd import Alignment, Forwarder, _capi, build, prepare
 from test_encode_tiles_cpu import run_check_under_asan_ubsan
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -205,22 +204,7 @@ def test_alignment_kernels_use_no_scratch():
     src = ('#include <hip/hip_runtime.h>\n#include "kernels_align.hpp"\n'
            'template __global__ void k_aln_columns<2>(const uint8_t *, uint64_t, uint64_t, uint64_t, uint32_t, uint8_t *);\n'
            'template __global__ void k_aln_columns<3>(const uint8_t *, uint64_t, uint64_t, uint64_t, uint32_t, uint8_t *);\n')
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "align_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_aln_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_aln_")
     kernels = ("k_aln_summary", "k_aln_scan", "k_aln_scatter", "k_aln_columnsILi2E", "k_aln_columnsILi3E")
     for k in kernels:
         assert any(re.match(r"_Z\d+%s[A-Z]" % k, n) for n in seen), (k, sorted(seen))

@@ -32,3 +32,18 @@ def test_every_reachable_include_is_a_dep():
             assert os.path.exists(target), "%s includes %s, which does not exist" % (path, name)
             todo.append(target)
     assert len(seen) > 30 and any(p.endswith("options_host.hpp") for p in seen) and any(p.endswith("kernels_zip4.hpp") for p in seen)
+
+
+def test_engine_headers_are_host_parts_of_the_one_translation_unit():
+    """Every engine_*.hpp is included from imcoal_fwd.hip exactly once and from nowhere else, and holds neither a kernel
+    (those live in kernels_*.hpp) nor a piece of the C ABI (that is imcoal_fwd.hip's)."""
+    csrc = os.path.join(build.PKG, "csrc")
+    engine = sorted(f for f in os.listdir(csrc) if f.startswith("engine_") and f.endswith(".hpp"))
+    assert engine
+    includes = {os.path.basename(f): INCLUDE.findall(open(f).read()) for f in build.DEPS}
+    for name in engine:
+        assert includes["imcoal_fwd.hip"].count(name) == 1, name
+        others = [f for f, inc in includes.items() if f != "imcoal_fwd.hip" and any(os.path.basename(i) == name for i in inc)]
+        assert not others, (name, others)
+        text = open(os.path.join(csrc, name)).read()
+        assert 'extern "C"' not in text and "__global__" not in text, name

@@ -5,13 +5,12 @@ register budget.  The tokens are compared with the host encoder's on the device 
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from imcoalhmm_amd import Forwarder, _capi, build, hmm
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -99,22 +98,7 @@ def test_from_device_refuses_what_it_cannot_take(lib, arr):
 
 def test_encoder_kernels_use_no_scratch():
     src = '#include <hip/hip_runtime.h>\n#include "kernels_encode.hpp"\n'
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "encode_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_enc_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_enc_")
     kernels = ("k_enc_summary", "k_enc_scan", "k_enc_scatter", "k_enc_mark_summary", "k_enc_mark_scatter", "k_enc_snapshot",
                "k_enc_histogram", "k_enc_load", "k_enc_validate", "k_enc_narrow")
     for k in kernels:

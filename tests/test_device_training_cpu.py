@@ -6,12 +6,11 @@ tests/test_gpu_device_training.py (the kernels)."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
 from imcoalhmm_amd import _capi, build, hmm
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -62,22 +61,7 @@ def test_trainer_kernels_use_no_scratch():
     src = ('#include <hip/hip_runtime.h>\n#include "kernels_train.hpp"\n'
            'template __global__ void k_trn_pair_hist<true>(const uint16_t *, uint32_t, uint32_t, uint32_t *);\n'
            'template __global__ void k_trn_pair_hist<false>(const uint16_t *, uint32_t, uint32_t, uint32_t *);\n')
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "train_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_trn_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_trn_")
     kernels = ("k_trn_load", "k_trn_pair_histILb1E", "k_trn_pair_histILb0E", "k_trn_argmax", "k_trn_pair_count", "k_trn_candidates")
     for k in kernels:
         assert any(re.match(r"_Z\d+%s[A-Z]" % k, n) for n in seen), (k, sorted(seen))

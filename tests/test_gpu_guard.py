@@ -5,7 +5,7 @@ been switched back on, died with "Memory access fault by GPU".  The working tree
 five minutes shows a half-edited summation, gpurun_out/full_2.log), so the faulting access cannot be replayed.  What
 CAN be done is to make any access of that class impossible to miss: with IMC_GUARD=1 every device buffer of the
 library is its own virtual-memory mapping whose end is flush against unmapped address space (dev_alloc in
-csrc/imcoal_fwd.hip), so a kernel that touches even one vector load past the declared end of a buffer faults every
+csrc/engine_core.hpp), so a kernel that touches even one vector load past the declared end of a buffer faults every
 time, not only when the allocator happens to leave a hole behind it (which is what freeing the 100 MB chunk did).
 
 This test replays that create / evaluate / free / compression-flip / create sequence - and one pass over every

@@ -171,7 +171,7 @@ def test_results_do_not_depend_on_the_call():
     # 257 systems: more work matrices than one launch's workspace takes, so the last system runs in a later round
     many = take(case, [1 + k % 8 for k in range(256)] + [0])
     # (precondition: nine padded work matrices per distinct (rate matrix, dt) of every system, against the 256 MiB a launch
-    #  may take - MODEL_WORK_CAP in csrc/imcoal_fwd.hip - so that systems are read and written at a non-zero round offset)
+    #  may take - MODEL_WORK_CAP in csrc/engine_model.hpp - so that systems are read and written at a non-zero round offset)
     padded = [16 * ((int(q) + 15) // 16) for q in case["q_size"]]
     work_bytes = sum(9 * 8 * padded[q] ** 2 for b in range(257)
                      for q, _ in {(int(q), float(d)) for q, d in zip(case["piece_q"], many["dt"][b])})

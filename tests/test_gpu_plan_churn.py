@@ -1,4 +1,4 @@
-"""A plan owns its device memory (DevBuf in csrc/imcoal_fwd.hip): erasing it from the plan list - eviction of the least
+"""A plan owns its device memory (DevBuf in csrc/engine_core.hpp): erasing it from the plan list - eviction of the least
 recently used plan, the chunk filters of imc_obs_free and imc_obs_recompress - gives back every buffer it allocated.
 Pinned here with something other than the code under test: the device's own free-memory figure, read through torch.
 

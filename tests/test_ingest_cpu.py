@@ -7,13 +7,12 @@ compared with the host parser's on the device in tests/test_gpu_device_ingest.py
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
 from imcoalhmm_amd import Forwarder, _capi, build, hmm, prepare
 from test_encode_tiles_cpu import run_check_under_asan_ubsan
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -130,22 +129,7 @@ def test_errors_that_need_no_device_are_the_same_in_both_modes(lib, tmp_path, mo
 
 def test_ingest_kernels_use_no_scratch():
     src = '#include <hip/hip_runtime.h>\n#include "kernels_ingest.hpp"\n'
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "ingest_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_ing_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_ing_")
     kernels = ("k_ing_text_summary", "k_ing_scan", "k_ing_text_scatter", "k_ing_unpack2", "k_ing_pairwise")
     for k in kernels:
         assert any(re.match(r"_Z\d+%s[A-Z]" % k, n) for n in seen), (k, sorted(seen))

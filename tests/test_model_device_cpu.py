@@ -4,15 +4,14 @@ silent numpy fallback of models.py, the host path's bits after its degree choice
 the kernels' register budget.  The arithmetic is checked on the device in tests/test_gpu_model_device.py."""
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from imcoalhmm_amd import _capi, build
+from imcoalhmm_amd import _capi
 from imcoalhmm_amd import models as M
 from model_device_cases import _dp, call_transitions, one_space_case
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -118,21 +117,6 @@ def test_host_expm_is_unchanged_bit_for_bit():
 
 def test_model_kernels_do_not_spill():
     src = '#include <hip/hip_runtime.h>\n#include "kernels_model.hpp"\n'
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "model_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(REPO, "imcoalhmm_amd", "csrc"), "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_model_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_model_")
     assert len(seen) >= 3, seen                               # k_model_expm, k_model_joint, k_model_unpad
     assert all(v == 0 for v in seen.values()), seen

@@ -8,12 +8,12 @@ import ctypes
 import os
 import re
 import subprocess
-import tempfile
 
 import pytest
 
 from imcoalhmm_amd import Alignment, _capi, build, prepare
 from test_encode_tiles_cpu import run_check_under_asan_ubsan
+from kernel_scratch_cases import scratch_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -188,22 +188,7 @@ def test_phylip_headers_hold_no_device_code_of_their_own():
 
 def test_phylip_kernels_use_no_scratch():
     src = '#include <hip/hip_runtime.h>\n#include "kernels_phylip.hpp"\n'
-    with tempfile.TemporaryDirectory() as tmp:
-        tu = os.path.join(tmp, "phylip_kernels.hip")
-        with open(tu, "w") as fh:
-            fh.write(src)
-        cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-               "-Rpass-analysis=kernel-resource-usage", "-I", CSRC, "-o", os.path.join(tmp, "k.o"), tu]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and re.match(r"_Z\d+k_phy_", name):
-            seen[name] = int(m.group(1))
+    seen = scratch_bytes(src, "k_phy_")
     kernels = ("k_phy_summary", "k_phy_scan", "k_phy_count", "k_phy_partial", "k_phy_offsets", "k_phy_scatter")
     for k in kernels:
         assert any(re.match(r"_Z\d+%s[A-Z]" % k, n) for n in seen), (k, sorted(seen))
