@@ -114,6 +114,182 @@ __device__ __forceinline__ void zip3_rescale(double (&P)[NT][NT], int &ex)
     ex += e;
 }
 
+// ---- what the blocked kernels share: this file's scan and table build, kernels_zip4.hpp's scan and table kernels ------
+// Lane l = 16 q + 4 bq + r of a wavefront: MFMA block bq, element (4K + q, 4J + r) of every tile (K, J) of that block's
+// operator; lo / lx: the lane's offsets into a table entry's tile-row (zip3_load_row).
+struct Zip3Lane { int q, bq, r, lo, lx; };
+template <int NT>
+__device__ __forceinline__ Zip3Lane zip3_lane(int lane)
+{
+    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
+    return {q, bq, r, (q * 4 + r) * Zip3Geom<NT>::NTE, q * 4 + r};
+}
+
+// The lane's fragment F (the layout of an MFMA B operand and result) <-> a table entry X of TOK doubles (LDS or global).
+// AGENT: relaxed agent-scope atomics, for entries that workgroups hand to each other (zip3_tail).
+template <int NT, bool AGENT = false>
+__device__ __forceinline__ void zip3_frag_load(double (&F)[NT][NT], const double *X, const Zip3Lane &ln)
+{
+    using Geo = Zip3Geom<NT>;
+#pragma unroll
+    for (int K = 0; K < NT; ++K)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            const double *p = &X[Geo::idx(4 * K + ln.q, 4 * J + ln.r)];
+            if constexpr (AGENT) F[K][J] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else F[K][J] = *p;
+        }
+}
+template <int NT, bool AGENT = false>
+__device__ __forceinline__ void zip3_frag_store(double *X, const double (&F)[NT][NT], const Zip3Lane &ln)
+{
+    using Geo = Zip3Geom<NT>;
+#pragma unroll
+    for (int K = 0; K < NT; ++K)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            double *p = &X[Geo::idx(4 * K + ln.q, 4 * J + ln.r)];
+            if constexpr (AGENT) __hip_atomic_store(p, F[K][J], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else *p = F[K][J];
+        }
+}
+
+// Entry (i, j) of a raw symbol's operator, C_s[i][j] = E[s][i] * T[j][i], or of the identity.  The parameters are read
+// either way (symbol 0's for the identity) and the result selected: `s` may differ from lane to lane.
+__device__ __forceinline__ double raw_operator(const double *Etg, const double *Tp, int PP, int s, int i, int j, bool is_identity)
+{
+    const double v = Etg[(size_t)(is_identity ? 0 : s) * PP + i] * Tp[(size_t)j * PP + i];
+    return is_identity ? (i == j ? 1.0 : 0.0) : v;
+}
+
+// A parameter set from the caller's mapped staging slot (host memory, ~2 us per round trip) into LDS: IN_FLIGHT 16-byte
+// loads per lane in flight together, then the stores.  pstride is even; the caller puts a barrier behind it.
+template <int IN_FLIGHT, int THREADS>
+__device__ __forceinline__ void stage_params_to_lds(double *lp, const double *src, int pstride, int tid)
+{
+    for (int k0 = 0; k0 < pstride; k0 += IN_FLIGHT * 2 * THREADS) {
+        double2 v[IN_FLIGHT];
+#pragma unroll
+        for (int u = 0; u < IN_FLIGHT; ++u) {
+            const int k = k0 + (u * THREADS + tid) * 2;
+            v[u] = k < pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < IN_FLIGHT; ++u) {
+            const int k = k0 + (u * THREADS + tid) * 2;
+            if (k < pstride) *reinterpret_cast<double2 *>(lp + k) = v[u];
+        }
+    }
+}
+
+// Token loads of the scans are GLOBAL loads: through the segment descriptor's generic pointer they are flat loads, which
+// count against the LDS counter too and can return out of order with the operand refills - every wait behind one
+// becomes a full one.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) uint8_t *gptr;
+typedef const __attribute__((address_space(1))) u32x4 *gptr4;
+typedef const __attribute__((address_space(1))) uint32_t *gptr1;
+
+// The segment of one MFMA block of a scan workgroup: slot = 4 * wavefront + block, 0 .. SLOTS - 1.
+struct Zip3Segment {
+    bool valid, first;      // the slot has a segment; it is its chunk's first (starts from pi . E, ends as a vector)
+    int len;                // tokens (0 for an idle slot)
+    int tok0;               // a first segment's token 0: it goes into the start vector
+    gptr tokg;              // the token stream
+    int maxlen, nfull;      // over the wavefront: the longest segment; the blocks of RESCALE_EVERY tokens that every valid segment has
+};
+
+// The operator a segment starts from: pi . E[tok0] in column 0 for a chunk's first segment, the identity elsewhere
+// (N x N of the NP x NP), zero for an idle slot.
+template <int NT>
+__device__ __forceinline__ void zip3_start(double (&P)[NT][NT], const BigArgs &a, const Zip3Segment &sg, const Zip3Lane &ln,
+                                           const double *pi_p, const double *Etg)
+{
+#pragma unroll
+    for (int K = 0; K < NT; ++K)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            const int i = 4 * K + ln.q, c = 4 * J + ln.r;
+            double v;
+            if (sg.first) v = (c == 0 && i < a.N) ? pi_p[i] * Etg[(size_t)sg.tok0 * a.PP + i] : 0.0;
+            else v = (i == c && i < a.N) ? 1.0 : 0.0;
+            P[K][J] = sg.valid ? v : 0.0;
+        }
+}
+
+// The segment setup of a scan: the slot's descriptor, its start operator into P, then the wavefront's block counts (in
+// this order: with the two reductions in front of the start operator the 21-24 state scans spill more registers).
+template <int NT, bool WIDE>
+__device__ __forceinline__ Zip3Segment zip3_segment(double (&P)[NT][NT], const BigArgs &a, const Z2Block &blk, int slot, const Zip3Lane &ln,
+                                                    const double *pi_p, const double *Etg)
+{
+    Zip3Segment s;
+    s.valid = slot < (int)blk.n;
+    // A lane without a segment runs the wavefront's unconditional token loads on another segment's stream: the FIRST
+    // slot of its own wavefront (whose length bounds the wavefront's full blocks: nfull is a minimum over the valid
+    // lanes), not the workgroup's segment 0 - in a packed block (Z2Block::first == 2) that may be a one-column chunk
+    // beside a thousand-column one, and the loads then ran hundreds of bytes past its buffer (found under IMC_GUARD=1).
+    const uint32_t seg = blk.seg0 + (s.valid ? slot : ((slot & ~3) < (int)blk.n ? (slot & ~3) : 0));
+    const SegDesc sd = a.segs[seg];
+    s.len = s.valid ? (int)sd.len : 0;
+    s.first = (sd.first & SEG_FIRST) != 0;
+    s.tok0 = (s.valid && s.first) ? seg_token(sd.obs, WIDE, 0) : 0;
+    s.tokg = (gptr)sd.obs;
+    zip3_start<NT>(P, a, s, ln, pi_p, Etg);
+    s.maxlen = wave_max_i32(s.len);
+    s.nfull = s.maxlen == 0 ? 0 : wave_min_i32(s.valid ? s.len / RESCALE_EVERY : INT_MAX);   // idle wavefronts still join the fold's barriers
+    return s;
+}
+
+// A packed block's (Z2Block::first == 2) output: every slot is a whole one-segment chunk - its vector goes out as it is.
+template <int NT>
+__device__ __forceinline__ void zip3_emit_packed(const BigArgs &a, const Z2Block &blk, const double (&P)[NT][NT], int ex, int b, int slot,
+                                                 const Zip3Lane &ln)
+{
+    constexpr int NP = Zip3Geom<NT>::NP;
+    if (slot < (int)blk.n && ln.r == 0) {
+        const size_t gvp = (size_t)b * a.n_vecs_total + blk.out_vec0 + slot;
+#pragma unroll
+        for (int K = 0; K < NT; ++K)
+            if (4 * K + ln.q < a.N) a.P[gvp * NP + 4 * K + ln.q] = P[K][0];
+        if (ln.q == 0) a.EX[gvp] = ex;
+    }
+}
+
+// A folded block's output, by slot 0: the forward vector (column 0) of a block that starts its chunk, else the operator
+// with one exponent per column.
+template <int NT>
+__device__ __forceinline__ void zip3_emit(const BigArgs &a, const Z2Block &blk, const double (&P)[NT][NT], int ex, int b, int slot,
+                                          const Zip3Lane &ln)
+{
+    constexpr int NP = Zip3Geom<NT>::NP;
+    if (slot != 0) return;
+    const int q = ln.q, r = ln.r;
+    const size_t gv = (size_t)b * a.n_vecs_total + blk.out_vec0;
+    double *Pout = a.P + gv * NP;
+    if (blk.first) {
+        if (r == 0) {
+#pragma unroll
+            for (int K = 0; K < NT; ++K)
+                if (4 * K + q < a.N) Pout[4 * K + q] = P[K][0];
+        }
+        if (q == 0 && r == 0) a.EX[gv] = ex;
+    } else {
+#pragma unroll
+        for (int K = 0; K < NT; ++K)
+#pragma unroll
+            for (int J = 0; J < NT; ++J) {
+                const int i = 4 * K + q, c = 4 * J + r;
+                if (i < a.N && c < a.N) Pout[(size_t)i * NP + c] = P[K][J];
+            }
+        if (q == 0) {
+#pragma unroll
+            for (int J = 0; J < NT; ++J)
+                if (4 * J + r < a.N) a.EX[gv + 4 * J + r] = ex;
+        }
+    }
+}
+
 // ---- fold the workgroup's n segments into one: P_0 <- P_{n-1} ... P_1 P_0 ------------------------------------------------
 // Slot s = 4 * wavefront + block holds segment s's operator P (registers, the layout of an MFMA B operand) and exponent.
 // X: exchange area of Z2SLOTS entries of TOK doubles (the operator table's space once it is dead), xe: Z2SLOTS ints.
@@ -130,21 +306,15 @@ __device__ __forceinline__ void zip3_rescale(double (&P)[NT][NT], int &ex)
 // SLOTS: segments per workgroup of the calling kernel (Z2SLOTS; 16 for the four-wavefront workgroups of 25-32 states,
 // whose stage B then ends at level 4).
 template <int NT, bool TABLE_LIVE, bool RESCALE = true, int SLOTS = Z2SLOTS>
-__device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *X, int *xe, int n, int slot, int wv, int lo, int lx)
+__device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *X, int *xe, int n, int slot, int wv, const Zip3Lane &ln)
 {
-    using Geo = Zip3Geom<NT>;
-    constexpr int TOK = Geo::TOK;
+    constexpr int TOK = Zip3Geom<NT>::TOK;
     if (n <= 1) return;                                     // workgroup-uniform
-    const int lane = threadIdx.x & 63;                      // (wv: this wavefront's index among those that fold together)
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
+    const int bq = ln.bq, lo = ln.lo, lx = ln.lx;           // (wv: this wavefront's index among those that fold together)
     double Q[NT][NT], al[NT];
     auto put = [&](int area) __attribute__((always_inline)) {
-        double *dst = X + (size_t)area * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) dst[Geo::idx(4 * K + q, 4 * J + r)] = P[K][J];
-        if (q == 0 && r == 0) xe[area] = ex;
+        zip3_frag_store<NT>(X + (size_t)area * TOK, P, ln);
+        if (ln.q == 0 && ln.r == 0) xe[area] = ex;
     };
     auto take = [&](int area, bool act) __attribute__((always_inline)) {     // P <- X[area] * P where act
         const double *src = X + (size_t)area * TOK;
@@ -180,11 +350,7 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
     if (wv != 0) return;
     {   // level 3: block b takes the pair (2b, 2b + 1)
         const int lo_w = 2 * bq, hi_w = 2 * bq + 1;
-        const double *src = X + (size_t)(lo_w < nw ? lo_w : 0) * 4 * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) P[K][J] = src[Geo::idx(4 * K + q, 4 * J + r)];
+        zip3_frag_load<NT>(P, X + (size_t)(lo_w < nw ? lo_w : 0) * 4 * TOK, ln);
         ex = xe[(lo_w < nw ? lo_w : 0) * 4];
         take((hi_w < nw ? hi_w : 0) * 4, hi_w < nw);
     }
@@ -217,23 +383,16 @@ __device__ __forceinline__ void zip3_fold(double (&P)[NT][NT], int &ex, double *
 // exponent has a 128-byte slot): a last arriver that shares an XCD with an earlier one must not find a line in that
 // L2 that was fetched before all of its words were written.
 template <int NT, int SLOTS = Z2SLOTS>
-__device__ __forceinline__ void zip3_tail(const BigArgs &a, double (&P)[NT][NT], int &ex, double *X, int *xe, int b, int bx, int slot, int lo, int lx)
+__device__ __forceinline__ void zip3_tail(const BigArgs &a, double (&P)[NT][NT], int &ex, double *X, int *xe, int b, int bx, int slot, const Zip3Lane &ln)
 {
-    using Geo = Zip3Geom<NT>;
-    constexpr int TOK = Geo::TOK;
+    constexpr int TOK = Zip3Geom<NT>::TOK;
     __shared__ int s_last;
     const Z2Tail td = a.tail[bx];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int q = lane >> 4, r = lane & 3;
+    const int tid = threadIdx.x, lane = tid & 63, q = ln.q, r = ln.r;
     const size_t cb = (size_t)b * a.n_chunks + td.chunk;
     if (td.n_units > 1) {                                    // (workgroup-uniform)
         if (slot == 0) {
-            double *dst = a.tailX + (cb * a.tail_stride + td.unit) * TOK;
-#pragma unroll
-            for (int K = 0; K < NT; ++K)
-#pragma unroll
-                for (int J = 0; J < NT; ++J)
-                    __hip_atomic_store(&dst[Geo::idx(4 * K + q, 4 * J + r)], P[K][J], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            zip3_frag_store<NT, true>(a.tailX + (cb * a.tail_stride + td.unit) * TOK, P, ln);
             if (q == 0 && r == 0) __hip_atomic_store(&a.tailE[(cb * a.tail_stride + td.unit) * 32], ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (tid < 64) {                                      // wavefront 0 holds slot 0: it alone stored
@@ -244,16 +403,13 @@ __device__ __forceinline__ void zip3_tail(const BigArgs &a, double (&P)[NT][NT],
         __syncthreads();
         if (!s_last) return;
         const bool valid = slot < (int)td.n_units;
-        const double *src = a.tailX + (cb * a.tail_stride + (valid ? slot : 0)) * TOK;
+        zip3_frag_load<NT, true>(P, a.tailX + (cb * a.tail_stride + (valid ? slot : 0)) * TOK, ln);
 #pragma unroll
         for (int K = 0; K < NT; ++K)
 #pragma unroll
-            for (int J = 0; J < NT; ++J) {
-                const double v = __hip_atomic_load(&src[Geo::idx(4 * K + q, 4 * J + r)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                P[K][J] = valid ? v : 0.0;
-            }
+            for (int J = 0; J < NT; ++J) P[K][J] = valid ? P[K][J] : 0.0;
         ex = __hip_atomic_load(&a.tailE[(cb * a.tail_stride + (valid ? slot : 0)) * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        zip3_fold<NT, true, true, SLOTS>(P, ex, X, xe, (int)td.n_units, slot, tid >> 6, lo, lx);
+        zip3_fold<NT, true, true, SLOTS>(P, ex, X, xe, (int)td.n_units, slot, tid >> 6, ln);
         if (tid == 0) __hip_atomic_store(&a.tail_arrive[cb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (slot == 0) {
@@ -280,23 +436,10 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate3(BigAr
     const int b = blockIdx.y;
     const double *pp = a.params + (size_t)b * a.pstride;
     if (a.params_src) {
-        // small launch: every workgroup fetches the parameter set straight from the caller's mapped staging slot (all of
-        // a lane's loads in flight together: host memory, ~2 us per round trip) into LDS behind the table's lists
+        // small launch: every workgroup fetches the parameter set straight from the caller's mapped staging slot into
+        // LDS behind the table's lists
         double *lp = reinterpret_cast<double *>(reinterpret_cast<char *>(lds) + ((Geo::lds_bytes(a.A) + 15) & ~(size_t)15));
-        const double *src = a.params_src + (size_t)b * a.pstride;
-        for (int k0 = 0; k0 < (int)a.pstride; k0 += 2 * 2 * THREADS) {
-            double2 v[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                v[u] = k < (int)a.pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                if (k < (int)a.pstride) *reinterpret_cast<double2 *>(lp + k) = v[u];
-            }
-        }
+        stage_params_to_lds<2, THREADS>(lp, a.params_src + (size_t)b * a.pstride, (int)a.pstride, tid);
         __syncthreads();
         pp = lp;
     }
@@ -310,8 +453,7 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate3(BigAr
         const int sidx = idx / (NP * NP);
         const int rem = idx - sidx * NP * NP;
         const int i = rem / NP, j = rem - i * NP;
-        if (sidx < a.S) C[(size_t)sidx * TOK + Geo::idx(i, j)] = Etg[(size_t)sidx * a.PP + i] * Tp[(size_t)j * a.PP + i];
-        else C[(size_t)IDENT * TOK + Geo::idx(i, j)] = i == j ? 1.0 : 0.0;
+        C[(size_t)(sidx < a.S ? sidx : IDENT) * TOK + Geo::idx(i, j)] = raw_operator(Etg, Tp, a.PP, sidx, i, j, sidx >= a.S);
     }
     if (tid < a.S) cex[tid] = 0;
     if (tid == 0) cex[IDENT] = 0;
@@ -324,35 +466,28 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate3(BigAr
     // goes to one MFMA block (wavefront w, block b takes the (4w + b)-th token of the depth), and the product is the
     // scan's own step with C_left in the role of P - NT^3 MFMAs per wavefront for four tokens, against ~4800 cycles
     // per token for an element-per-thread product (measured: 2.2 us per token, a fifth of the whole kernel at 44 tokens).
+    const Zip3Lane ln = zip3_lane<NT>(tid & 63);
+    const int lo = ln.lo, lx = ln.lx;
     {
-        const int lane0 = tid & 63;
-        const int q0 = lane0 >> 4, b0 = (lane0 >> 2) & 3, r0 = lane0 & 3, wv = tid >> 6;
-        const int lo0 = (q0 * 4 + r0) * Geo::NTE, lx0 = q0 * 4 + r0;
+        const int wv = tid >> 6;
         for (int d = 0; d < a.tab_nlvl; ++d) {
             const int o0 = m_lvl[d], o1 = m_lvl[d + 1];
             for (int base = o0; base < o1; base += Z2SLOTS) {
                 if (base + wv * 4 >= o1) continue;               // nothing for this wavefront (wavefront-uniform)
-                const int ti = base + wv * 4 + b0;
+                const int ti = base + wv * 4 + ln.bq;
                 const bool have = ti < o1;
                 const int z = have ? m_order[ti] : IDENT;
                 const int zl = have ? m_left[z] : IDENT, zr = have ? m_right[z] : IDENT;
                 const double *Cl = C + (size_t)zl * TOK, *Cr = C + (size_t)zr * TOK;
                 double Bt[NT][NT], Out[NT][NT], arow0[NT];
-#pragma unroll
-                for (int K = 0; K < NT; ++K)
-#pragma unroll
-                    for (int J = 0; J < NT; ++J) Bt[K][J] = Cl[Geo::idx(4 * K + q0, 4 * J + r0)];
-                zip3_load_row<NT>(arow0, Cr, 0, lo0, lx0);
-                zip3_step<NT>(Bt, Out, Cr, Cr, arow0, lo0, lx0);
+                zip3_frag_load<NT>(Bt, Cl, ln);
+                zip3_load_row<NT>(arow0, Cr, 0, lo, lx);
+                zip3_step<NT>(Bt, Out, Cr, Cr, arow0, lo, lx);
                 int e2 = 0;
                 zip3_rescale<NT>(Out, e2);
                 if (have) {
-                    double *Cz = C + (size_t)z * TOK;
-#pragma unroll
-                    for (int K = 0; K < NT; ++K)
-#pragma unroll
-                        for (int J = 0; J < NT; ++J) Cz[Geo::idx(4 * K + q0, 4 * J + r0)] = Out[K][J];
-                    if (q0 == 0 && r0 == 0) cex[z] = cex[zl] + cex[zr] + e2;
+                    zip3_frag_store<NT>(C + (size_t)z * TOK, Out, ln);
+                    if (ln.q == 0 && ln.r == 0) cex[z] = cex[zl] + cex[zr] + e2;
                 }
             }
             __syncthreads();
@@ -360,44 +495,14 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate3(BigAr
     }
 
     // ---- scan: one segment per MFMA block ----
-    const int lane = tid & 63;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
     const Z2Block blk = a.blocks[blockIdx.x];
-    const int slot = (tid >> 6) * 4 + bq;                   // 0..Z2SLOTS-1 within the workgroup
-    const bool valid = slot < (int)blk.n;
-    // A lane without a segment runs the wavefront's unconditional token loads on another segment's stream: the FIRST
-    // slot of its own wavefront (whose length bounds the wavefront's full blocks: nfull is a minimum over the valid
-    // lanes), not the workgroup's segment 0 - in a packed block (Z2Block::first == 2) that may be a one-column chunk
-    // beside a thousand-column one, and the loads then ran hundreds of bytes past its buffer (found under IMC_GUARD=1).
-    const uint32_t seg = blk.seg0 + (valid ? slot : ((slot & ~3) < (int)blk.n ? (slot & ~3) : 0));
-    const SegDesc sd = a.segs[seg];
-    const int len = valid ? (int)sd.len : 0;
-    const bool first = (sd.first & SEG_FIRST) != 0;
-    const uint8_t *tokp = sd.obs;
-    // (token loads as GLOBAL loads: through the descriptor's generic pointer they are flat loads, which also count
-    // against the LDS counter and turn every LDS wait behind them into a full one)
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(1))) u32x4 *gptr4;
-    const __attribute__((address_space(1))) uint8_t *tokg = (const __attribute__((address_space(1))) uint8_t *)tokp;
-
+    const int slot = (tid >> 6) * 4 + ln.bq;                // 0..Z2SLOTS-1 within the workgroup
     double P[NT][NT], Q[NT][NT];
-    {
-        const int tok0 = (valid && first) ? (int)tokp[0] : 0;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) {
-                const int i = 4 * K + q, c = 4 * J + r;
-                double v;
-                if (first) v = (c == 0 && i < a.N) ? pi_p[i] * Etg[(size_t)tok0 * a.PP + i] : 0.0;
-                else v = (i == c && i < a.N) ? 1.0 : 0.0;
-                P[K][J] = valid ? v : 0.0;
-            }
-    }
+    const Zip3Segment sg = zip3_segment<NT, false>(P, a, blk, slot, ln, pi_p, Etg);
+    const int len = sg.len, maxlen = sg.maxlen, nfull = sg.nfull;
+    const bool first = sg.first;
+    const gptr tokg = sg.tokg;
     int ex = 0;
-    const int maxlen = wave_max_i32(len);
-    const int nfull = maxlen == 0 ? 0 : wave_min_i32(valid ? len / RESCALE_EVERY : INT_MAX);   // idle wavefronts still join the fold's barriers
     // a step pair; `arow` carries the prefetched first tile-row of t0's operator in and of tn's operator out
     double arow[NT];
     auto two_steps = [&](int t0, int t1, int tn) __attribute__((always_inline)) {
@@ -449,46 +554,14 @@ __global__ __launch_bounds__(Z2WAVES * 64, Z2WAVES / 4) void k_zpropagate3(BigAr
         masked_block(bi, min(RESCALE_EVERY, (maxlen - bi * RESCALE_EVERY + 1) & ~1));
     zip3_rescale<NT>(P, ex);
 
-    // ---- packed block (Z2Block::first == 2): every slot is a whole one-segment chunk - its vector goes out as it is ----
-    if (blk.first == 2) {                                   // (workgroup-uniform: nobody reaches the fold's barriers)
-        if (slot < (int)blk.n && r == 0) {
-            const size_t gvp = (size_t)b * a.n_vecs_total + blk.out_vec0 + slot;
-#pragma unroll
-            for (int K = 0; K < NT; ++K)
-                if (4 * K + q < a.N) a.P[gvp * NP + 4 * K + q] = P[K][0];
-            if (q == 0) a.EX[gvp] = ex;
-        }
+    if (blk.first == 2) {                                   // a packed block (workgroup-uniform: nobody reaches the fold's barriers)
+        zip3_emit_packed<NT>(a, blk, P, ex, b, slot, ln);
         return;
     }
 
     // ---- fold the workgroup's segments into one (zip3_fold): the operator table is dead once every wavefront is
     // here; its space becomes the exchange area ----
-    zip3_fold<NT, true>(P, ex, C, cex, (int)blk.n, slot, tid >> 6, lo, lx);
-
-    if (slot == 0) {
-        const size_t gv = (size_t)b * a.n_vecs_total + blk.out_vec0;
-        double *Pout = a.P + gv * NP;
-        if (blk.first) {
-            if (r == 0) {
-#pragma unroll
-                for (int K = 0; K < NT; ++K)
-                    if (4 * K + q < a.N) Pout[4 * K + q] = P[K][0];
-            }
-            if (q == 0 && r == 0) a.EX[gv] = ex;
-        } else {
-#pragma unroll
-            for (int K = 0; K < NT; ++K)
-#pragma unroll
-                for (int J = 0; J < NT; ++J) {
-                    const int i = 4 * K + q, c = 4 * J + r;
-                    if (i < a.N && c < a.N) Pout[(size_t)i * NP + c] = P[K][J];
-                }
-            if (q == 0) {
-#pragma unroll
-                for (int J = 0; J < NT; ++J)
-                    if (4 * J + r < a.N) a.EX[gv + 4 * J + r] = ex;
-            }
-        }
-    }
-    if (a.tail) zip3_tail<NT>(a, P, ex, C, cex, b, (int)blockIdx.x, slot, lo, lx);
+    zip3_fold<NT, true>(P, ex, C, cex, (int)blk.n, slot, tid >> 6, ln);
+    zip3_emit<NT>(a, blk, P, ex, b, slot, ln);
+    if (a.tail) zip3_tail<NT>(a, P, ex, C, cex, b, (int)blockIdx.x, slot, ln);
 }

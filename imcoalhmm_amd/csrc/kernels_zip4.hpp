@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_z4_raw(BigArgs a)
     const int entry = sidx < a.S ? sidx : a.A;
     for (int idx = threadIdx.x; idx < NP * NP; idx += blockDim.x) {
         const int i = idx / NP, j = idx - i * NP;
-        Gt[(size_t)entry * TOK + Geo::idx(i, j)] = sidx < a.S ? Etg[(size_t)sidx * a.PP + i] * Tp[(size_t)j * a.PP + i] : (i == j ? 1.0 : 0.0);
+        Gt[(size_t)entry * TOK + Geo::idx(i, j)] = raw_operator(Etg, Tp, a.PP, sidx, i, j, sidx >= a.S);
     }
     if (threadIdx.x == 0) Gc[entry] = 0;
 }
@@ -107,9 +107,9 @@ __global__ __launch_bounds__(64) void k_z4_level(BigArgs a, int first, int count
 {
     using Geo = Zip3Geom<NT>;
     constexpr int TOK = Geo::TOK;
-    const int b = blockIdx.y, lane = threadIdx.x;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const int b = blockIdx.y;
+    const Zip3Lane ln = zip3_lane<NT>(threadIdx.x);
+    const int q = ln.q, bq = ln.bq, r = ln.r, lo = ln.lo, lx = ln.lx;
     double *Gt = a.Ctab + (size_t)b * (a.A + 1) * TOK;
     int *Gc = a.cex + (size_t)b * (a.A + 1);
     const int ti = blockIdx.x * 4 + bq;
@@ -118,10 +118,7 @@ __global__ __launch_bounds__(64) void k_z4_level(BigArgs a, int first, int count
     const int z = td.x, zl = td.y, zr = td.z;
     const double *Gl = Gt + (size_t)zl * TOK, *Gr = Gt + (size_t)zr * TOK;
     double Bt[NT][NT], Ar[NT][NT], Out[NT][NT];
-#pragma unroll
-    for (int K = 0; K < NT; ++K)
-#pragma unroll
-        for (int J = 0; J < NT; ++J) Bt[K][J] = Gl[Geo::idx(4 * K + q, 4 * J + r)];
+    zip3_frag_load<NT>(Bt, Gl, ln);
 #pragma unroll
     for (int I = 0; I < NT; ++I) zip4_load_row_global<NT>(Ar[I], Gr, I, lo, lx);
     const int cel = Gc[zl], cer = Gc[zr];
@@ -129,11 +126,7 @@ __global__ __launch_bounds__(64) void k_z4_level(BigArgs a, int first, int count
     int e2 = 0;
     zip3_rescale<NT>(Out, e2);
     if (have) {
-        double *Gz = Gt + (size_t)z * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) Gz[Geo::idx(4 * K + q, 4 * J + r)] = Out[K][J];
+        zip3_frag_store<NT>(Gt + (size_t)z * TOK, Out, ln);
         if (q == 0 && r == 0) Gc[z] = cel + cer + e2;
     }
 }
@@ -165,8 +158,8 @@ __device__ __forceinline__ void z4_split_entry(const BigArgs &a, double *Gt, int
     using Geo = Zip3Geom<NT>;
     constexpr int TOK = Geo::TOK, NPASS = (NT + 3) / 4;
     const int lane = threadIdx.x & 63;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const Zip3Lane ln = zip3_lane<NT>(lane);
+    const int q = ln.q, bq = ln.bq, r = ln.r, lo = ln.lo, lx = ln.lx;
     const int IDENT = a.A;
     // this lane's column tiles: where element (4K + q, 4J + r) of an entry lives is toff + K * tstr (Zip3Geom::idx)
     int tcol[NPASS], toff[NPASS], tstr[NPASS];
@@ -182,9 +175,7 @@ __device__ __forceinline__ void z4_split_entry(const BigArgs &a, double *Gt, int
         tstr[p] = mainp ? 16 * Geo::NTE : 16;
     }
     auto leaf = [&](int tok, int i, int j) __attribute__((always_inline)) {
-        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
-        const double v = Etg[(size_t)(tok == IDENT ? 0 : tok) * a.PP + i] * Tp[(size_t)j * a.PP + i];
-        return tok == IDENT ? (i == j ? 1.0 : 0.0) : v;
+        return raw_operator(lp + a.PP + (size_t)a.PP * a.PP, lp + a.PP, a.PP, tok, i, j, tok == IDENT);
     };
     auto expo = [&](int tok) __attribute__((always_inline)) { if constexpr (FIRST) return 0; else return Gc[tok]; };
     auto load_B = [&](double (&Bt)[NPASS][NT], int tok) __attribute__((always_inline)) {
@@ -276,6 +267,28 @@ __device__ __forceinline__ void z4_split_entry(const BigArgs &a, double *Gt, int
     if (lane == 0) Gc[z] = eL + eR + e;
 }
 
+// The first table launch of an evaluation (k_z4_level2 / k_z4_level3<., true>) leaves behind what the later ones read: workgroup 0
+// copies the parameter set `lp` (LDS) to a.params, and the raw symbols' entries and the identity are dealt over the workgroups.
+template <int NT, int THREADS>
+__device__ __forceinline__ void z4_publish_raw(const BigArgs &a, double *Gt, int *Gc, const double *lp, int b, int tid)
+{
+    using Geo = Zip3Geom<NT>;
+    constexpr int NP = Geo::NP;
+    if (blockIdx.x == 0) {                                                // (workgroup-uniform)
+        double *dp = const_cast<double *>(a.params) + (size_t)b * a.pstride;
+        for (int k = tid * 2; k < (int)a.pstride; k += 2 * THREADS) *reinterpret_cast<double2 *>(dp + k) = *reinterpret_cast<const double2 *>(lp + k);
+    }
+    const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
+    for (int s = blockIdx.x; s <= a.S; s += gridDim.x) {
+        const int entry = s < a.S ? s : a.A;
+        for (int idx = tid; idx < NP * NP; idx += THREADS) {
+            const int i = idx / NP, j = idx - i * NP;
+            Gt[(size_t)entry * Geo::TOK + Geo::idx(i, j)] = raw_operator(Etg, Tp, a.PP, s, i, j, s >= a.S);
+        }
+        if (tid == 0) Gc[entry] = 0;
+    }
+}
+
 // TWO dictionary depths per launch.  A token of the second depth has at least one child in the first, which a sibling
 // workgroup of the same launch is only just building - so the wavefront RECOMPUTES that child from the grandchildren
 // (both older than the launch), keeps the product in registers (a left child: a result tile is already in the layout
@@ -302,13 +315,13 @@ template <int NT, bool FIRST, int SPLIT = 0>
 __global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs a, const int4 *desc2, int first, int count, const double *params_src)
 {
     using Geo = Zip3Geom<NT>;
-    constexpr int TOK = Geo::TOK, NP = Geo::NP, WAVES = SPLIT ? SPLIT : 1, THREADS = WAVES * 64;
+    constexpr int TOK = Geo::TOK, WAVES = SPLIT ? SPLIT : 1, THREADS = WAVES * 64;
     // SPLIT = 0: one entry per MFMA block, D layout in, A rows out; else one entry per wavefront
     __shared__ __attribute__((aligned(16))) double turn[(SPLIT ? WAVES : 4) * TOK];
     extern __shared__ __attribute__((aligned(16))) double rawtab[];        // FIRST: the parameter set (a.pstride doubles)
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const Zip3Lane ln = zip3_lane<NT>(tid & 63);
+    const int q = ln.q, bq = ln.bq, r = ln.r, lo = ln.lo, lx = ln.lx;
     double *Gt = a.Ctab + (size_t)b * (a.A + 1) * TOK;
     int *Gc = a.cex + (size_t)b * (a.A + 1);
     const int IDENT = a.A;
@@ -319,40 +332,9 @@ __global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs 
         if (wti < count) { e0 = desc2[2 * (first + wti)]; e1 = desc2[2 * (first + wti) + 1]; }
     }
     // FIRST: the parameters and the table's raw entries for the launches that follow (the split form writes them behind its own entry)
-    auto publish = [&]() __attribute__((always_inline)) {
-        const double *lp = rawtab;
-        if (blockIdx.x == 0) {                                            // (workgroup-uniform)
-            double *dp = const_cast<double *>(a.params) + (size_t)b * a.pstride;
-            for (int k = tid * 2; k < (int)a.pstride; k += 2 * THREADS) *reinterpret_cast<double2 *>(dp + k) = *reinterpret_cast<const double2 *>(lp + k);
-        }
-        // the table's raw entries and the identity, dealt over the launch's workgroups (later launches read them)
-        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
-        for (int s = blockIdx.x; s <= a.S; s += gridDim.x) {
-            double *Gz = Gt + (size_t)(s < a.S ? s : IDENT) * TOK;
-            for (int idx = tid; idx < NP * NP; idx += THREADS) {
-                const int i = idx / NP, j = idx - i * NP;
-                Gz[Geo::idx(i, j)] = s < a.S ? Etg[(size_t)s * a.PP + i] * Tp[(size_t)j * a.PP + i] : (i == j ? 1.0 : 0.0);
-            }
-            if (tid == 0) Gc[s < a.S ? s : IDENT] = 0;
-        }
-    };
+    auto publish = [&]() __attribute__((always_inline)) { z4_publish_raw<NT, THREADS>(a, Gt, Gc, rawtab, b, tid); };
     if constexpr (FIRST) {
-        const double *src = params_src + (size_t)b * a.pstride;
-        double *lp = rawtab;                                               // a.pstride doubles (even)
-        // (all of a lane's loads in flight together: `src` is host memory, ~2 us per round trip over PCIe)
-        for (int k0 = 0; k0 < (int)a.pstride; k0 += 8 * 2 * THREADS) {
-            double2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                v[u] = k < (int)a.pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                if (k < (int)a.pstride) *reinterpret_cast<double2 *>(lp + k) = v[u];
-            }
-        }
+        stage_params_to_lds<8, THREADS>(rawtab, params_src + (size_t)b * a.pstride, (int)a.pstride, tid);   // a.pstride doubles (even)
         if constexpr (WAVES > 1) __syncthreads();
         else wave_fence();
         if constexpr (SPLIT == 0) publish();
@@ -385,20 +367,17 @@ __global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs 
     // or the identity, formed on the fly from the parameters in LDS
     const double *lp = rawtab;
     auto leaf = [&](int tok, int i, int j) __attribute__((always_inline)) {
-        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
-        const double v = Etg[(size_t)(tok == IDENT ? 0 : tok) * a.PP + i] * Tp[(size_t)j * a.PP + i];
-        return tok == IDENT ? (i == j ? 1.0 : 0.0) : v;
+        return raw_operator(lp + a.PP + (size_t)a.PP * a.PP, lp + a.PP, a.PP, tok, i, j, tok == IDENT);
     };
     auto expo = [&](int tok) __attribute__((always_inline)) { if constexpr (FIRST) return 0; else return Gc[tok]; };
     auto load_B = [&](double (&Bt)[NT][NT], int tok) __attribute__((always_inline)) {
         const double *G = Gt + (size_t)tok * TOK;
+        if constexpr (FIRST) {
 #pragma unroll
-        for (int K = 0; K < NT; ++K)
+            for (int K = 0; K < NT; ++K)
 #pragma unroll
-            for (int J = 0; J < NT; ++J) {
-                if constexpr (FIRST) Bt[K][J] = leaf(tok, 4 * K + q, 4 * J + r);
-                else Bt[K][J] = G[Geo::idx(4 * K + q, 4 * J + r)];
-            }
+                for (int J = 0; J < NT; ++J) Bt[K][J] = leaf(tok, 4 * K + q, 4 * J + r);
+        } else zip3_frag_load<NT>(Bt, G, ln);
     };
     auto load_A = [&](double (&Ar)[NT][NT], int tok) __attribute__((always_inline)) {     // Ar[I][K] = C[4I + r][4K + q]
         const double *G = Gt + (size_t)tok * TOK;
@@ -438,10 +417,7 @@ __global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs 
         eR = expo(t0) + expo(t1);
         zip4_step_regs<NT>(Bt, Out, Ar);
         double *mine = turn + bq * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) mine[Geo::idx(4 * K + q, 4 * J + r)] = Out[K][J];
+        zip3_frag_store<NT>(mine, Out, ln);
         wave_fence();
 #pragma unroll
         for (int I = 0; I < NT; ++I) zip3_load_row<NT>(R[I], mine, I, lo, lx);
@@ -455,11 +431,7 @@ __global__ __launch_bounds__((SPLIT ? SPLIT : 1) * 64) void k_z4_level2(BigArgs 
     int e2 = 0;
     zip3_rescale<NT>(Out, e2);
     if (have) {
-        double *Gz = Gt + (size_t)z * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) Gz[Geo::idx(4 * K + q, 4 * J + r)] = Out[K][J];
+        zip3_frag_store<NT>(Gt + (size_t)z * TOK, Out, ln);
         if (q == 0 && r == 0) Gc[z] = eL + eR + e2;
     }
 }
@@ -484,11 +456,11 @@ template <int NT, bool FIRST>
 __global__ __launch_bounds__(Z4L3_WAVES * 64, 3) void k_z4_level3(BigArgs a, const int4 *desc3, int first, int count, const double *params_src)
 {
     using Geo = Zip3Geom<NT>;
-    constexpr int TOK = Geo::TOK, NP = Geo::NP, THREADS = Z4L3_WAVES * 64;
+    constexpr int TOK = Geo::TOK, THREADS = Z4L3_WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) double l3lds[];         // [waves][4][TOK] exchange areas | [waves][4] ints | FIRST: parameters
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const int b = blockIdx.y, tid = threadIdx.x, wv = tid >> 6;
+    const Zip3Lane ln = zip3_lane<NT>(tid & 63);
+    const int q = ln.q, bq = ln.bq, r = ln.r, lo = ln.lo, lx = ln.lx;
     double *Gt = a.Ctab + (size_t)b * (a.A + 1) * TOK;
     int *Gc = a.cex + (size_t)b * (a.A + 1);
     const int IDENT = a.A;
@@ -497,37 +469,9 @@ __global__ __launch_bounds__(Z4L3_WAVES * 64, 3) void k_z4_level3(BigArgs a, con
     int *xe = reinterpret_cast<int *>(l3lds + (size_t)Z4L3Geom<NT>::AREAS * TOK) + wv * 4;
     const double *lp = l3lds + Z4L3Geom<NT>::PARAMS_AT;                   // FIRST: a.pstride doubles behind the ints
     if constexpr (FIRST) {
-        const double *src = params_src + (size_t)b * a.pstride;
-        double *lpw = const_cast<double *>(lp);
-        // (all of a lane's loads in flight together: `src` is host memory, ~2 us per round trip over PCIe)
-        for (int k0 = 0; k0 < (int)a.pstride; k0 += 2 * 2 * THREADS) {
-            double2 v[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                v[u] = k < (int)a.pstride ? *reinterpret_cast<const double2 *>(src + k) : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = k0 + (u * THREADS + tid) * 2;
-                if (k < (int)a.pstride) *reinterpret_cast<double2 *>(lpw + k) = v[u];
-            }
-        }
+        stage_params_to_lds<2, THREADS>(const_cast<double *>(lp), params_src + (size_t)b * a.pstride, (int)a.pstride, tid);
         __syncthreads();
-        if (blockIdx.x == 0) {
-            double *dp = const_cast<double *>(a.params) + (size_t)b * a.pstride;
-            for (int k = tid * 2; k < (int)a.pstride; k += 2 * THREADS) *reinterpret_cast<double2 *>(dp + k) = *reinterpret_cast<const double2 *>(lp + k);
-        }
-        // the table's raw entries and the identity, dealt over the launch's workgroups (later launches read them)
-        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
-        for (int s = blockIdx.x; s <= a.S; s += gridDim.x) {
-            double *Gz = Gt + (size_t)(s < a.S ? s : IDENT) * TOK;
-            for (int idx = tid; idx < NP * NP; idx += THREADS) {
-                const int i = idx / NP, j = idx - i * NP;
-                Gz[Geo::idx(i, j)] = s < a.S ? Etg[(size_t)s * a.PP + i] * Tp[(size_t)j * a.PP + i] : (i == j ? 1.0 : 0.0);
-            }
-            if (tid == 0) Gc[s < a.S ? s : IDENT] = 0;
-        }
+        z4_publish_raw<NT, THREADS>(a, Gt, Gc, lp, b, tid);
     }
     const int ti = blockIdx.x * Z4L3_WAVES + wv;                          // (wavefront-uniform)
     if (ti >= count) return;
@@ -538,21 +482,24 @@ __global__ __launch_bounds__(Z4L3_WAVES * 64, 3) void k_z4_level3(BigArgs a, con
 #pragma unroll
     for (int k = 1; k < 4; ++k) { t0 = bq == k ? leaves[2 * k] : t0; t1 = bq == k ? leaves[2 * k + 1] : t1; }
     auto leaf = [&](int tok, int i, int j) __attribute__((always_inline)) {
-        const double *Tp = lp + a.PP, *Etg = lp + a.PP + (size_t)a.PP * a.PP;
-        const double v = Etg[(size_t)(tok == IDENT ? 0 : tok) * a.PP + i] * Tp[(size_t)j * a.PP + i];
-        return tok == IDENT ? (i == j ? 1.0 : 0.0) : v;
+        return raw_operator(lp + a.PP + (size_t)a.PP * a.PP, lp + a.PP, a.PP, tok, i, j, tok == IDENT);
     };
     double Bt[NT][NT], P[NT][NT];
     int ex;
     {
         const double *G0 = Gt + (size_t)t0 * TOK, *G1 = Gt + (size_t)t1 * TOK;
+        if constexpr (FIRST) {
 #pragma unroll
-        for (int K = 0; K < NT; ++K)
+            for (int K = 0; K < NT; ++K)
 #pragma unroll
-            for (int J = 0; J < NT; ++J) {
-                if constexpr (FIRST) Bt[K][J] = leaf(t0, 4 * K + q, 4 * J + r);
-                else Bt[K][J] = G0[Geo::idx(4 * K + q, 4 * J + r)];
-            }
+                for (int J = 0; J < NT; ++J) Bt[K][J] = leaf(t0, 4 * K + q, 4 * J + r);
+        } else {
+            // (zip3_frag_load's loop in place: through the helper the 12- and 16-state instances lose a wavefront of occupancy)
+#pragma unroll
+            for (int K = 0; K < NT; ++K)
+#pragma unroll
+                for (int J = 0; J < NT; ++J) Bt[K][J] = G0[Geo::idx(4 * K + q, 4 * J + r)];
+        }
         if constexpr (FIRST) ex = 0;
         else ex = Gc[t0] + Gc[t1];
         // P = C_t1 * C_t0, the A operand's tile-rows one row ahead of their use (ten registers instead of fifty)
@@ -578,14 +525,10 @@ __global__ __launch_bounds__(Z4L3_WAVES * 64, 3) void k_z4_level3(BigArgs a, con
     }
     // (no rescale between the three levels: products of a few normalised operators stay far inside the exponent range,
     // and powers of two scale exactly - the entry's bits are those of the one-depth-per-launch build)
-    zip3_fold<NT, false, false>(P, ex, X, xe, 4, bq, 0, lo, lx);          // 1 -> 0, 3 -> 2, then 2 -> 0
+    zip3_fold<NT, false, false>(P, ex, X, xe, 4, bq, 0, ln);          // 1 -> 0, 3 -> 2, then 2 -> 0
     zip3_rescale<NT>(P, ex);
     if (bq == 0) {
-        double *Gz = Gt + (size_t)z * TOK;
-#pragma unroll
-        for (int K = 0; K < NT; ++K)
-#pragma unroll
-            for (int J = 0; J < NT; ++J) Gz[Geo::idx(4 * K + q, 4 * J + r)] = P[K][J];
+        zip3_frag_store<NT>(Gt + (size_t)z * TOK, P, ln);
         if (q == 0 && r == 0) Gc[z] = ex;
     }
 }
@@ -716,30 +659,21 @@ __global__ __launch_bounds__(Zip4Shape<NT>::WAVES * 64, Zip4Shape<NT>::WAVES / 4
 
     // ---- scan: one segment per MFMA block ----
     Z4_STAMP(1);
-    const int lane = tid & 63;
-    const int q = lane >> 4, bq = (lane >> 2) & 3, r = lane & 3;
-    const int lo = (q * 4 + r) * Geo::NTE, lx = q * 4 + r;
+    const Zip3Lane ln = zip3_lane<NT>(tid & 63);
+    const int lo = ln.lo, lx = ln.lx;
     const Z2Block blk = a.blocks[bx];
-    const int slot = (tid >> 6) * 4 + bq;                   // 0..SLOTS-1 within the workgroup
+    const int slot = (tid >> 6) * 4 + ln.bq;                // 0..SLOTS-1 within the workgroup
+    // zip3_segment's text in place, to be kept in step with it by hand: through the helper this kernel's hybrid form
+    // measured 0.3 - 0.6 us slower than before (profiles/blocked_scaffold_ab.txt).  The rule for an idle lane's stream
+    // and the reason for it stand at zip3_segment.
+    const int q = ln.q, r = ln.r;
     const bool valid = slot < (int)blk.n;
-    // A lane without a segment runs the wavefront's unconditional token loads on another segment's stream: the FIRST
-    // slot of its own wavefront (whose length bounds the wavefront's full blocks: nfull is a minimum over the valid
-    // lanes), not the workgroup's segment 0 - in a packed block (Z2Block::first == 2) that may be a one-column chunk
-    // beside a thousand-column one, and the loads then ran hundreds of bytes past its buffer (found under IMC_GUARD=1).
     const uint32_t seg = blk.seg0 + (valid ? slot : ((slot & ~3) < (int)blk.n ? (slot & ~3) : 0));
     const SegDesc sd = a.segs[seg];
     const int len = valid ? (int)sd.len : 0;
     const bool first = (sd.first & SEG_FIRST) != 0;
     const uint8_t *tokp = sd.obs;
-    // (token loads as GLOBAL loads: through the generic pointer of the segment descriptor they are flat loads, which
-    // count against the LDS counter too and can return out of order with the operand refills - every wait behind one
-    // becomes a full one)
-    typedef const __attribute__((address_space(1))) uint8_t *gptr;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(1))) u32x4 *gptr4;
-    typedef const __attribute__((address_space(1))) uint32_t *gptr1;
     const gptr tokg = (gptr)tokp;
-
     double P[NT][NT], Q[NT][NT];
     {
         const int tok0 = (valid && first) ? seg_token(tokp, WIDE, 0) : 0;
@@ -906,50 +840,26 @@ __global__ __launch_bounds__(Zip4Shape<NT>::WAVES * 64, Zip4Shape<NT>::WAVES / 4
     if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024 && blockIdx.y == 0) g_z4_dbg[1024 * 8 + blockIdx.x * 8 + (threadIdx.x >> 6)] = wall_clock64();
 #endif
 
-    // ---- packed block (Z2Block::first == 2): every slot is a whole one-segment chunk - its vector goes out as it is ----
-    if (blk.first == 2) {                                   // (workgroup-uniform: nobody reaches the fold's barriers)
-        if (valid && r == 0) {
+    if (blk.first == 2) {                                   // a packed block (workgroup-uniform: nobody reaches the fold's barriers)
+        // (zip3_emit_packed's text in place: with both output helpers the 21-24 state, 16-bit, streamed instance spills one register more)
+        if (valid && ln.r == 0) {
             const size_t gvp = (size_t)b * a.n_vecs_total + blk.out_vec0 + slot;
 #pragma unroll
             for (int K = 0; K < NT; ++K)
-                if (4 * K + q < a.N) a.P[gvp * NP + 4 * K + q] = P[K][0];
-            if (q == 0) a.EX[gvp] = ex;
+                if (4 * K + ln.q < a.N) a.P[gvp * NP + 4 * K + ln.q] = P[K][0];
+            if (ln.q == 0) a.EX[gvp] = ex;
         }
         return;
     }
 
     // ---- fold the workgroup's segments into one (zip3_fold; the LDS entries become the exchange area; the streamed
     // form keeps nothing in LDS during the scan, so its wavefronts start folding as they finish) ----
-    zip3_fold<NT, HYB, true, SLOTS>(P, ex, C, xex, (int)blk.n, slot, tid >> 6, lo, lx);
+    zip3_fold<NT, HYB, true, SLOTS>(P, ex, C, xex, (int)blk.n, slot, tid >> 6, ln);
 
     Z4_STAMP(5);
 #ifdef IMC_Z4_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 1024 && blockIdx.y == 0) g_z4_dbg[blockIdx.x * 8 + 7] = (long long)nfull * 1000000 + maxlen;
 #endif
-    if (slot == 0) {
-        const size_t gv = (size_t)b * a.n_vecs_total + blk.out_vec0;
-        double *Pout = a.P + gv * NP;
-        if (blk.first) {
-            if (r == 0) {
-#pragma unroll
-                for (int K = 0; K < NT; ++K)
-                    if (4 * K + q < a.N) Pout[4 * K + q] = P[K][0];
-            }
-            if (q == 0 && r == 0) a.EX[gv] = ex;
-        } else {
-#pragma unroll
-            for (int K = 0; K < NT; ++K)
-#pragma unroll
-                for (int J = 0; J < NT; ++J) {
-                    const int i = 4 * K + q, c = 4 * J + r;
-                    if (i < a.N && c < a.N) Pout[(size_t)i * NP + c] = P[K][J];
-                }
-            if (q == 0) {
-#pragma unroll
-                for (int J = 0; J < NT; ++J)
-                    if (4 * J + r < a.N) a.EX[gv + 4 * J + r] = ex;
-            }
-        }
-    }
-    if (a.tail) zip3_tail<NT, SLOTS>(a, P, ex, C, xex, b, bx, slot, lo, lx);
+    zip3_emit<NT>(a, blk, P, ex, b, slot, ln);
+    if (a.tail) zip3_tail<NT, SLOTS>(a, P, ex, C, xex, b, bx, slot, ln);
 }
